@@ -23,10 +23,16 @@ Launch: `python bench.py --gpus N` spawns N ranks under torch.distributed.run it
 torch / HIP import); under torch.distributed.run (WORLD_SIZE set) --gpus must equal the world
 size.  The barrier and the max-over-ranks reduction of the timed region use torch.distributed.
 
-Printed JSON line: the metric, a "roofline" object for the dominant kernel (the encode; HIP
-events on the launching stream, on serial launches after the timed region) and a
-"cpu_baseline" object (the C restatement under oracle/, run on the host cores of rank 0 at
-N = 1: warm-up + median of 5, which doubles as the bit-exactness check of the root).
+Printed JSON line: the metric ("value", with "ms_per_step" = the timed region / --steps).  A plain
+run does nothing else: set-up, --warmup untimed steps, --steps timed steps, the line.  With --full
+the line also carries a "roofline" object for the dominant kernel (the encode; HIP events on the
+launching stream, on serial launches after the timed region), one commitment's "latency", the
+"verify" timing, the sharded engine's N = 1 figure and a "cpu_baseline" object (the C restatement
+under oracle/, run on the host cores of rank 0 at N = 1: warm-up + median of 5, which doubles as
+the bit-exactness check of the root, the "parity_*" flags).
+
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy
+(dump_outputs below); the inputs are seeded, so two builds can be compared array for array.
 """
 import argparse
 import glob
@@ -141,6 +147,18 @@ def parse():
                          "Merlin transcript of one overlaps the kernels of the others.  0: 16, 20 for "
                          "--code sdig, or 4 for --code pos (a 1 GiB request's 2.3 GiB codeword per slot: deeper "
                          "pipelines only contend for HBM)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything else the line can carry: the "
+                         "roofline launches, one commitment's latency, the verifier, the PCIe copy rates of a host "
+                         "input, the sharded engine's N = 1 figure, and the oracle's CPU baseline and parity "
+                         "flags.  Without it a run sets up, warms up, times --steps steps and prints the line, "
+                         "and --cpu-baseline, --verify-reps, --roofline-steps, --sharded-n1 and --no-prof have "
+                         "nothing to act on")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (root, "
+                         "proof parts, opened columns, or the encoded rows) as DIR/<name>.npy: the little-endian "
+                         "32-bit words of every u64 limb as float64, digests byte by byte as float32; at most "
+                         "64 MB in all (a larger output is a fixed, seeded sample of its words)")
     args = ap.parse_args()
     if args.code in ("sdig", "encode", "sdig-encode"):
         args.mode = "replicas"  # cfg2 / cfg4 run as independent steps per rank
@@ -277,6 +295,49 @@ def job_throughput(n_per_step, steps, world, elapsed):
     return n_per_step * steps * world / elapsed
 
 
+# --dump-outputs, replicas: the worker slot that runs the last timed step, set as that step is handed
+# out; a workload's step(slot) keeps what it returns to its caller only then, so every other timed
+# step runs exactly as without the option
+KEEP_SLOT = [None]
+DUMP_BUDGET = 60 << 20  # bytes of .npy payload over all arrays of one --dump-outputs (the limit is 64 MB)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write {name: array} as path/<name>.npy.  u64 limbs go out as their little-endian
+    32-bit words in float64 and digest bytes (uint8) one per float32, so every value is exact.  The
+    arrays share DUMP_BUDGET, smallest first; one larger than its share is sampled at word indices
+    drawn from default_rng(SEED), the same on every run."""
+    os.makedirs(path, exist_ok=True)
+    conv = []
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype == np.uint8:
+            conv.append((name, a.reshape(-1), np.dtype(np.float32)))
+        else:
+            conv.append((name, a.reshape(-1).view(np.uint64).view("<u4"), np.dtype(np.float64)))
+    conv.sort(key=lambda c: c[1].size * c[2].itemsize)
+    left = DUMP_BUDGET
+    for i, (name, words, dt) in enumerate(conv):
+        cap = left // (len(conv) - i) // dt.itemsize
+        if words.size > cap:
+            words = words[np.sort(np.random.default_rng(SEED).integers(0, words.size, cap))]
+        out = words.astype(dt)
+        np.save(os.path.join(path, name + ".npy"), out)
+        left -= out.nbytes
+
+
+def proof_arrays(root, pf):
+    """what LcCommit::commit + prove hand their caller: the root and the proof's parts"""
+    cols = pf.columns
+    out = {"root": np.frombuffer(root, np.uint8), "p_eval": pf.p_eval,
+           "columns": np.stack([c.col for c in cols]),
+           "paths": np.frombuffer(b"".join(b"".join(c.path) for c in cols), np.uint8)}
+    pr = pf.p_random_vec
+    if pr:
+        out["p_random"] = np.stack(pr)
+    return out
+
+
 def ntt_muls(n):
     """Montgomery products of one length-n four-step fft_io (the last stage of each pass is
     multiplication-free): (n/2)(log2 n - 2) butterflies + n inter-pass twiddles."""
@@ -362,6 +423,7 @@ def ligero_or_sdig(args, L, torch, rank, local_rank):
     gate = threading.Semaphore(args.commit_slots) if args.commit_slots > 0 else None
 
     timeline = []  # (slot, t_gate, t_commit_start, t_commit_end, t_prove_end) with --timeline
+    last = []      # [root, proof] of the step run_replicas marks with KEEP_SLOT (--dump-outputs)
 
     def transcript(root):
         tr = L.Transcript(b"test transcript")
@@ -382,9 +444,11 @@ def ligero_or_sdig(args, L, torch, rank, local_rank):
             c = commit()
         t_c = time.perf_counter()
         root = c.get_root()
-        c.prove(outer, enc, transcript(root))
+        pf = c.prove(outer, enc, transcript(root))
         if args.timeline:
             timeline.append((slot, t_a, t_b, t_c, time.perf_counter()))
+        if KEEP_SLOT[0] == slot:
+            last[:] = [root, pf]
         return root
 
     inner = L.field_random(fid, n_per_row, 8)  # verify returns sum_c inner[c] p_eval[c]
@@ -455,7 +519,7 @@ def ligero_or_sdig(args, L, torch, rank, local_rank):
                 "field": args.field, "len": n, "n_rows": n_rows, "n_per_row": n_per_row, "n_cols": n_cols,
                 "n_col_opens": nco, "n_degree_tests": ndt},
         step=step, cpu_baseline=cpu_baseline, input_bytes=n * B, verify_bench=verify_bench, cpu_verify=cpu_verify,
-        latency=latency,
+        latency=latency, outputs=lambda: proof_arrays(*last),
         prepare=lambda: enc.prepare_thread(n_rows), reserve=lambda count: enc.reserve(n, count),
         timeline=timeline,
         enc_kernels=("transpose", "sdig_encode") if sdig else ("ntt_pass_a", "ntt_pass_b", "ntt_small"),
@@ -487,9 +551,16 @@ def encode_workload(args, L, torch, rank, local_rank):
     dst = [torch.empty(n_rows * n_cols * nl, dtype=torch.int64, device=dev) for _ in range(max(1, args.pipeline))]
     torch.cuda.synchronize()
 
+    last = [0]  # the slot the latest step wrote (--dump-outputs)
+
     def step(slot):
         enc.encode_rows_device(d_src.data_ptr(), n_per_row, n_per_row, dst[slot].data_ptr(), n_cols, n_rows)
+        last[0] = slot
         return None
+
+    def outputs():
+        torch.cuda.synchronize()
+        return {"encoded_rows": dst[last[0]].cpu().numpy().view(np.uint64)}
 
     ocache = {}
 
@@ -525,7 +596,7 @@ def encode_workload(args, L, torch, rank, local_rank):
         config={"workload": f"Ligero R-S encode, {args.field}, 2^{args.log_len} coeffs, "
                             f"{n_rows}x{n_per_row}->{n_cols}",
                 "field": args.field, "len": n, "n_rows": n_rows, "n_per_row": n_per_row, "n_cols": n_cols},
-        step=step, cpu_baseline=cpu_baseline, root_is_parity=True, cpu_reps_ok=False,
+        step=step, cpu_baseline=cpu_baseline, root_is_parity=True, cpu_reps_ok=False, outputs=outputs,
         enc_kernels=("ntt_pass_a", "ntt_pass_b", "ntt_small"),
         enc_kernel_desc=f"ntt_encode = ntt_pass_a + ntt_pass_b (one launch each per step, all {n_rows} rows)",
         algo_bytes=n_rows * n_per_row * B + n_rows * n_cols * B,
@@ -551,9 +622,16 @@ def sdig_encode_workload(args, L, torch, rank, local_rank):
     dst = [torch.empty(n_rows * n_cols * nl, dtype=torch.int64, device=dev) for _ in range(max(1, args.pipeline))]
     torch.cuda.synchronize()
 
+    last = [0]  # the slot the latest step wrote (--dump-outputs)
+
     def step(slot):
         enc.encode_rows_device(d_src.data_ptr(), n_per_row, n_per_row, dst[slot].data_ptr(), n_cols, n_rows)
+        last[0] = slot
         return None
+
+    def outputs():
+        torch.cuda.synchronize()
+        return {"encoded_rows": dst[last[0]].cpu().numpy().view(np.uint64)}
 
     ocache = {}
 
@@ -590,7 +668,7 @@ def sdig_encode_workload(args, L, torch, rank, local_rank):
                             f"call, {n_rows}x{n_per_row}->{n_cols}",
                 "field": args.field, "len": n, "batch": k, "n_rows": n_rows, "n_per_row": n_per_row,
                 "n_cols": n_cols, "matrix_nnz": nnz},
-        step=step, cpu_baseline=cpu_baseline, root_is_parity=True, cpu_reps_ok=False,
+        step=step, cpu_baseline=cpu_baseline, root_is_parity=True, cpu_reps_ok=False, outputs=outputs,
         enc_kernels=("transpose", "sdig_encode"),
         enc_kernel_desc=(f"sdig_encode = transpose to element-major + 13 SpMM / Reed-Solomon levels + transpose "
                          f"back (one call, all {n_rows} rows)"),
@@ -658,16 +736,27 @@ def pos_workload(args, L, torch, rank, local_rank):
             gate.acquire()
         try:
             if fused:
-                c, _ = commit_eval(slot)
+                c, ev = commit_eval(slot)
             else:
                 c = commit(slot)
         finally:
             if gate is not None:
                 gate.release()
         if not fused:
-            P.verifiable_polynomial_evaluation(c, left)
-        c.open_columns(cols)
-        return c.get_root()
+            ev = P.verifiable_polynomial_evaluation(c, left)
+        opened = c.open_columns(cols)
+        root = c.get_root()
+        if KEEP_SLOT[0] == slot:
+            last[:] = [root, ev, opened]
+        return root
+
+    last = []
+
+    def outputs():
+        root, ev, opened = last
+        return {"root": np.frombuffer(root, np.uint8), "eval": np.asarray(ev),
+                "columns": np.stack([o.col for o in opened]),
+                "paths": np.frombuffer(b"".join(b"".join(o.path) for o in opened), np.uint8)}
 
     def cpu_baseline(O):
         # bounded sample: the first 1/16 of the file (rows are independent; same dims)
@@ -707,7 +796,7 @@ def pos_workload(args, L, torch, rank, local_rank):
                                 + {"0": "off", "2": "at round 2", "3": "at the output phase"}.get(
                                     os.environ.get("LCPC_ROW1_PREFETCH", "1"), "at round 3"))
                                if row1_active(nc, fi) else "four-step (ntt_pass_a + ntt_pass_b)")},
-        step=step, cpu_baseline=cpu_baseline, parity=parity, input_bytes=n_bytes,
+        step=step, cpu_baseline=cpu_baseline, parity=parity, input_bytes=n_bytes, outputs=outputs,
         enc_kernels=("ntt_pass_a", "ntt_pass_b", "ntt_small", "ntt_row1"),
         enc_kernel_desc=(f"ntt_encode = ntt_row1 (one launch per commit, all {n_rows} rows)" if row1_active(nc, fi) else
                          f"ntt_encode = ntt_pass_a + ntt_pass_b (one launch each per commit, all {n_rows} rows)"),
@@ -1007,7 +1096,9 @@ def main():
         out = run_sharded(args, L, torch, dist, rank, world, device, backend, share)
     else:
         out = run_replicas(args, L, torch, dist, rank, world, device_idx, backend)
-        if world == 1 and args.code == "ligero" and args.sharded_n1 == 2:
+        if not args.full:
+            pass  # a plain run is the replicas line alone
+        elif world == 1 and args.code == "ligero" and args.sharded_n1 == 2:
             # the row-sharded engine on this one GPU, like for like with the N > 1 lines
             # (--mode auto runs it there): same steps and warm-up, after the replicas' figures
             sharded_n1 = sharded_n1_figure(args, L, torch, device)
@@ -1047,7 +1138,8 @@ def sharded_n1_child(args):
     N > 1 rank's do, not after this process's replicas run left its stream pools in use (the
     in-process figure, --sharded-n1 2, measured 9.1-9.4 against 10.1-10.4 G/s on one box)."""
     import subprocess
-    drop = {"--mode": 1, "--sharded-n1": 1, "--cpu-baseline": 1, "--verify-reps": 1, "--timeline": 1}
+    drop = {"--mode": 1, "--sharded-n1": 1, "--cpu-baseline": 1, "--verify-reps": 1, "--timeline": 1,
+            "--dump-outputs": 1}
     argv, i = [], 0
     src = sys.argv[1:]
     while i < len(src):
@@ -1119,12 +1211,16 @@ def run_sharded(args, L, torch, dist, rank, world, device, backend, share):
     barrier()
     t0 = time.perf_counter()
     c0, th0 = os.times(), cgroup_throttle()
-    troots, _ = S["run"](n_timed)
+    # (--dump-outputs: the driver also hands back the proofs it built, for the last one to be written)
+    troots, tproofs = S["run"](n_timed, keep=bool(args.dump_outputs))
     barrier()
     elapsed = time.perf_counter() - t0
     c1, th1 = os.times(), cgroup_throttle()
     L.prof_enable(False)
     stats = L.prof_stats() if prof_timed else {}
+    if args.dump_outputs and tproofs and tproofs[-1] is not None:  # on the last commitment's root rank
+        dump_outputs(args.dump_outputs, proof_arrays(troots[-1], tproofs[-1]))
+    del tproofs
     # recorded, not asserted: the line still prints, and main() exits non-zero on a mismatch
     steps_agree = len(troots) == n_timed and all(r == roots[0] for r in list(troots) + list(roots))
     elapsed = max_over_ranks(dist, elapsed, "cpu" if backend == "gloo" else device)
@@ -1133,7 +1229,7 @@ def run_sharded(args, L, torch, dist, rank, world, device, backend, share):
     # launching streams, every kernel of those serial steps)
     lat_c, lat_p, iso = [], [], {}
     sc = pf = None
-    for rep in range(1 + args.roofline_steps):
+    for rep in range(1 + args.roofline_steps if args.full else 0):
         if rep == 1 and not args.no_prof:
             L.prof_reset()
             L.prof_enable(True)
@@ -1146,7 +1242,7 @@ def run_sharded(args, L, torch, dist, rank, world, device, backend, share):
         if rep >= 1:
             lat_c.append(1e3 * (t2 - t1))
             lat_p.append(1e3 * (t3 - t2))
-    if not args.no_prof:
+    if args.full and not args.no_prof:
         L.prof_enable(False)
         iso = L.prof_stats()
     lat_c.sort()
@@ -1208,7 +1304,7 @@ def run_sharded(args, L, torch, dist, rank, world, device, backend, share):
     # region), so that an N > 1 line carries its own proof of a right answer: every timed step's
     # root, the kept warm-up proof and the verifier's value against the oracle's.  The timed CPU
     # baseline is the N = 1 line's (--cpu-baseline on forces it at every N)
-    want_cpu = args.cpu_baseline in ("on", "auto")
+    want_cpu = args.full and args.cpu_baseline in ("on", "auto")
     if rank == 0 and want_cpu:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_ffi as O  # checker / CPU baseline only
@@ -1319,12 +1415,18 @@ def run_pos_sharded(args, L, torch, dist, rank, world, device, backend, share):
     t0 = time.perf_counter()
     troots = []
     for _ in range(args.steps):
-        r_, _ = step()
+        r_, res_t = step()
         troots.append(r_)
     barrier()
     elapsed = max_over_ranks(dist, time.perf_counter() - t0, "cpu" if backend == "gloo" else device)
+    if args.dump_outputs and rank == 0:
+        ev_t, opened_t = res_t
+        dump_outputs(args.dump_outputs, {
+            "root": np.frombuffer(troots[-1], np.uint8), "eval": np.asarray(ev_t),
+            "columns": np.stack([o.col for o in opened_t]),
+            "paths": np.frombuffer(b"".join(b"".join(o.path) for o in opened_t), np.uint8)})
     iso = {}
-    if not args.no_prof:
+    if args.full and not args.no_prof:
         L.prof_reset()
         L.prof_enable(True)
         for _ in range(args.roofline_steps):
@@ -1356,7 +1458,7 @@ def run_pos_sharded(args, L, torch, dist, rank, world, device, backend, share):
                   mul_count=nr * pos_ntt_muls(nc)[0], mul_model=pos_ntt_muls(nc)[1], leaf_compressions=0)
     out.update(roofline_objects(wl, iso, {}, args, traffic_rows_frac=nr / n_rows))
     out["steps_agree"] = all(r == root for r in troots)
-    want_cpu = args.cpu_baseline in ("on", "auto")
+    want_cpu = args.full and args.cpu_baseline in ("on", "auto")
     if rank == 0:
         import hashlib
         ev, opened = res0
@@ -1448,6 +1550,8 @@ def run_replicas(args, L, torch, dist, rank, world, device_idx, backend):
                 if todo[0] <= 0:
                     return
                 todo[0] -= 1
+                if todo[0] == 0 and args.dump_outputs:
+                    KEEP_SLOT[0] = slot
             try:
                 roots.append(wl.step(slot))
             except Exception as e:
@@ -1485,8 +1589,11 @@ def run_replicas(args, L, torch, dist, rank, world, device_idx, backend):
                    "steps": sorted(tl, key=lambda r: r[2])}, open(args.timeline, "w"))
     L.prof_enable(False)
     stats = L.prof_stats() if (prof and args.prof_timed) else {}
+    if args.dump_outputs and rank == 0 and getattr(wl, "outputs", None):
+        dump_outputs(args.dump_outputs, wl.outputs())  # (rank 0's polynomial; the others' differ by seed)
+    KEEP_SLOT[0] = None
     iso = {}
-    if prof:
+    if prof and args.full:
         # The roofline launches: the same step run serially after the timed region, so each
         # encode launch has the GPU to itself.  One untimed step first: this (main) thread's
         # pinned staging is allocated on first use.
@@ -1497,7 +1604,7 @@ def run_replicas(args, L, torch, dist, rank, world, device_idx, backend):
             wl.step(0)
         L.prof_enable(False)
         iso = L.prof_stats()
-    lat = wl.latency(3) if getattr(wl, "latency", None) else None
+    lat = wl.latency(3) if args.full and getattr(wl, "latency", None) else None
     elapsed = max_over_ranks(dist, elapsed, "cpu" if backend == "gloo" else f"cuda:{device_idx}")
     scaling = getattr(wl, "scaling", "weak")
     value = job_throughput(wl.units, args.steps, world if scaling == "weak" else 1, elapsed)
@@ -1512,7 +1619,7 @@ def run_replicas(args, L, torch, dist, rank, world, device_idx, backend):
     }
     if lat:
         out["latency"] = lat
-    if args.input != "device":
+    if args.full and args.input != "device":
         from lcpc_proof_of_storage_amd import _native
         ib = wl.input_bytes
         rates = h2d_copy_rates(torch, ib, f"cuda:{device_idx}")
@@ -1545,14 +1652,14 @@ def run_replicas(args, L, torch, dist, rank, world, device_idx, backend):
                                      "what": f"per-step work / the timed region's ms_per_step ({P} calls in flight)"}
 
     gev = None
-    if getattr(wl, "verify_bench", None) and args.verify_reps > 0:
+    if args.full and getattr(wl, "verify_bench", None) and args.verify_reps > 0:
         vms, gev = wl.verify_bench(args.verify_reps)
         out["verify"] = {"ms": vms, "reps": args.verify_reps,
                          "what": "LcEvalProof::verify of one proof of this workload (host + GPU, serial)"}
     if root is not None:
         out["root"] = root.hex()
     out["steps_agree"] = steps_agree
-    want_cpu = args.cpu_baseline in ("on", "auto")  # rank 0's polynomial checked at every N
+    want_cpu = args.full and args.cpu_baseline in ("on", "auto")  # rank 0's polynomial checked at every N
     if rank == 0 and want_cpu:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_ffi as O  # checker / CPU baseline only

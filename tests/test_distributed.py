@@ -120,3 +120,21 @@ def test_single_process_has_no_group():
     import bench
     assert bench.init_dist(1, 0) is None
     assert bench.max_over_ranks(None, 3.5) == 3.5
+
+
+def test_dump_outputs_sampling_is_fixed_and_bounded(tmp_path, monkeypatch):
+    """an output over the budget is written as the same seeded sample of its words every time"""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 1 << 16)
+    big = np.arange(1 << 15, dtype=np.uint64) * np.uint64(0x100000001)
+    small = np.arange(32, dtype=np.uint8)
+    for tag in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / tag), {"rows": big, "root": small})
+    a, b = np.load(tmp_path / "a" / "rows.npy"), np.load(tmp_path / "b" / "rows.npy")
+    assert a.dtype == np.float64 and np.array_equal(a, b) and 0 < a.nbytes < (1 << 16)
+    words = big.view("<u4").astype(np.float64)
+    assert np.isin(a, words).all()
+    r = np.load(tmp_path / "a" / "root.npy")
+    assert r.dtype == np.float32 and np.array_equal(r, small.astype(np.float32))
+    assert a.nbytes + r.nbytes <= 1 << 16

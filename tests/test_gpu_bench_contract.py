@@ -15,12 +15,13 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(*args, timeout=100):
+def _bench(*args, timeout=100, full=True):
     env = dict(os.environ)
     env.pop("RANK", None)
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], cwd=ROOT, env=env,
-                       capture_output=True, text=True, timeout=timeout)
+    # --full: the roofline, cpu_baseline, latency, verify and parity keys checked below
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *(["--full"] if full else []), *args],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -105,8 +106,8 @@ def _bench_ranks(world, extra_env, *args, timeout=280):
     env = dict(os.environ, LCPC_BENCH_BACKEND="gloo", LCPC_BENCH_SHARE_GPU="1", **extra_env)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), *args], cwd=ROOT,
-                       env=env, capture_output=True, text=True, timeout=timeout)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(world), *args],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -182,3 +183,35 @@ def test_bench_pos_small(gpu, pos_eval):
     _check_cpu(d)
     assert d["parity_root_vs_oracle"] and d["parity_eval_vs_oracle"] and d["parity_cols_vs_oracle"]
     assert d["parity_ok"] is True
+
+
+@pytest.mark.parametrize("mode", ["replicas", "sharded"])
+def test_bench_plain_run_and_dump_small(gpu, tmp_path, mode):
+    """without --full the line is the timed steps' figure alone; --dump-outputs writes the last
+    timed step's root and proof parts, the same arrays on every run"""
+    import numpy as np
+    runs = []
+    for tag in ("a", "b"):
+        d = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--log-len", "16", "--mode", mode,
+                   "--dump-outputs", str(tmp_path / tag), full=False)
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert abs(d["value"] * d["ms_per_step"] * 1e-3 - (1 << 16)) < 1e-6 * (1 << 16)
+        for k in ("metric", "unit", "higher_is_better", "dtype", "root", "steps_agree"):
+            assert k in d, k
+        for k in ("roofline", "kernels", "cpu_baseline", "cpu_baseline_1core", "verify", "sharded_n1", "scale_base",
+                  "parity_ok", "parity_root_vs_oracle"):
+            assert k not in d, k
+        arrs = {f[:-4]: np.load(tmp_path / tag / f) for f in sorted(os.listdir(tmp_path / tag))}
+        assert set(arrs) == {"root", "p_eval", "p_random", "columns", "paths"}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert bytes(arrs["root"].astype(np.uint8)).hex() == d["root"]
+        cfg = d["config"]
+        nl = 2  # Ft127: two u64 limbs, written as four 32-bit words
+        assert arrs["p_eval"].size == cfg["n_per_row"] * nl * 2
+        assert arrs["p_random"].size == cfg["n_degree_tests"] * cfg["n_per_row"] * nl * 2
+        assert arrs["columns"].size == cfg["n_col_opens"] * cfg["n_rows"] * nl * 2
+        assert arrs["paths"].size == cfg["n_col_opens"] * 32 * (cfg["n_cols"].bit_length() - 1)
+        assert all(float(a.max()) < 2.0 ** 32 and float(a.min()) >= 0 for a in arrs.values())
+        runs.append(arrs)
+    assert all(np.array_equal(runs[0][k], runs[1][k]) for k in runs[0])

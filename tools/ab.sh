@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 for i in 1 2; do
   for v in A B; do
     if [ $v = A ]; then E=""; else E="$SW"; fi
-    timeout -k 10 300 env $E python bench.py --steps "$STEPS" --cpu-baseline off "$@" > "$OUT/$v$i.json" 2> "$OUT/$v$i.err" || { tail -20 "$OUT/$v$i.err"; exit 1; }
+    timeout -k 10 300 env $E python bench.py --full --steps "$STEPS" --cpu-baseline off "$@" > "$OUT/$v$i.json" 2> "$OUT/$v$i.err" || { tail -20 "$OUT/$v$i.err"; exit 1; }
     python -c "import json;d=json.load(open('$OUT/$v$i.json'));k=d['kernels'];print('$v$i', '%.3f G/s'%(d['value']/1e9), '%.4f ms/step'%d['ms_per_step'], ' '.join('%s=%.4f'%(n,k[n]['avg_ms']) for n in sorted(k) if not n.startswith('host')))"
   done
 done

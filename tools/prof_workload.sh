@@ -7,10 +7,10 @@ TAG=${1:-wl}; STEPS=${2:-256}; shift; shift
 export TMPDIR=/tmp
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
-timeout -k 10 300 python bench.py --steps "$STEPS" "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" \
+timeout -k 10 300 python bench.py --full --steps "$STEPS" "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" \
   || { tail -20 "$OUT/bench.err"; exit 1; }
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
-  python3 bench.py --steps "$STEPS" --cpu-baseline off --verify-reps 0 "$@" > "$OUT/bench_under_prof.json" 2> "$OUT/prof.err" \
+  python3 bench.py --full --steps "$STEPS" --cpu-baseline off --verify-reps 0 "$@" > "$OUT/bench_under_prof.json" 2> "$OUT/prof.err" \
   || { tail -20 "$OUT/prof.err"; exit 1; }
 for c in FETCH_SIZE WRITE_SIZE; do
   n=$(echo "$c" | cut -d_ -f1 | tr 'A-Z' 'a-z')

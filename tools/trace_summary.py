@@ -4,7 +4,7 @@
     python tools/trace_summary.py gpurun_out/<tag>/prof/run_kernel_trace.csv [--last R]
 
 Prints, per kernel, the launch count and average duration over all launches and over the last
-R launches -- bench.py's roofline steps run serially at the end of the process, so the last R
+R launches -- the roofline steps of bench.py --full run serially at the end of the process, so the last R
 encode launches are the ones its HIP-event roofline figure is taken on -- plus the GPU busy
 fraction of the trace span (union of kernel intervals).
 """
