@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define LCPC_ABI_VERSION 1
+#define LCPC_ABI_VERSION 2 /* 2: the PoS column chunk-CV cache (lcpc_pos_chunk_cache_*) */
 
 typedef enum lcpc_status {
   LCPC_OK = 0,
@@ -474,6 +474,66 @@ lcpc_status lcpc_pos_reencode_rows(const uint8_t *bytes, size_t n_bytes, size_t 
 lcpc_status lcpc_pos_decode_porenc(const uint8_t *porenc, size_t pre, size_t enc,
                                    size_t row_capacity, size_t row_lo, size_t row_hi,
                                    uint8_t *out);
+
+/* ------------------------------------------------------------------ PoS column chunk-CV cache
+ * Incremental Merkle updates of a stored file (no counterpart in the reference, whose edit_bytes /
+ * append_bytes rehash the whole .porenc; the trees are the same bit for bit).  A column digest is
+ * BLAKE3(32 zero bytes || the column's rows_written 8-byte elements): a tree over 1-KiB chunks,
+ * where a chunk's chaining value (CV) depends only on its bytes, its chunk counter and whether it
+ * is the message's only chunk (the ROOT flag).  Chunk 0 covers rows [0, 124), chunk c >= 1 rows
+ * [128 c - 4, 128 c + 124) (lcpc_leaf_chunk_first_row).  The cache keeps every column's CVs in
+ * device memory, [chunk][column] x 32 bytes (the layout lcpc_pos_writer computes them in); an
+ * update rereads and rehashes only the chunks an edit or append changed, and the digests and tree
+ * are one fold of the cache that leaves it intact.  WriteableFt63 only, like the file layer. */
+typedef struct lcpc_pos_chunk_cache lcpc_pos_chunk_cache;
+/* Host-only (no device): the chunks [*chunk_lo, *chunk_hi) an update must rehash when rows
+ * [row_lo, row_hi) changed and the row count went from old_rows to new_rows >= old_rows: the
+ * chunks holding those rows, and on growth everything from min(chunk of row_lo, the old last
+ * chunk) -- whose length changes, or which loses ROOT if it was the only chunk -- through the new
+ * last chunk.  A shrinking row count or row_hi > new_rows is LCPC_ERR_INVALID_ARG; nothing to do
+ * gives an empty range. */
+lcpc_status lcpc_pos_update_chunk_range(size_t old_rows, size_t new_rows, size_t row_lo,
+                                        size_t row_hi, size_t *chunk_lo, size_t *chunk_hi);
+/* One full pass over the image (the cost of lcpc_pos_porenc_tree), keeping the CVs.
+ * LCPC_ERR_INVALID_ARG if an element is not canonical, as lcpc_pos_porenc_tree. */
+lcpc_status lcpc_pos_chunk_cache_from_porenc(const uint8_t *porenc, size_t enc, size_t rows_written,
+                                             size_t row_capacity, lcpc_pos_chunk_cache **out);
+/* From saved CVs: lcpc_leaf_n_chunks(LCPC_FT63, rows_written) * enc * 32 bytes, [chunk][column]. */
+lcpc_status lcpc_pos_chunk_cache_from_cvs(const uint8_t *cvs, size_t enc, size_t rows_written,
+                                          lcpc_pos_chunk_cache **out);
+void lcpc_pos_chunk_cache_free(lcpc_pos_chunk_cache *c);
+size_t lcpc_pos_chunk_cache_enc(const lcpc_pos_chunk_cache *c);
+size_t lcpc_pos_chunk_cache_rows(const lcpc_pos_chunk_cache *c);
+size_t lcpc_pos_chunk_cache_n_chunks(const lcpc_pos_chunk_cache *c);
+/* CVs of chunks [chunk_lo, chunk_hi): (chunk_hi - chunk_lo) * enc * 32 bytes */
+lcpc_status lcpc_pos_chunk_cache_copy_cvs(const lcpc_pos_chunk_cache *c, size_t chunk_lo,
+                                          size_t chunk_hi, uint8_t *out);
+/* Rows [row_lo, row_hi) of the image changed and the file now has new_rows_written rows (>= the
+ * cache's): the chunks of lcpc_pos_update_chunk_range are reread from the image (enc strided
+ * slices through page-locked staging) and rehashed, the cache growing by whole chunk rows; the
+ * range is reported (either pointer may be NULL).  On any error, a non-canonical element
+ * (LCPC_ERR_INVALID_ARG) included, the cache is unchanged. */
+lcpc_status lcpc_pos_chunk_cache_update(lcpc_pos_chunk_cache *c, const uint8_t *porenc,
+                                        size_t row_capacity, size_t row_lo, size_t row_hi,
+                                        size_t new_rows_written, size_t *chunk_lo, size_t *chunk_hi);
+/* The same with the image read from the open file fd (pread of the affected slices) instead of a
+ * mapping: mapping and unmapping a multi-GB .porenc costs more than an update's 1 KiB per column.
+ * A file that ends before a slice is LCPC_ERR_INVALID_ARG. */
+lcpc_status lcpc_pos_chunk_cache_update_fd(lcpc_pos_chunk_cache *c, int fd, size_t row_capacity,
+                                           size_t row_lo, size_t row_hi, size_t new_rows_written,
+                                           size_t *chunk_lo, size_t *chunk_hi);
+/* The enc column digests and / or MerkleTree::to_bytes (2 enc - 1 digests) from the cache; either
+ * may be NULL; layouts of lcpc_pos_writer_finalize. */
+lcpc_status lcpc_pos_chunk_cache_tree(const lcpc_pos_chunk_cache *c, uint8_t *digests, uint8_t *tree);
+/* After lcpc_pos_writer_finalize: the writer's chunk count and its n_chunks * enc * 32 bytes of
+ * CVs, so a new file gets its cache without a second pass over the image. */
+size_t lcpc_pos_writer_n_chunks(const lcpc_pos_writer *w);
+lcpc_status lcpc_pos_writer_copy_cvs(const lcpc_pos_writer *w, uint8_t *out);
+/* lcpc_leaves_from_cvs by the cache's non-clobbering fold (one thread per column, a register stack
+ * of subtree roots): the same leaves; cvs_after (optional) receives the device copy of the CVs as
+ * the fold left it, which equals cvs. */
+lcpc_status lcpc_leaves_fold_cvs(const uint8_t *cvs, size_t n_chunks, size_t n_cols, uint8_t *leaves,
+                                 uint8_t *cvs_after);
 
 /* ------------------------------------------------------------------ row shards (multi-GPU)
  * One process per GPU holds rows [row0, row0 + n_shard_rows) of an n_rows x n_per_row Ligero

@@ -189,6 +189,20 @@ SIGNATURES = {
     "lcpc_shard_gather_columns_device": (i32, [vp, u64p, sz, vp]),
     "lcpc_field_sum_device": (i32, [i32, vp, sz, sz, u64p]),
     "lcpc_pos_reencode_rows": (i32, [u8p, sz, sz, sz, sz, u8p, sz]),
+    "lcpc_pos_update_chunk_range": (i32, [sz, sz, sz, sz, szp, szp]),
+    "lcpc_pos_chunk_cache_from_porenc": (i32, [u8p, sz, sz, sz, C.POINTER(vp)]),
+    "lcpc_pos_chunk_cache_from_cvs": (i32, [u8p, sz, sz, C.POINTER(vp)]),
+    "lcpc_pos_chunk_cache_free": (None, [vp]),
+    "lcpc_pos_chunk_cache_enc": (sz, [vp]),
+    "lcpc_pos_chunk_cache_rows": (sz, [vp]),
+    "lcpc_pos_chunk_cache_n_chunks": (sz, [vp]),
+    "lcpc_pos_chunk_cache_copy_cvs": (i32, [vp, sz, sz, u8p]),
+    "lcpc_pos_chunk_cache_update": (i32, [vp, u8p, sz, sz, sz, sz, szp, szp]),
+    "lcpc_pos_chunk_cache_update_fd": (i32, [vp, i32, sz, sz, sz, sz, szp, szp]),
+    "lcpc_pos_chunk_cache_tree": (i32, [vp, u8p, u8p]),
+    "lcpc_pos_writer_n_chunks": (sz, [vp]),
+    "lcpc_pos_writer_copy_cvs": (i32, [vp, u8p]),
+    "lcpc_leaves_fold_cvs": (i32, [u8p, sz, sz, u8p, u8p]),
     "lcpc_challenge_tensor": (i32, [vp, i32, sz, u64p]),
     "lcpc_transcript_append_field_elems": (i32, [vp, u8p, sz, i32, u64p, sz]),
     "lcpc_challenge_columns": (i32, [vp, sz, sz, u64p]),

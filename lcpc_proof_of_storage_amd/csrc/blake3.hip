@@ -299,10 +299,26 @@ __global__ __launch_bounds__(256) void k_leaf_chunks_eval(const uint32_t *__rest
 // n_rows * N % 4 == 0 (16-B aligned columns); the message word w of a column is memory word w - 8
 // of the column (w >= 8), and a 4-word unit lies wholly inside or outside the message.
 // fuse2: a two-chunk message hashed whole by one wave (grid.y = 1, leaves written directly).
-template <class F, bool CANON>
-__global__ __launch_bounds__(256) void k_leaf_chunks_cm(const uint32_t *__restrict__ m, size_t n_rows,
-                                                        size_t n_cols, uint32_t *__restrict__ cvs,
-                                                        uint8_t *__restrict__ leaves, int n_chunks, int fuse2) {
+//
+// SLICE (the PoS chunk-CV cache, canonical input only): m holds, per column, only the rows of the
+// chunks [chunk0, chunk0 + gridDim.y) of messages n_rows rows long -- column c at m + c * col_words
+// words (col_words a multiple of 4, at least the slice's words rounded up to 4), its word 0 being
+// message word w_base (a multiple of 4: 8 + 2 * first row of chunk0).  n_rows may be odd there, so
+// the message can end inside a 4-word unit: the words past it are zeroed.  Every element is checked
+// < p (*bad set otherwise: from_repr would refuse it), and the chaining value of (chunk, col) goes
+// to cvs[(chunk - cv_chunk0) * cv_stride + col] whatever n_chunks is -- straight into a
+// [chunk][column] array of cv_stride columns whose first chunk row is chunk cv_chunk0 (0: the whole
+// cache), cvs already offset to this launch's first column.
+struct CmSlice {
+  size_t col_words, w_base, cv_stride;
+  int chunk0, cv_chunk0;
+  uint32_t *bad;
+};
+
+template <class F, bool CANON, bool SLICE>
+__device__ __forceinline__ void leaf_chunks_cm_body(const uint32_t *__restrict__ m, size_t n_rows, size_t n_cols,
+                                                    uint32_t *__restrict__ cvs, uint8_t *__restrict__ leaves,
+                                                    int n_chunks, int fuse2, const CmSlice &sl) {
   constexpr int N = F::N;
   static_assert(16 % N == 0 && 8 % N == 0, "element must tile a BLAKE3 block");
   constexpr int EPB = 16 / N;
@@ -311,7 +327,9 @@ __global__ __launch_bounds__(256) void k_leaf_chunks_cm(const uint32_t *__restri
   const size_t col0 = ((size_t)blockIdx.x * 4 + wave) * 64, col = col0 + lane;
   if (col0 >= n_cols) return;  // whole waves
   const size_t msg_words = 8 + n_rows * N;  // the column's message, in words
+  const size_t col_words = SLICE ? sl.col_words : n_rows * N, w_base = SLICE ? sl.w_base : 8;
   const int unit = lane & 3, csub = lane >> 2;
+  bool noncanon = false;
   // block b (of the chunk starting at message word w0): this lane's 4 loads, unit `unit` (words
   // 4 unit .. +3) of column col0 + csub + 16 i
   auto gload = [&](size_t w0, int b, uint4 r[4]) {
@@ -320,8 +338,11 @@ __global__ __launch_bounds__(256) void k_leaf_chunks_cm(const uint32_t *__restri
 #pragma unroll
     for (int i = 0; i < 4; i++) {
       const size_t c = col0 + csub + 16 * i;
-      r[i] = in && c < n_cols ? reinterpret_cast<const uint4 *>(m + c * n_rows * N + (w - 8))[0]
+      r[i] = in && c < n_cols ? reinterpret_cast<const uint4 *>(m + c * col_words + (w - w_base))[0]
                               : make_uint4(0, 0, 0, 0);
+      if constexpr (SLICE) {  // the message ends inside this unit (msg_words is even)
+        if (w + 2 == msg_words) r[i].z = r[i].w = 0;
+      }
     }
   };
   auto wave_sync = [] {
@@ -364,6 +385,7 @@ __global__ __launch_bounds__(256) void k_leaf_chunks_cm(const uint32_t *__restri
         Fe<F> e;
 #pragma unroll
         for (int i = 0; i < N; i++) e.v[i] = msg[k * N + i];
+        if constexpr (SLICE) noncanon |= !fe_is_canonical<F>(e);  // (prefix and tail words are zero)
         uint32_t w[N];
         if constexpr (CANON)
           fe_canon_repr_words<F>(e, w);
@@ -391,14 +413,84 @@ __global__ __launch_bounds__(256) void k_leaf_chunks_cm(const uint32_t *__restri
     if (col < n_cols) store8(reinterpret_cast<uint32_t *>(leaves + 32 * col), leaf);
     return;
   }
-  const int chunk = blockIdx.y;
+  const int chunk = (SLICE ? sl.chunk0 : 0) + blockIdx.y;
   chunk_cv(chunk, cv);
   if (col >= n_cols) return;
+  if constexpr (SLICE) {
+    if (noncanon) atomicOr(sl.bad, 1u);
+    store8(cvs + ((size_t)(chunk - sl.cv_chunk0) * sl.cv_stride + col) * 8, cv);
+    return;
+  }
   if (n_chunks == 1 && leaves) {
     store8(reinterpret_cast<uint32_t *>(leaves + 32 * col), cv);
   } else {
     store8(cvs + ((size_t)chunk * n_cols + col) * 8, cv);
   }
+}
+
+template <class F, bool CANON>
+__global__ __launch_bounds__(256) void k_leaf_chunks_cm(const uint32_t *__restrict__ m, size_t n_rows,
+                                                        size_t n_cols, uint32_t *__restrict__ cvs,
+                                                        uint8_t *__restrict__ leaves, int n_chunks, int fuse2) {
+  leaf_chunks_cm_body<F, CANON, false>(m, n_rows, n_cols, cvs, leaves, n_chunks, fuse2, CmSlice{});
+}
+
+// chunks [sl.chunk0, sl.chunk0 + gridDim.y) of canonical column slices into a chunk-CV cache (SLICE above)
+template <class F>
+__global__ __launch_bounds__(256) void k_leaf_chunks_cm_slice(const uint32_t *__restrict__ m, size_t n_rows,
+                                                              size_t n_cols, uint32_t *__restrict__ cvs,
+                                                              int n_chunks, CmSlice sl) {
+  leaf_chunks_cm_body<F, true, true>(m, n_rows, n_cols, cvs, nullptr, n_chunks, 0, sl);
+}
+
+// The leaf of one column from its chunk chaining values without touching them (the PoS chunk-CV
+// cache must survive the fold): one thread per column walks cvs[0][col], cvs[1][col], ... with a
+// register stack of subtree roots, level[k] = the root of a complete 2^k-chunk subtree, present
+// iff bit k of the number of chunks taken so far is set (BLAKE3's merge rule: after chunk i, pop
+// and merge while the count has a trailing zero bit -- that is, while bit k of i is set).  The
+// last chunk merges with every level still present, lowest first, ROOT on the last parent.  The
+// chunk index is the same for every thread, so which level is read or written is uniform: the
+// stack is picked over by unrolled compares (static register indices, one instance of the round
+// function), never indexed dynamically; adjacent threads read adjacent 32-byte values.
+// n_chunks >= 2 and n_chunks - 1 < 2^D.
+template <int D>
+__global__ __launch_bounds__(64) void k_leaf_fold_stack(const uint32_t *__restrict__ cvs, size_t n_cols,
+                                                        int n_chunks, uint8_t *__restrict__ leaves) {
+  const size_t col = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (col >= n_cols) return;
+  uint32_t level[D][8], cv[8], nxt[8];
+  load8(cvs + col * 8, nxt);
+  for (int i = 0; i < n_chunks; i++) {
+#pragma unroll
+    for (int q = 0; q < 8; q++) cv[q] = nxt[q];
+    if (i + 1 < n_chunks) load8(cvs + ((size_t)(i + 1) * n_cols + col) * 8, nxt);  // in flight over the merges
+    const bool last = i + 1 == n_chunks;
+    for (int k = 0; k < D; k++) {
+      const bool top = (i >> (k + 1)) == 0;  // no level above k is present
+      if ((i >> k) & 1) {
+        uint32_t l[8], o[8];
+#pragma unroll
+        for (int j = 0; j < D; j++)
+          if (j == k) {
+#pragma unroll
+            for (int q = 0; q < 8; q++) l[q] = level[j][q];
+          }
+        parent_cv(l, cv, last && top, o);
+#pragma unroll
+        for (int q = 0; q < 8; q++) cv[q] = o[q];
+      } else if (!last) {
+#pragma unroll
+        for (int j = 0; j < D; j++)
+          if (j == k) {
+#pragma unroll
+            for (int q = 0; q < 8; q++) level[j][q] = cv[q];
+          }
+        break;
+      }
+      if (last && top) break;
+    }
+  }
+  store8(reinterpret_cast<uint32_t *>(leaves + 32 * col), cv);
 }
 
 // The same chunks for an element that does not tile a 64-byte block (Ft191: 24 bytes, so
@@ -741,6 +833,51 @@ hipError_t leaves_from_cvs(uint32_t *cvs, size_t n_cols, int n_chunks, uint8_t *
   if (!n_cols) return hipSuccess;
   if (n_chunks == 1) return hipMemcpyAsync(leaves, cvs, n_cols * 32, hipMemcpyDeviceToDevice, s);
   return launch_leaf_merge(cvs, n_cols, n_chunks, leaves, s);
+}
+
+hipError_t leaves_fold_cvs(const uint32_t *cvs, size_t n_cols, size_t n_chunks, uint8_t *leaves,
+                           hipStream_t s) {
+  if (!n_cols) return hipSuccess;
+  if (n_chunks == 0 || n_chunks > ((size_t)1 << 20)) return hipErrorInvalidValue;
+  if (n_chunks == 1) return hipMemcpyAsync(leaves, cvs, n_cols * 32, hipMemcpyDeviceToDevice, s);
+  prof::Scope ps("leaf_fold", s);
+  const dim3 grid((unsigned)((n_cols + 63) / 64));
+  if (n_chunks <= 256)
+    hipLaunchKernelGGL((k_leaf_fold_stack<8>), grid, dim3(64), 0, s, cvs, n_cols, (int)n_chunks, leaves);
+  else
+    hipLaunchKernelGGL((k_leaf_fold_stack<20>), grid, dim3(64), 0, s, cvs, n_cols, (int)n_chunks, leaves);
+  return hipGetLastError();
+}
+
+hipError_t leaf_chunk_cvs_slices(int fid, const uint32_t *slices, size_t col_elems, size_t n_rows,
+                                 size_t n_cols, size_t chunk_lo, size_t chunk_hi, uint32_t *cvs,
+                                 size_t cv_chunk0, size_t cv_stride, uint32_t *bad, hipStream_t s) {
+  if (n_cols == 0 || chunk_hi <= chunk_lo) return hipSuccess;
+  const size_t n_chunks = leaf_n_chunks(fid, n_rows);
+  if (chunk_hi > n_chunks || chunk_hi - chunk_lo > 65535 || cv_chunk0 > chunk_lo || !bad || n_cols > cv_stride) return hipErrorInvalidValue;
+  return dispatch_field(fid, [&]<class F>() -> hipError_t {
+    if constexpr (16 % F::N == 0 && 8 % F::N == 0) {
+      // first row of chunk_lo and the rows the slices must hold
+      const size_t r_lo = chunk_lo ? (256 * chunk_lo - 8 + F::N - 1) / F::N : 0;
+      const size_t r_hi = chunk_hi == n_chunks ? n_rows : (256 * chunk_hi - 8 + F::N - 1) / F::N;
+      CmSlice sl;
+      sl.col_words = col_elems * F::N;
+      sl.w_base = 8 + r_lo * F::N;
+      sl.cv_stride = cv_stride;
+      sl.chunk0 = (int)chunk_lo;
+      sl.cv_chunk0 = (int)cv_chunk0;
+      sl.bad = bad;
+      if (sl.col_words % 4 || sl.w_base % 4 || sl.col_words < (((r_hi - r_lo) * F::N + 3) & ~(size_t)3))
+        return hipErrorInvalidValue;
+      prof::Scope ps("leaf_chunks", s);
+      const dim3 grid((unsigned)((n_cols + 255) / 256), (unsigned)(chunk_hi - chunk_lo));
+      hipLaunchKernelGGL((k_leaf_chunks_cm_slice<F>), grid, dim3(256), 0, s, slices, n_rows, n_cols, cvs,
+                         (int)n_chunks, sl);
+      return hipGetLastError();
+    } else {
+      return hipErrorInvalidValue;  // elements that straddle blocks (Ft191) have no column-major kernel
+    }
+  });
 }
 
 hipError_t leaf_hashes(int fid, const uint32_t *m, size_t n_rows, size_t n_cols, size_t stride,

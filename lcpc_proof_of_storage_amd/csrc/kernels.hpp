@@ -91,6 +91,22 @@ hipError_t leaf_chunk_cvs(int fid, const uint32_t *m, size_t row0, size_t n_rows
 // leaf digests from all n_chunks chaining values ([chunk][col] layout; cvs is clobbered)
 hipError_t leaves_from_cvs(uint32_t *cvs, size_t n_cols, int n_chunks, uint8_t *leaves,
                            hipStream_t s);
+// the same leaves, bit for bit, with cvs left untouched (a chunk-CV cache that outlives the fold):
+// one thread per column and one launch, a register stack of subtree roots (n_chunks <= 2^20)
+hipError_t leaves_fold_cvs(const uint32_t *cvs, size_t n_cols, size_t n_chunks, uint8_t *leaves,
+                           hipStream_t s);
+// Chunk-CV cache of column-major canonical files: chaining values of chunks [chunk_lo, chunk_hi) of
+// n_cols column messages (n_rows rows in total) from slices [col][col_elems] of little-endian
+// canonical elements that hold only those chunks' rows (from lcpc_leaf_chunk_first_row(chunk_lo)
+// on; the message's last chunk may be short).  col_elems: elements between columns, at least the
+// slice's rows, with col_elems * N a multiple of 4 words.  The value of (chunk, col) is written to
+// cvs[((chunk - cv_chunk0) * cv_stride + col) * 8]: cvs is a [chunk][cv_stride columns] array whose
+// first chunk row is chunk cv_chunk0 <= chunk_lo (0: the cache itself), offset to the first of
+// these columns; a one-chunk message's value carries ROOT; *bad |= 1 if an element is not < p.
+// Fields whose element tiles a block.
+hipError_t leaf_chunk_cvs_slices(int fid, const uint32_t *slices, size_t col_elems, size_t n_rows,
+                                 size_t n_cols, size_t chunk_lo, size_t chunk_hi, uint32_t *cvs,
+                                 size_t cv_chunk0, size_t cv_stride, uint32_t *bad, hipStream_t s);
 // leaf_hashes of a canonical row-major codeword that also writes each (chunk, column)'s share of
 // u^T Enc(M): partials[chunk][col] = sum over the chunk's rows r of left[r] * m[r][col]
 // (Montgomery left, canonical results; leaf_n_chunks(fid, n_rows) x n_cols elements).  Fields

@@ -8,6 +8,10 @@
 // LCPC_ERR_NO_DEVICE.
 #include "host_internal.hpp"
 
+#include <unistd.h>
+
+#include <cerrno>
+
 using namespace lcpc;
 using namespace lcpc_host;
 
@@ -2610,6 +2614,309 @@ lcpc_status lcpc_pos_decode_porenc(const uint8_t *porenc, size_t pre, size_t enc
 
 }  // extern "C"
 
+// Column chunk-CV cache of a stored file: the chaining value of every 1-KiB BLAKE3 chunk of every
+// column message (32 zero bytes || the column's rows_written canonical elements), [chunk][column],
+// kept in device memory.  A chunk's value depends only on its bytes, its counter and whether it is
+// the message's only chunk, so after an edit or an append only the chunks whose rows, length or
+// one-chunk flag changed are read from the image and rehashed; the column digests are one
+// non-clobbering fold of the cache (leaves_fold_cvs) and the tree follows as everywhere else.
+struct lcpc_pos_chunk_cache {
+  Device *dev = nullptr;
+  size_t enc = 0, rows = 0, n_chunks = 0, cap_chunks = 0;
+  DBuf cvs;  // cap_chunks x enc x 32 B, the first n_chunks chunk rows valid
+};
+
+namespace {
+
+size_t pos_chunk_of_row(size_t row) { return (32 + row * POS_WB) / 1024; }
+
+lcpc_status pos_update_chunk_range(size_t old_rows, size_t new_rows, size_t row_lo, size_t row_hi,
+                                   size_t *chunk_lo, size_t *chunk_hi) {
+  if (new_rows < old_rows) return fail(LCPC_ERR_INVALID_ARG, "a stored file's row count cannot shrink");
+  if (row_lo > row_hi || row_hi > new_rows) return fail(LCPC_ERR_INVALID_ARG, "row range");
+  size_t lo = 0, hi = 0;
+  if (row_lo < row_hi) {
+    lo = pos_chunk_of_row(row_lo);
+    hi = pos_chunk_of_row(row_hi - 1) + 1;
+  }
+  if (new_rows > old_rows) {
+    // the old last chunk changes length (or, the only chunk so far, loses ROOT); every later one is new
+    const size_t old_last = leaf_n_chunks(POS_FID, old_rows) - 1;
+    lo = row_lo < row_hi ? std::min(lo, old_last) : old_last;
+    hi = leaf_n_chunks(POS_FID, new_rows);
+  }
+  *chunk_lo = lo;
+  *chunk_hi = hi;
+  return LCPC_OK;
+}
+
+// Chunks [c_lo, c_hi) of every column of the image (messages of n_rows rows) hashed into dst, a
+// device [chunk][enc] array whose first chunk row is chunk c_lo: only those chunks' rows are read,
+// enc strided slices staged through page-locked memory a block of columns at a time, each block's
+// host copy overlapping the previous block's upload and hashing.  *bad (device) collects the
+// not-< p flag.  The image is the mapping porenc or, with fd >= 0, the open file fd read with
+// pread: mapping and unmapping a multi-GB file costs more than an update's 1 KiB per column.
+lcpc_status cache_hash_chunks(Device *dev, hipStream_t s, const uint8_t *porenc, int fd, size_t enc,
+                              size_t row_capacity, size_t n_rows, size_t c_lo, size_t c_hi, uint32_t *dst,
+                              uint32_t *bad) {
+  const int fid = POS_FID;
+  const size_t n_chunks = leaf_n_chunks(fid, n_rows);
+  const size_t r_lo = std::min(n_rows, lcpc_leaf_chunk_first_row((lcpc_field)fid, c_lo));
+  const size_t r_hi = c_hi == n_chunks ? n_rows : lcpc_leaf_chunk_first_row((lcpc_field)fid, c_hi);
+  const size_t R = r_hi - r_lo;
+  const size_t col_elems = R + (R & 1);  // 16-byte aligned slices (the kernel masks the pad)
+  const size_t col_bytes = col_elems * POS_WB;
+  const size_t cpb = col_bytes ? std::max<size_t>(1, std::min(enc, POS_STAGE_BYTES / col_bytes)) : enc;
+  DBuf dcols[2];
+  Pinned stg[2];
+  Events ev;
+  HIP_TRY(ev.init());
+  for (int i = 0; i < 2; i++) {
+    HIP_TRY(dcols[i].alloc(dev, cpb * col_bytes));
+    if (col_bytes && !stg[i].get(dev, cpb * col_bytes)) return fail(LCPC_ERR_OUT_OF_MEMORY, "pinned host staging");
+  }
+  int k = 0;
+  for (size_t c0 = 0; c0 < enc; c0 += cpb, k++) {
+    const size_t nc = std::min(enc, c0 + cpb) - c0;
+    const int slot = k & 1;
+    if (col_bytes) {
+      if (k >= 2) HIP_TRY(hipEventSynchronize(ev.e[slot]));  // its last upload has left it
+      {
+        prof::HostScope hs("cache_image_read");
+        std::atomic<bool> short_read{false};
+        parallel_for(nc, [&](size_t c) {
+          uint8_t *to = stg[slot].b() + c * col_bytes;
+          const size_t at = ((c0 + c) * row_capacity + r_lo) * POS_WB, want = R * POS_WB;
+          if (fd < 0) {
+            std::memcpy(to, porenc + at, want);
+            return;
+          }
+          for (size_t got = 0; got < want;) {
+            const ssize_t n = pread(fd, to + got, want - got, (off_t)(at + got));
+            if (n <= 0) {
+              if (n < 0 && errno == EINTR) continue;
+              short_read = true;
+              return;
+            }
+            got += (size_t)n;
+          }
+        });
+        if (short_read) {
+          (void)hipStreamSynchronize(s);  // the other slot's upload may still be reading its staging
+          return fail(LCPC_ERR_INVALID_ARG, "encoded file shorter than row_capacity * encoded_size elements");
+        }
+      }
+      prof::Scope ps("cache_h2d", s);
+      HIP_TRY(hipMemcpyAsync(dcols[slot].p, stg[slot].p, nc * col_bytes, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipEventRecord(ev.e[slot], s));
+    }
+    HIP_TRY(leaf_chunk_cvs_slices(fid, dcols[slot].as<uint32_t>(), col_elems, n_rows, nc, c_lo, c_hi, dst + c0 * 8,
+                                  c_lo, enc, bad, s));
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  for (auto &b : dcols) b.settle();
+  return LCPC_OK;
+}
+
+lcpc_status cache_check_enc(size_t enc) {
+  if (enc < 2 || (enc & (enc - 1))) return fail(LCPC_ERR_INVALID_ARG, "encoded width must be a power of 2 (>= 2)");
+  return LCPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+lcpc_status lcpc_pos_update_chunk_range(size_t old_rows, size_t new_rows, size_t row_lo, size_t row_hi,
+                                        size_t *chunk_lo, size_t *chunk_hi) {
+  if (!chunk_lo || !chunk_hi) return fail(LCPC_ERR_INVALID_ARG, "null argument");
+  return pos_update_chunk_range(old_rows, new_rows, row_lo, row_hi, chunk_lo, chunk_hi);
+}
+
+size_t lcpc_pos_writer_n_chunks(const lcpc_pos_writer *w) {
+  return w && w->finalized ? w->chunks_done : 0;
+}
+
+lcpc_status lcpc_pos_writer_copy_cvs(const lcpc_pos_writer *w, uint8_t *out) {
+  if (!w || !out) return fail(LCPC_ERR_INVALID_ARG, "null argument");
+  if (!w->finalized) return fail(LCPC_ERR_INVALID_ARG, "writer not finalized");
+  std::memcpy(out, w->cvs.data(), w->cvs.size());
+  return LCPC_OK;
+}
+
+lcpc_status lcpc_pos_chunk_cache_from_porenc(const uint8_t *porenc, size_t enc, size_t rows_written,
+                                             size_t row_capacity, lcpc_pos_chunk_cache **out) {
+  lcpc_status st = cache_check_enc(enc);
+  if (st) return st;
+  if (!out || (!porenc && rows_written)) return fail(LCPC_ERR_INVALID_ARG, "null argument");
+  if (rows_written > row_capacity) return fail(LCPC_ERR_INVALID_ARG, "rows_written > row_capacity");
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  hipStream_t s = lease.s;
+  auto c = std::make_unique<lcpc_pos_chunk_cache>();
+  c->dev = dev;
+  c->enc = enc;
+  c->rows = rows_written;
+  c->n_chunks = c->cap_chunks = leaf_n_chunks(POS_FID, rows_written);
+  HIP_TRY(c->cvs.alloc(dev, c->cap_chunks * enc * 32));
+  DBuf dbad;
+  HIP_TRY(dbad.alloc(dev, 4));
+  HIP_TRY(hipMemsetAsync(dbad.p, 0, 4, s));
+  if ((st = cache_hash_chunks(dev, s, porenc, -1, enc, row_capacity, rows_written, 0, c->n_chunks, c->cvs.as<uint32_t>(),
+                              dbad.as<uint32_t>())))
+    return st;
+  uint32_t bad = 0;
+  HIP_TRY(hipMemcpyAsync(&bad, dbad.p, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  c->cvs.settle();
+  if (bad) return fail(LCPC_ERR_INVALID_ARG, "encoded file holds a non-canonical element (from_repr fails)");
+  *out = c.release();
+  return LCPC_OK;
+}
+
+lcpc_status lcpc_pos_chunk_cache_from_cvs(const uint8_t *cvs, size_t enc, size_t rows_written,
+                                          lcpc_pos_chunk_cache **out) {
+  lcpc_status st = cache_check_enc(enc);
+  if (st) return st;
+  if (!out || !cvs) return fail(LCPC_ERR_INVALID_ARG, "null argument");
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  auto c = std::make_unique<lcpc_pos_chunk_cache>();
+  c->dev = dev;
+  c->enc = enc;
+  c->rows = rows_written;
+  c->n_chunks = c->cap_chunks = leaf_n_chunks(POS_FID, rows_written);
+  if ((st = upload(dev, c->cvs, cvs, c->n_chunks * enc * 32))) return st;
+  HIP_TRY(hipStreamSynchronize(lease.s));
+  c->cvs.settle();
+  *out = c.release();
+  return LCPC_OK;
+}
+
+void lcpc_pos_chunk_cache_free(lcpc_pos_chunk_cache *c) { delete c; }
+size_t lcpc_pos_chunk_cache_enc(const lcpc_pos_chunk_cache *c) { return c ? c->enc : 0; }
+size_t lcpc_pos_chunk_cache_rows(const lcpc_pos_chunk_cache *c) { return c ? c->rows : 0; }
+size_t lcpc_pos_chunk_cache_n_chunks(const lcpc_pos_chunk_cache *c) { return c ? c->n_chunks : 0; }
+
+lcpc_status lcpc_pos_chunk_cache_copy_cvs(const lcpc_pos_chunk_cache *c, size_t chunk_lo, size_t chunk_hi,
+                                          uint8_t *out) {
+  if (!c) return fail(LCPC_ERR_INVALID_ARG, "null cache");
+  if (chunk_lo > chunk_hi || chunk_hi > c->n_chunks) return fail(LCPC_ERR_INVALID_ARG, "chunk range");
+  if (chunk_lo == chunk_hi) return LCPC_OK;
+  if (!out) return fail(LCPC_ERR_INVALID_ARG, "null argument");
+  Lease lease(c->dev);
+  HIP_TRY(hipSetDevice(c->dev->id));
+  HIP_TRY(hipMemcpyAsync(out, c->cvs.as<uint8_t>() + chunk_lo * c->enc * 32, (chunk_hi - chunk_lo) * c->enc * 32,
+                         hipMemcpyDeviceToHost, lease.s));
+  HIP_TRY(hipStreamSynchronize(lease.s));
+  return LCPC_OK;
+}
+
+static lcpc_status chunk_cache_update(lcpc_pos_chunk_cache *c, const uint8_t *porenc, int fd, size_t row_capacity,
+                                      size_t row_lo, size_t row_hi, size_t new_rows_written, size_t *chunk_lo,
+                                      size_t *chunk_hi) {
+  if (!c) return fail(LCPC_ERR_INVALID_ARG, "null cache");
+  size_t c_lo = 0, c_hi = 0;
+  lcpc_status st = pos_update_chunk_range(c->rows, new_rows_written, row_lo, row_hi, &c_lo, &c_hi);
+  if (st) return st;
+  if (new_rows_written > row_capacity) return fail(LCPC_ERR_INVALID_ARG, "rows_written > row_capacity");
+  if (!porenc && fd < 0 && new_rows_written) return fail(LCPC_ERR_INVALID_ARG, "null argument");
+  if (chunk_lo) *chunk_lo = c_lo;
+  if (chunk_hi) *chunk_hi = c_hi;
+  if (c_lo == c_hi) return LCPC_OK;
+  Device *dev = c->dev;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  hipStream_t s = lease.s;
+  const size_t enc = c->enc, new_chunks = leaf_n_chunks(POS_FID, new_rows_written);
+  // rehash into a side buffer: the cache is touched only once every element has passed the check
+  DBuf fresh, dbad;
+  HIP_TRY(fresh.alloc(dev, (c_hi - c_lo) * enc * 32));
+  HIP_TRY(dbad.alloc(dev, 4));
+  HIP_TRY(hipMemsetAsync(dbad.p, 0, 4, s));
+  if ((st = cache_hash_chunks(dev, s, porenc, fd, enc, row_capacity, new_rows_written, c_lo, c_hi, fresh.as<uint32_t>(),
+                              dbad.as<uint32_t>())))
+    return st;
+  uint32_t bad = 0;
+  HIP_TRY(hipMemcpyAsync(&bad, dbad.p, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (bad) return fail(LCPC_ERR_INVALID_ARG, "encoded file holds a non-canonical element (from_repr fails)");
+  if (new_chunks > c->cap_chunks) {  // grow by whole chunk rows (doubling, so appends stay amortised)
+    const size_t cap = std::max(new_chunks, 2 * c->cap_chunks);
+    DBuf bigger;
+    HIP_TRY(bigger.alloc(dev, cap * enc * 32));
+    HIP_TRY(hipMemcpyAsync(bigger.p, c->cvs.p, c->n_chunks * enc * 32, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    bigger.settle();
+    c->cvs = std::move(bigger);
+    c->cap_chunks = cap;
+  }
+  HIP_TRY(hipMemcpyAsync(c->cvs.as<uint8_t>() + c_lo * enc * 32, fresh.p, (c_hi - c_lo) * enc * 32,
+                         hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  c->rows = new_rows_written;
+  c->n_chunks = new_chunks;
+  return LCPC_OK;
+}
+
+lcpc_status lcpc_pos_chunk_cache_update(lcpc_pos_chunk_cache *c, const uint8_t *porenc, size_t row_capacity,
+                                        size_t row_lo, size_t row_hi, size_t new_rows_written, size_t *chunk_lo,
+                                        size_t *chunk_hi) {
+  return chunk_cache_update(c, porenc, -1, row_capacity, row_lo, row_hi, new_rows_written, chunk_lo, chunk_hi);
+}
+
+lcpc_status lcpc_pos_chunk_cache_update_fd(lcpc_pos_chunk_cache *c, int fd, size_t row_capacity, size_t row_lo,
+                                           size_t row_hi, size_t new_rows_written, size_t *chunk_lo,
+                                           size_t *chunk_hi) {
+  if (fd < 0) return fail(LCPC_ERR_INVALID_ARG, "file descriptor");
+  return chunk_cache_update(c, nullptr, fd, row_capacity, row_lo, row_hi, new_rows_written, chunk_lo, chunk_hi);
+}
+
+lcpc_status lcpc_pos_chunk_cache_tree(const lcpc_pos_chunk_cache *c, uint8_t *digests, uint8_t *tree) {
+  if (!c) return fail(LCPC_ERR_INVALID_ARG, "null cache");
+  Device *dev = c->dev;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  hipStream_t s = lease.s;
+  const size_t enc = c->enc;
+  DBuf hashes;
+  HIP_TRY(hashes.alloc(dev, (2 * enc - 1) * 32));
+  HIP_TRY(leaves_fold_cvs(c->cvs.as<uint32_t>(), enc, c->n_chunks, hashes.as<uint8_t>(), s));
+  if (tree) {
+    HIP_TRY(merkle_tree(hashes.as<uint8_t>(), enc, s));
+    HIP_TRY(hipMemcpyAsync(tree, hashes.p, (2 * enc - 1) * 32, hipMemcpyDeviceToHost, s));
+  }
+  if (digests) HIP_TRY(hipMemcpyAsync(digests, hashes.p, enc * 32, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return LCPC_OK;
+}
+
+lcpc_status lcpc_leaves_fold_cvs(const uint8_t *cvs, size_t n_chunks, size_t n_cols, uint8_t *leaves,
+                                 uint8_t *cvs_after) {
+  if ((!cvs || !leaves) && n_cols) return fail(LCPC_ERR_INVALID_ARG, "null argument");
+  if (n_chunks == 0) return fail(LCPC_ERR_INVALID_ARG, "n_chunks");
+  if (!n_cols) return LCPC_OK;
+  lcpc_status st;
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  DBuf dc, dl;
+  if ((st = upload(dev, dc, cvs, n_chunks * n_cols * 32))) return st;
+  HIP_TRY(dl.alloc(dev, n_cols * 32));
+  HIP_TRY(leaves_fold_cvs(dc.as<uint32_t>(), n_cols, n_chunks, dl.as<uint8_t>(), lease.s));
+  HIP_TRY(hipMemcpyAsync(leaves, dl.p, n_cols * 32, hipMemcpyDeviceToHost, lease.s));
+  if (cvs_after) HIP_TRY(hipMemcpyAsync(cvs_after, dc.p, n_chunks * n_cols * 32, hipMemcpyDeviceToHost, lease.s));
+  HIP_TRY(hipStreamSynchronize(lease.s));
+  return LCPC_OK;
+}
+
+}  // extern "C"
+
 // ColumnDigestAccumulator<Blake3, F> with ColumnsToCareAbout::All (column_digest_accumulator.rs:
 // 17-118): encoded rows pushed one batch at a time; every column's message is the 32 zero bytes
 // then the repr of its elements, hashed in 1-KiB BLAKE3 chunks on the GPU as soon as a chunk is
@@ -2701,6 +3008,10 @@ lcpc_status lcpc_column_digests_finalize(lcpc_column_digests *a, uint8_t *digest
   if (a->finalized) return fail(LCPC_ERR_INVALID_ARG, "accumulator already finalized");
   const size_t w = a->width;
   if (tree && (w < 2 || (w & (w - 1)))) return fail(LCPC_ERR_INVALID_ARG, "Input needs to be a power of two, at least two.");
+  // With no rows pushed every column's message is the 32-byte zero prefix alone: one chunk of one
+  // 32-byte block with ROOT, so each digest is BLAKE3(32 zero bytes), as the reference's untouched
+  // hashers give.  acc_run covers it: its upload of zero rows is an allocation only and the chunk
+  // kernel loads no element of a zero-row message.
   const size_t n_chunks = leaf_n_chunks(a->fid, a->rows_in);
   lcpc_status st = acc_run(a, n_chunks, a->rows_in);
   if (st) return st;

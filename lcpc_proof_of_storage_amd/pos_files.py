@@ -14,6 +14,8 @@ formats of the reference's proof-of-storage/src/lcpc_online (names kept):
   RowGeneratorIter      row_generator_iter.rs:8-165     (new_ligero, next, get_column_digests,
                         get_specified_column_digests, convert_to_commit_root, get_full_columns)
   ColumnDigestAccumulator, ColumnsToCareAbout   column_digest_accumulator.rs:9-118
+  ColumnChunkCache, the `.porcv` sidecar          no counterpart: incremental Merkle updates
+                        (FileHandler(chunk_cache=True)), same trees and files as without it
 
 Layout of a `.porenc` file (WriteableFt63): column c occupies row_capacity * 8 bytes starting at
 byte c * row_capacity * 8; its first rows_written elements are the canonical little-endian repr
@@ -159,6 +161,162 @@ def get_decoded_file_size_from_rate(encoded_file_size: int, pre_encoded_len: int
             * DATA_BYTE_CAPACITY * pre_encoded_len)
 
 
+# ---------------------------------------------------------------- column chunk-CV cache
+# A column digest is BLAKE3(32 zero bytes || the column's elements): a tree over 1-KiB chunks whose
+# chaining values (CVs) depend only on the chunk's bytes, its counter and whether it is the only
+# chunk.  Keeping them ([chunk][column] x 32 B) makes an edit or append rehash only the chunks it
+# touched ("Incremental Merkle updates").  The `.porcv` sidecar stores them next to the
+# reference's four files: a 64-byte header, then the CVs.
+CHUNK_CV_EXTENSION = "porcv"
+CHUNK_CV_MAGIC = b"PORCV\x00\x00\x01"   # 8 bytes: name and format version 1
+CHUNK_CV_HEADER_BYTES = 64
+CHUNK_BYTES, CV_BYTES = 1024, 32
+
+
+def leaf_n_chunks(rows_written: int) -> int:
+    """1-KiB chunks of a column message of rows_written elements (the empty message has one)."""
+    return max(1, -(-(DIGEST_BYTES + rows_written * WRITTEN_BYTES_WIDTH) // CHUNK_BYTES))
+
+
+def encode_chunk_cv_header(enc: int, rows_written: int, n_chunks: int, root: bytes) -> bytes:
+    """magic/version, u64 LE enc, rows_written, n_chunks, the 32-byte root the CVs fold to."""
+    if len(root) != DIGEST_BYTES:
+        raise ValueError("root must be 32 bytes")
+    return (CHUNK_CV_MAGIC + enc.to_bytes(8, "little") + rows_written.to_bytes(8, "little")
+            + n_chunks.to_bytes(8, "little") + bytes(root))
+
+
+def parse_chunk_cv_header(header: bytes) -> Tuple[int, int, int, bytes]:
+    """(enc, rows_written, n_chunks, root); ValueError on a short header or another magic."""
+    if len(header) < CHUNK_CV_HEADER_BYTES:
+        raise ValueError("chunk-CV sidecar shorter than its header")
+    if header[:8] != CHUNK_CV_MAGIC:
+        raise ValueError("not a chunk-CV sidecar (magic / version)")
+    enc, rows, n_chunks = (int.from_bytes(header[8 + 8 * i:16 + 8 * i], "little") for i in range(3))
+    return enc, rows, n_chunks, bytes(header[32:64])
+
+
+def check_chunk_cv_sidecar(header: bytes, file_len: int, enc: int, rows_written: int, root: bytes) -> int:
+    """The sidecar's n_chunks if its header matches the file's metadata (enc, rows_written), its
+    length holds every CV and its root is the stored tree's; ValueError otherwise."""
+    h_enc, h_rows, h_chunks, h_root = parse_chunk_cv_header(header)
+    if (h_enc, h_rows) != (enc, rows_written) or h_chunks != leaf_n_chunks(rows_written):
+        raise ValueError("chunk-CV sidecar is for other dimensions")
+    if file_len < CHUNK_CV_HEADER_BYTES + h_chunks * h_enc * CV_BYTES:
+        raise ValueError("chunk-CV sidecar body is short")
+    if h_root != bytes(root):
+        raise ValueError("chunk-CV sidecar root differs from the stored tree's")
+    return h_chunks
+
+
+def write_chunk_cv_sidecar(path: str, enc: int, rows_written: int, root: bytes, cvs: np.ndarray,
+                           chunk_lo: int = 0, n_chunks: Optional[int] = None) -> None:
+    """cvs = the CVs of chunks [chunk_lo, chunk_lo + len(cvs)); the other chunk rows of an existing
+    sidecar stay.  The body is written first, then the header (a torn write leaves a header whose
+    root no longer matches the tree, and the next attach rebuilds)."""
+    cvs = np.ascontiguousarray(cvs, dtype=np.uint8).reshape(-1, enc, CV_BYTES)
+    n_chunks = leaf_n_chunks(rows_written) if n_chunks is None else n_chunks
+    if chunk_lo + cvs.shape[0] > n_chunks:
+        raise ValueError("chunk rows beyond the sidecar")
+    whole = chunk_lo == 0 and cvs.shape[0] == n_chunks
+    if not whole and not os.path.isfile(path):
+        raise FileNotFoundError("no chunk-CV sidecar to update")
+    with open(path, "w+b" if whole else "r+b") as f:
+        f.truncate(CHUNK_CV_HEADER_BYTES + n_chunks * enc * CV_BYTES)
+        f.seek(CHUNK_CV_HEADER_BYTES + chunk_lo * enc * CV_BYTES)
+        f.write(cvs.tobytes())
+        f.flush()
+        f.seek(0)
+        f.write(encode_chunk_cv_header(enc, rows_written, n_chunks, root))
+
+
+class ColumnChunkCache:
+    """lcpc_pos_chunk_cache: every column's chunk CVs, resident on the GPU."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @classmethod
+    def from_porenc(cls, image: np.ndarray, enc: int, rows_written: int, row_capacity: int) -> "ColumnChunkCache":
+        """One full pass over a `.porenc` image (a u8 array, typically over an mmap)."""
+        h = N.vp()
+        _raise(N.load().lcpc_pos_chunk_cache_from_porenc(_u8(image), enc, rows_written, row_capacity, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_cvs(cls, cvs, enc: int, rows_written: int) -> "ColumnChunkCache":
+        a = np.ascontiguousarray(cvs, dtype=np.uint8).reshape(-1)
+        if a.size != leaf_n_chunks(rows_written) * enc * CV_BYTES:
+            raise ValueError("cvs must hold leaf_n_chunks(rows_written) * enc chaining values")
+        h = N.vp()
+        _raise(N.load().lcpc_pos_chunk_cache_from_cvs(_u8(a), enc, rows_written, C.byref(h)))
+        return cls(h)
+
+    @staticmethod
+    def update_chunk_range(old_rows: int, new_rows: int, row_lo: int, row_hi: int) -> Tuple[int, int]:
+        """The chunks [lo, hi) an update rehashes (lcpc_pos_update_chunk_range; host only)."""
+        lo, hi = C.c_size_t(), C.c_size_t()
+        _raise(N.load().lcpc_pos_update_chunk_range(old_rows, new_rows, row_lo, row_hi, C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
+
+    @property
+    def enc(self) -> int:
+        return N.load().lcpc_pos_chunk_cache_enc(self._h)
+
+    @property
+    def rows(self) -> int:
+        return N.load().lcpc_pos_chunk_cache_rows(self._h)
+
+    @property
+    def n_chunks(self) -> int:
+        return N.load().lcpc_pos_chunk_cache_n_chunks(self._h)
+
+    def copy_cvs(self, chunk_lo: int = 0, chunk_hi: Optional[int] = None) -> np.ndarray:
+        chunk_hi = self.n_chunks if chunk_hi is None else chunk_hi
+        out = np.zeros((max(chunk_hi - chunk_lo, 0), self.enc, CV_BYTES), np.uint8)
+        _raise(N.load().lcpc_pos_chunk_cache_copy_cvs(self._h, chunk_lo, chunk_hi, _u8(out)))
+        return out
+
+    def update(self, image: np.ndarray, row_capacity: int, row_lo: int, row_hi: int,
+               new_rows_written: int) -> Tuple[int, int]:
+        """Rows [row_lo, row_hi) of the image changed, the file now has new_rows_written rows:
+        rehash the affected chunks only; returns the chunk range rewritten."""
+        lo, hi = C.c_size_t(), C.c_size_t()
+        _raise(N.load().lcpc_pos_chunk_cache_update(self._h, _u8(image), row_capacity, row_lo, row_hi,
+                                                    new_rows_written, C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
+
+    def update_file(self, encoded_file, row_capacity: int, row_lo: int, row_hi: int,
+                    new_rows_written: int) -> Tuple[int, int]:
+        """update() with the image read from the open `.porenc` file (pread of the affected
+        slices): no mapping of the whole file for 1 KiB per column."""
+        lo, hi = C.c_size_t(), C.c_size_t()
+        _raise(N.load().lcpc_pos_chunk_cache_update_fd(self._h, encoded_file.fileno(), row_capacity, row_lo, row_hi,
+                                                       new_rows_written, C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
+
+    def digests(self) -> np.ndarray:
+        d = np.zeros((self.enc, DIGEST_BYTES), np.uint8)
+        _raise(N.load().lcpc_pos_chunk_cache_tree(self._h, _u8(d), None))
+        return d
+
+    def tree(self) -> MerkleTree:
+        t = np.zeros((2 * self.enc - 1, DIGEST_BYTES), np.uint8)
+        _raise(N.load().lcpc_pos_chunk_cache_tree(self._h, None, _u8(t)))
+        return MerkleTree(t)
+
+    def close(self) -> None:
+        if self._h is not None:
+            N.load().lcpc_pos_chunk_cache_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ---------------------------------------------------------------- mapped file images
 class _Image:
     """A read/write mmap of a `.porenc` file (zero-length files map to nothing)."""
@@ -250,7 +408,7 @@ class EncodedFileWriter:
         _raise(N.load().lcpc_pos_writer_push_bytes(self._h, p, len(data)))
         self.bytes_received += len(data)
 
-    def _finalize(self, want_digests: bool, want_tree: bool):
+    def _finalize(self, want_digests: bool, want_tree: bool, keep_chunk_cvs: bool = False):
         if self._done:
             raise RuntimeError("writer already finalized")
         self._ensure_capacity(self._rows_for(self.bytes_received))
@@ -262,6 +420,8 @@ class EncodedFileWriter:
             _raise(N.load().lcpc_pos_writer_finalize(
                 self._h, _u8(digests) if want_digests else None, _u8(tree) if want_tree else None,
                 C.byref(rows), C.byref(nbytes)))
+            if keep_chunk_cvs:  # the [chunk][column] CVs the digests were folded from
+                self.chunk_cvs = _writer_chunk_cvs(self._h, w)
         finally:
             self._done = True
             N.load().lcpc_pos_writer_free(self._h)
@@ -277,8 +437,9 @@ class EncodedFileWriter:
         _, t = self._finalize(False, True)
         return self.get_encoded_file_metadata(), t[-1].tobytes()
 
-    def finalize_to_merkle_tree(self) -> Tuple[EncodedFileMetadata, MerkleTree]:
-        _, t = self._finalize(False, True)
+    def finalize_to_merkle_tree(self, keep_chunk_cvs: bool = False) -> Tuple[EncodedFileMetadata, MerkleTree]:
+        """keep_chunk_cvs: also leave the column chunk CVs in self.chunk_cvs (ColumnChunkCache)."""
+        _, t = self._finalize(False, True, keep_chunk_cvs)
         return self.get_encoded_file_metadata(), MerkleTree(t)
 
     def __del__(self):
@@ -292,9 +453,11 @@ class EncodedFileWriter:
     @staticmethod
     def convert_unencoded_file(unencoded_file, target_encoded_file: str,
                                target_digest_file: Optional[str], target_metadata_file: Optional[str],
-                               num_pre_encoded_columns: int, num_encoded_columns: int
+                               num_pre_encoded_columns: int, num_encoded_columns: int,
+                               target_chunk_cv_file: Optional[str] = None
                                ) -> Tuple[EncodedFileMetadata, MerkleTree]:
-        """encoded_file_writer.rs:134-231: the whole file in one pass of the GPU writer."""
+        """encoded_file_writer.rs:134-231: the whole file in one pass of the GPU writer.
+        target_chunk_cv_file: also write the `.porcv` sidecar, from the CVs that pass computed."""
         if num_pre_encoded_columns < 1:
             raise ValueError("Number of pre-encoded columns must be greater than 0")
         if num_encoded_columns < 2 or num_encoded_columns & (num_encoded_columns - 1):
@@ -313,9 +476,21 @@ class EncodedFileWriter:
                 data = np.frombuffer(src, np.uint8) if total else np.zeros(0, np.uint8)
                 tree = np.zeros((2 * num_encoded_columns - 1, DIGEST_BYTES), np.uint8)
                 rows = C.c_size_t()
-                _raise(N.load().lcpc_pos_encode_file(_u8(data), total, num_pre_encoded_columns,
-                                                     num_encoded_columns, cap, img.ptr(), _u8(tree),
-                                                     C.byref(rows)))
+                cvs = None
+                if target_chunk_cv_file is None:
+                    _raise(N.load().lcpc_pos_encode_file(_u8(data), total, num_pre_encoded_columns,
+                                                         num_encoded_columns, cap, img.ptr(), _u8(tree),
+                                                         C.byref(rows)))
+                else:  # the same writer, called in steps so its CVs can be taken before it goes
+                    h = N.vp()
+                    _raise(N.load().lcpc_pos_writer_new(num_pre_encoded_columns, num_encoded_columns,
+                                                        img.ptr(), cap, 0, C.byref(h)))
+                    try:
+                        _raise(N.load().lcpc_pos_writer_push_bytes(h, _u8(data), total))
+                        _raise(N.load().lcpc_pos_writer_finalize(h, None, _u8(tree), C.byref(rows), None))
+                        cvs = _writer_chunk_cvs(h, num_encoded_columns)
+                    finally:
+                        N.load().lcpc_pos_writer_free(h)
                 del data
             finally:
                 if src is not None:
@@ -329,7 +504,17 @@ class EncodedFileWriter:
         if target_digest_file:
             with open(target_digest_file, "wb") as f:
                 write_tree_to_file(f, mt)
+        if target_chunk_cv_file:
+            write_chunk_cv_sidecar(target_chunk_cv_file, num_encoded_columns, rows.value, mt.root(), cvs)
         return meta, mt
+
+
+def _writer_chunk_cvs(writer_handle, enc: int) -> np.ndarray:
+    """The [chunk][column] CVs of a finalized lcpc_pos_writer."""
+    n = N.load().lcpc_pos_writer_n_chunks(writer_handle)
+    cvs = np.zeros((n, enc, CV_BYTES), np.uint8)
+    _raise(N.load().lcpc_pos_writer_copy_cvs(writer_handle, _u8(cvs)))
+    return cvs
 
 
 # ---------------------------------------------------------------- streamed rows
@@ -653,9 +838,15 @@ class FileHandler:
     re-encode only the touched rows (lcpc_pos_reencode_rows: pack, NTT and transpose on the GPU,
     written into the mapped `.porenc`), then rebuild the tree from the file on the GPU
     (lcpc_pos_porenc_tree), as the reference's edit_bytes / append_bytes do.
+
+    chunk_cache=True (off by default; nothing changes without it) keeps a ColumnChunkCache and its
+    `<ulid>.porcv` sidecar next to the four files: edit_bytes and append_bytes then reread and
+    rehash only the 1-KiB column chunks they touched and fold the tree from the cache, instead of
+    the whole `.porenc`.  The `.porenc`, `.portree` and `.meta` files are the same either way.
     """
 
-    def __init__(self, ulid: str, unencoded: str, encoded: str, merkle: str, metadata: str):
+    def __init__(self, ulid: str, unencoded: str, encoded: str, merkle: str, metadata: str,
+                 chunk_cache: bool = False):
         # new_attach_to_existing_files (:73-143)
         with open(metadata, "rb") as f:
             m = EncodedFileMetadata.read_from_file(f)
@@ -669,25 +860,82 @@ class FileHandler:
         self.merkle_tree_file_handle, self.metadata_file_handle = merkle, metadata
         with open(merkle, "rb") as f:
             self.merkle_tree = MerkleTree.from_bytes(f.read())
+        self.chunk_cache: Optional[ColumnChunkCache] = None
+        self.chunk_cv_file_handle = os.path.join(os.path.dirname(encoded), f"{ulid}.{CHUNK_CV_EXTENSION}")
+        self.last_chunk_range = (0, 0)   # chunks the last edit / append rehashed (chunk_cache only)
+        if chunk_cache:
+            self._attach_chunk_cache()
 
     # -- construction
     @classmethod
-    def new_attach_to_existing_ulid(cls, file_directory: str, ulid: str) -> "FileHandler":
+    def new_attach_to_existing_ulid(cls, file_directory: str, ulid: str, chunk_cache: bool = False) -> "FileHandler":
         paths = [os.path.join(file_directory, f"{ulid}.{e}") for e in
                  (UNENCODED_FILE_EXTENSION, ENCODED_FILE_EXTENSION, MERKLE_FILE_EXTENSION, METADATA_FILE_EXTENSION)]
         for p, what in zip(paths, ("unencoded", "encoded", "merkle", "metadata")):
             if not os.path.isfile(p):
                 raise FileNotFoundError(f"no {what} file found!")
-        return cls(ulid, *paths)
+        return cls(ulid, *paths, chunk_cache=chunk_cache)
 
     @classmethod
-    def new_attach_to_existing_files(cls, ulid, unencoded, encoded, merkle, metadata) -> "FileHandler":
-        return cls(ulid, unencoded, encoded, merkle, metadata)
+    def new_attach_to_existing_files(cls, ulid, unencoded, encoded, merkle, metadata,
+                                     chunk_cache: bool = False) -> "FileHandler":
+        return cls(ulid, unencoded, encoded, merkle, metadata, chunk_cache=chunk_cache)
+
+    # -- the column chunk-CV cache (chunk_cache=True)
+    def _with_image(self, fn):
+        """fn(u8 array over a read-only mmap of the .porenc image); no view of it may escape fn."""
+        with open(self.encoded_file_handle, "rb") as f:
+            return self._reader(f)._with_map(fn)
+
+    def _rebuild_chunk_cache(self) -> ColumnChunkCache:
+        """One full pass over the .porenc (the cost of recalculate_merkle_tree)."""
+        return self._with_image(lambda a: ColumnChunkCache.from_porenc(a, self.encoded_size, self.rows_written,
+                                                                       self.row_capacity))
+
+    def _attach_chunk_cache(self) -> None:
+        """Load the sidecar if it belongs to this file as it stands (header against the metadata,
+        length, root against the stored tree, and the CVs really fold to that root); otherwise --
+        a missing sidecar included -- rebuild it from the .porenc and rewrite it."""
+        cache = None
+        try:
+            with open(self.chunk_cv_file_handle, "rb") as f:
+                header = f.read(CHUNK_CV_HEADER_BYTES)
+                n_chunks = check_chunk_cv_sidecar(header, os.fstat(f.fileno()).st_size, self.encoded_size,
+                                                  self.rows_written, self.merkle_tree.root())
+                body = np.fromfile(f, np.uint8, n_chunks * self.encoded_size * CV_BYTES)
+            cache = ColumnChunkCache.from_cvs(body, self.encoded_size, self.rows_written)
+            if cache.tree() != self.merkle_tree:
+                cache.close()
+                cache = None
+        except (OSError, ValueError):
+            cache = None
+        if cache is None:
+            cache = self._rebuild_chunk_cache()
+            write_chunk_cv_sidecar(self.chunk_cv_file_handle, self.encoded_size, self.rows_written,
+                                   cache.tree().root(), cache.copy_cvs())
+        if self.chunk_cache is not None:
+            self.chunk_cache.close()
+        self.chunk_cache = cache
+
+    def _update_chunk_cache(self, row_lo: int, row_hi: int) -> MerkleTree:
+        """After rows [row_lo, row_hi) were re-encoded into the .porenc (self.rows_written is the
+        new count): rehash their chunks, fold the tree, rewrite those chunk rows of the sidecar
+        and the .portree."""
+        cache = self.chunk_cache
+        with open(self.encoded_file_handle, "rb") as f:
+            lo, hi = cache.update_file(f, self.row_capacity, row_lo, row_hi, self.rows_written)
+        self.last_chunk_range = (lo, hi)
+        tree = cache.tree()
+        write_chunk_cv_sidecar(self.chunk_cv_file_handle, self.encoded_size, self.rows_written, tree.root(),
+                               cache.copy_cvs(lo, hi), lo, cache.n_chunks)
+        self.merkle_tree = tree
+        self.write_tree(tree)
+        return tree
 
     @classmethod
     def create_from_unencoded_file(cls, ulid: str, file_handle_if_not_already_ulid: Optional[str],
                                    pre_encoded_size: int, encoded_size: int,
-                                   directory: Optional[str] = None) -> "FileHandler":
+                                   directory: Optional[str] = None, chunk_cache: bool = False) -> "FileHandler":
         """:145-199 -- the raw file is moved to <ulid>.porraw, then encoded (GPU writer)."""
         if encoded_size <= 0 or encoded_size & (encoded_size - 1):
             raise ValueError("encoded file size must be a power of two!")
@@ -697,12 +945,13 @@ class FileHandler:
         meta = _location(directory, ulid, METADATA_FILE_EXTENSION)
         if file_handle_if_not_already_ulid is not None:
             os.rename(file_handle_if_not_already_ulid, raw)
+        cv = _location(directory, ulid, CHUNK_CV_EXTENSION) if chunk_cache else None
         with open(raw, "r+b") as f:
-            m, _ = EncodedFileWriter.convert_unencoded_file(f, enc, tree, meta, pre_encoded_size, encoded_size)
+            m, _ = EncodedFileWriter.convert_unencoded_file(f, enc, tree, meta, pre_encoded_size, encoded_size, cv)
         m.ulid = ulid
         with open(meta, "wb") as f:
             m.write_to_file(f)
-        return cls(ulid, raw, enc, tree, meta)
+        return cls(ulid, raw, enc, tree, meta, chunk_cache=chunk_cache)
 
     # -- accessors
     def get_encoded_file_handle(self) -> str:
@@ -835,12 +1084,17 @@ class FileHandler:
             w = EncodedFileWriter(self.pre_encoded_size, self.encoded_size, self.total_data_bytes, tf)
             if self.total_data_bytes:
                 w.push_bytes(raw.read())
-            m, tree = w.finalize_to_merkle_tree()
+            m, tree = w.finalize_to_merkle_tree(keep_chunk_cvs=self.chunk_cache is not None)
         self.write_tree(tree)
         self.pre_encoded_size, self.encoded_size = m.pre_encoded_size, m.encoded_size
         self.total_data_bytes, self.row_capacity, self.rows_written = m.bytes_of_data, m.row_capacity, m.rows_written
         self._write_metadata()
         self.merkle_tree = tree
+        if self.chunk_cache is not None:  # the writer's own CVs: no second pass
+            write_chunk_cv_sidecar(self.chunk_cv_file_handle, self.encoded_size, self.rows_written, tree.root(),
+                                   w.chunk_cvs)
+            self.chunk_cache.close()
+            self.chunk_cache = ColumnChunkCache.from_cvs(w.chunk_cvs, self.encoded_size, self.rows_written)
 
     def edit_bytes(self, byte_start: int, unencoded_bytes_to_add: bytes) -> Tuple[bytes, MerkleTree]:
         """:279-333 -- returns the bytes that were replaced and the new tree."""
@@ -855,7 +1109,10 @@ class FileHandler:
             f.seek(byte_start)
             f.write(unencoded_bytes_to_add)
         rb = self._row_bytes()
-        self._reencode_rows(byte_start // rb, -(-(byte_start + n) // rb))
+        row_lo, row_hi = byte_start // rb, -(-(byte_start + n) // rb)
+        self._reencode_rows(row_lo, row_hi)
+        if self.chunk_cache is not None:
+            return original, self._update_chunk_cache(row_lo, max(row_lo, row_hi))
         return original, self.recalculate_merkle_tree()
 
     def append_bytes(self, bytes_to_add: bytes) -> MerkleTree:
@@ -872,7 +1129,11 @@ class FileHandler:
         self.total_data_bytes += len(bytes_to_add)
         self.rows_written = end_row
         self._reencode_rows(start_row, end_row)
-        tree = self.recalculate_merkle_tree()
+        # (the capacity growth above re-lays the image but changes no value: the cache stays valid)
+        if self.chunk_cache is not None:
+            tree = self._update_chunk_cache(start_row, max(start_row, end_row))
+        else:
+            tree = self.recalculate_merkle_tree()
         self._write_metadata()
         return tree
 
@@ -882,11 +1143,14 @@ class FileHandler:
         with open(self.unencoded_file_handle, "r+b") as f:
             m, tree = EncodedFileWriter.convert_unencoded_file(
                 f, self.encoded_file_handle, self.merkle_tree_file_handle, self.metadata_file_handle,
-                new_pre_encoded_columns, new_encoded_columns)
+                new_pre_encoded_columns, new_encoded_columns,
+                self.chunk_cv_file_handle if self.chunk_cache is not None else None)
         self.pre_encoded_size, self.encoded_size = new_pre_encoded_columns, new_encoded_columns
         self.rows_written, self.row_capacity = m.rows_written, m.row_capacity
         self.merkle_tree = tree
         self._write_metadata()  # keeps the ulid, which convert_unencoded_file's metadata lacks
+        if self.chunk_cache is not None:
+            self._attach_chunk_cache()  # the sidecar that pass just wrote, for the new shape
         m.ulid = self.file_ulid
         return m, tree
 
@@ -926,6 +1190,15 @@ class FileHandler:
                                              _u8(img), _u8(tree), C.byref(out_rows)))
         if MerkleTree(tree) != self.merkle_tree:
             raise AssertionError("the raw file's re-encoded tree differs from the stored tree")
+        if self.chunk_cache is not None:
+            if self.chunk_cache.tree() != self.merkle_tree:
+                raise AssertionError("the chunk-CV cache folds to a tree that differs from the stored tree")
+            fresh = self._rebuild_chunk_cache()
+            try:
+                if not np.array_equal(fresh.copy_cvs(), self.chunk_cache.copy_cvs()):
+                    raise AssertionError("the chunk-CV cache differs from one rebuilt from the encoded file")
+            finally:
+                fresh.close()
 
     def recalculate_tree_only(self) -> MerkleTree:
         with open(self.encoded_file_handle, "rb") as f:
@@ -936,6 +1209,11 @@ class FileHandler:
         for p in (self.unencoded_file_handle, self.encoded_file_handle, self.merkle_tree_file_handle,
                   self.metadata_file_handle):
             os.remove(p)
+        if self.chunk_cache is not None:
+            self.chunk_cache.close()
+            self.chunk_cache = None
+        if os.path.isfile(self.chunk_cv_file_handle):  # (also one an earlier cached handler left)
+            os.remove(self.chunk_cv_file_handle)
         d = os.path.dirname(self.unencoded_file_handle)
         if not os.listdir(d):
             os.rmdir(d)
