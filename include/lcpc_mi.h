@@ -30,7 +30,9 @@
 extern "C" {
 #endif
 
-#define LCPC_ABI_VERSION 2 /* 2: the PoS column chunk-CV cache (lcpc_pos_chunk_cache_*) */
+/* 2: the PoS column chunk-CV cache (lcpc_pos_chunk_cache_*); 3: R-S erasure decoding, scrub and
+ * repair of stored files (lcpc_rs_*, lcpc_pos_scrub_porenc, lcpc_pos_repair_columns) */
+#define LCPC_ABI_VERSION 3
 
 typedef enum lcpc_status {
   LCPC_OK = 0,
@@ -60,7 +62,10 @@ typedef enum lcpc_status {
   LCPC_ERR_NO_DEVICE = 33,
   LCPC_ERR_UNSUPPORTED = 34,
   /* a caller-owned transcript's callback (lcpc_transcript_ops) returned non-zero */
-  LCPC_ERR_TRANSCRIPT = 35
+  LCPC_ERR_TRANSCRIPT = 35,
+  /* erasure decoding: more erasures than the code's redundancy, or the surviving positions are
+   * not those of a codeword (no reference counterpart) */
+  LCPC_ERR_UNRECOVERABLE = 36
 } lcpc_status;
 
 typedef enum lcpc_field {
@@ -710,6 +715,59 @@ lcpc_status lcpc_sharded_p2p_schedule(lcpc_field f, size_t n_rows, size_t n_per_
                                       size_t n_degree_tests, size_t n_col_opens, int nranks, int rank,
                                       size_t n_polys, size_t lag, lcpc_p2p_record *out, size_t cap,
                                       size_t *n_out);
+
+/* ------------------------------------------------------------------ R-S erasure decoding, scrub, repair
+ * NO COUNTERPART IN THE REFERENCE.  Its decode_row is a plain ifft_oi over the whole stored row
+ * (lcpc_online.rs:568-574: one flipped byte corrupts the row's pre x 7 decoded bytes) and
+ * FileHandler::verify_all_files_agree (file_handler.rs:505-541) can only say "trees differ".  A
+ * stored file is Reed-Solomon encoded at rate <= 1/2 and column-major, so damage lands in few
+ * columns, the `.portree` leaves say which, and a row of len evaluations of a polynomial of degree
+ * < n_per_row is determined by any n_per_row of them: up to len - n_per_row damaged columns are
+ * recomputed from the others.  With L(x) = prod_{j erased} (x - x_j): the surviving evaluations
+ * times L(x_c) are those of P = f L (zero at the erased positions, which are never read), ifft_oi
+ * gives P's coefficients -- all zero from index n_per_row + n_erased on, or the row is no codeword
+ * -- and f(x_j) = P'(x_j) / L'(x_j) at the erased positions, one fft_io of the formal derivative.
+ * Two transforms per row, as one decode plus one re-encode.  Existing entry points, file formats
+ * and trees are unchanged. */
+/* Host only (no device): the len evaluation points in codeword order, Montgomery limbs
+ * (len x limbs u64): position c of an encoded row is f(out[c]), i.e. out = fft_io of the
+ * polynomial x, under the switches of lcpc_fft_convention.h the library was built with.
+ * LCPC_FFT_NOT_POWER_OF_TWO / LCPC_FFT_TOO_BIG for a bad length. */
+lcpc_status lcpc_rs_domain_points(lcpc_field f, size_t len, uint64_t *out);
+/* rows: n_rows x len elements (host, row-major, Montgomery, as lcpc_ifft_oi_rows), codewords of
+ * messages of n_per_row coefficients whose positions erased[0..n_erased) are unknown (never read:
+ * they may hold anything).  Fills those positions of every row in place with fully reduced
+ * Montgomery values; every other limb keeps its bits.  LCPC_ERR_INVALID_ARG: an index >= len, a
+ * duplicate index, n_per_row outside [1, len).  LCPC_ERR_UNRECOVERABLE: n_erased > len - n_per_row,
+ * or some row's surviving positions are not those of a codeword (checked whenever n_erased <
+ * len - n_per_row); no row is written then.  n_erased == 0 is that consistency check alone.  Rows
+ * go through the device in batches of bounded size.  All five fields. */
+lcpc_status lcpc_rs_erasure_decode_rows(lcpc_field f, uint64_t *rows, size_t n_rows, size_t len,
+                                        size_t n_per_row, const uint64_t *erased, size_t n_erased);
+/* The damage locator of a stored `.porenc` image (layout: lcpc_pos_encode_file): each column's
+ * first rows_written elements hashed as lcpc_pos_porenc_tree does and compared on the device with
+ * leaves (enc x 32 B, e.g. the head of the `.portree`).  status[c] = 0: the digest equals the leaf;
+ * 1: it differs; 2: the column holds an element that is not < p (its digest is then written as
+ * zeros).  Unlike lcpc_pos_porenc_tree a non-canonical element is a finding, not an error.  digests
+ * (enc x 32 B) may be NULL; *n_bad (may be NULL) = the number of non-zero status bytes.  Rows past
+ * rows_written are not looked at. */
+lcpc_status lcpc_pos_scrub_porenc(const uint8_t *porenc, size_t enc, size_t rows_written,
+                                  size_t row_capacity, const uint8_t *leaves, uint8_t *digests,
+                                  uint8_t *status, size_t *n_bad);
+/* Recomputes the columns bad_cols[0..n_bad) of the image from its other columns, which alone are
+ * read.  The image is const: the caller decides what to write.  Any output may be NULL:
+ *   cols_out     n_bad x rows_written x 8 B: column k = the canonical little-endian elements of
+ *                column bad_cols[k], as they belong in the image;
+ *   digests_out  n_bad x 32 B: their column digests (leaves), accumulated over the row batches as
+ *                chunk chaining values like the writer's;
+ *   data_out     rows_written x pre x 7 B: the decoded file (lcpc_pos_decode_porenc of the
+ *                completed rows): the read-only recovery path for a download from a damaged replica.
+ * Errors as lcpc_rs_erasure_decode_rows with len = enc, n_per_row = pre; LCPC_ERR_UNRECOVERABLE also
+ * when a column that is not listed holds a non-canonical element.  The outputs are undefined after
+ * an error. */
+lcpc_status lcpc_pos_repair_columns(const uint8_t *porenc, size_t pre, size_t enc, size_t rows_written,
+                                    size_t row_capacity, const uint64_t *bad_cols, size_t n_bad,
+                                    uint8_t *cols_out, uint8_t *digests_out, uint8_t *data_out);
 
 /* ------------------------------------------------------------------ diagnostics
  * On-device check of the stream-ordered buffer pool the commit / prove / shard paths share

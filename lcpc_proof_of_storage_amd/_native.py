@@ -203,6 +203,10 @@ SIGNATURES = {
     "lcpc_pos_writer_n_chunks": (sz, [vp]),
     "lcpc_pos_writer_copy_cvs": (i32, [vp, u8p]),
     "lcpc_leaves_fold_cvs": (i32, [u8p, sz, sz, u8p, u8p]),
+    "lcpc_rs_domain_points": (i32, [i32, sz, u64p]),
+    "lcpc_rs_erasure_decode_rows": (i32, [i32, u64p, sz, sz, sz, u64p, sz]),
+    "lcpc_pos_scrub_porenc": (i32, [u8p, sz, sz, sz, u8p, u8p, u8p, szp]),
+    "lcpc_pos_repair_columns": (i32, [u8p, sz, sz, sz, sz, u64p, sz, u8p, u8p, u8p]),
     "lcpc_challenge_tensor": (i32, [vp, i32, sz, u64p]),
     "lcpc_transcript_append_field_elems": (i32, [vp, u8p, sz, i32, u64p, sz]),
     "lcpc_challenge_columns": (i32, [vp, sz, sz, u64p]),

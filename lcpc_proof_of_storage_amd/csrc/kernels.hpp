@@ -167,4 +167,43 @@ hipError_t copy_words(void *dst, const void *src, size_t bytes, hipStream_t s, b
 hipError_t mul_elementwise(int fid, const uint32_t *a, const uint32_t *b, uint32_t *out,
                            size_t n, hipStream_t s);
 
+// ------------------------------------------------------------------ R-S erasure decoding (erasure.hip)
+// Rows of n = 2^log_n evaluations with the positions erased[0..n_erased) missing.  tw is a FORWARD
+// plan's d_tw (the evaluation points follow include/lcpc_fft_convention.h).  The caller has checked
+// the indices (each < n, no duplicates).
+// slot[c] = j if c == erased[j], else -1; lambda[c] = prod_{j} (x_c - x_erased[j]) for c not erased
+// (0 at the erased c); dinv[j] = 1 / prod_{i != j} (x_erased[j] - x_erased[i]).  Montgomery.
+hipError_t erasure_locator(int fid, const uint32_t *tw, int log_n, const uint32_t *erased, size_t n_erased,
+                           int32_t *slot, uint32_t *lambda, uint32_t *dinv, hipStream_t s);
+// dscale[k] = (k + 1) / n for k < n (Montgomery) from the canonical words of n^-1
+hipError_t erasure_dscale(int fid, int log_n, const uint32_t *inv_n_canon_words, uint32_t *dscale, hipStream_t s);
+// out[r][.] = in[r][c] * lambda[c] (0 at the erased c, which are not read), laid out as the natural-
+// order input of the inverse plan's ntt_rows (the opening reorder of ifft_oi folded in)
+hipError_t erasure_masked_rows(int fid, const uint32_t *in, uint32_t *out, int log_n, size_t n_rows,
+                               const int32_t *slot, const uint32_t *lambda, hipStream_t s);
+// the same from a column-major batch src[c][r] (r < B) of canonical elements (a `.porenc` slice; Ft63
+// only): transposed, converted to Montgomery form, masked.  plain (optional): the unmasked Montgomery
+// rows plain[r][c] at the columns that are not erased.  *bad = 1 if a column that is read holds an
+// element that is not < p; erased columns are never read.
+hipError_t erasure_masked_cols(int fid, const uint32_t *src, size_t B, int log_n, uint32_t *out, uint32_t *plain,
+                               const int32_t *slot, const uint32_t *lambda, uint32_t *bad, hipStream_t s);
+// h = the inverse plan's output of the masked rows (bit-reversed, unscaled coefficients of P):
+// out[r][k] = (k + 1) p_{k+1} / n, natural order, ready for the forward plan; *flag = 1 if a
+// coefficient p_k, k >= deg_bound (>= 1), is not zero
+hipError_t erasure_deriv(int fid, const uint32_t *h, uint32_t *out, int log_n, size_t n_rows, const uint32_t *dscale,
+                         size_t deg_bound, uint32_t *flag, hipStream_t s);
+// e = the forward plan's output of erasure_deriv's rows: v(r, j) = e[r][erased[j]] * dinv[j] to
+// vals[r][j] and (optional) cm[j][r], canonical words if canon, else Montgomery; rows (optional):
+// rows[r][erased[j]] = v in Montgomery form (completes erasure_masked_cols' plain rows)
+hipError_t erasure_fill(int fid, const uint32_t *e, int log_n, size_t n_rows, const uint32_t *erased, size_t n_erased,
+                        const uint32_t *dinv, uint32_t *vals, uint32_t *cm, uint32_t *rows, bool canon,
+                        hipStream_t s);
+// col_bad[c] = 1 (never cleared here) if column c of cols[c][r], r < n_rows, canonical words, holds
+// an element that is not < p
+hipError_t scrub_col_canon(int fid, const uint32_t *cols, size_t n_rows, size_t n_cols, uint32_t *col_bad,
+                           hipStream_t s);
+// status[c] = 2 if col_bad[c] (digest c is then zeroed), else 0 / 1: digest c equals / differs from leaf c
+hipError_t scrub_status(uint8_t *digests, const uint8_t *leaves, const uint32_t *col_bad, size_t n_cols,
+                        uint8_t *status, hipStream_t s);
+
 }  // namespace lcpc

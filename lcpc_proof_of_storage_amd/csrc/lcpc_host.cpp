@@ -3032,3 +3032,415 @@ lcpc_status lcpc_column_digests_finalize(lcpc_column_digests *a, uint8_t *digest
 }
 
 }  // extern "C"
+
+// ================================================================= R-S erasure decoding, scrub, repair
+// No counterpart in the reference (its decode_row is a plain ifft_oi and verify_all_files_agree can
+// only say "trees differ"): the redundancy of the rate <= 1/2 code is used to locate damaged columns
+// of a stored file against its Merkle leaves and to recompute them.  Kernels: erasure.hip.
+namespace {
+
+// a * b R^-1 mod p on 32-bit words (CIOS), host side: only lcpc_rs_domain_points needs it
+template <class F>
+void host_mont_mul(const uint32_t *a, const uint32_t *b, uint32_t *out) {
+  constexpr int N = F::N;
+  uint32_t t[N + 2] = {0};
+  for (int i = 0; i < N; i++) {
+    uint64_t c = 0;
+    for (int j = 0; j < N; j++) {
+      const uint64_t x = (uint64_t)a[j] * b[i] + t[j] + c;
+      t[j] = (uint32_t)x;
+      c = x >> 32;
+    }
+    uint64_t x = (uint64_t)t[N] + c;
+    t[N] = (uint32_t)x;
+    t[N + 1] = (uint32_t)(x >> 32);
+    const uint32_t m = t[0] * F::NP;
+    x = (uint64_t)m * F::P[0] + t[0];
+    c = x >> 32;
+    for (int j = 1; j < N; j++) {
+      x = (uint64_t)m * F::P[j] + t[j] + c;
+      t[j - 1] = (uint32_t)x;
+      c = x >> 32;
+    }
+    x = (uint64_t)t[N] + c;
+    t[N - 1] = (uint32_t)x;
+    t[N] = t[N + 1] + (uint32_t)(x >> 32);
+  }
+  bool ge = t[N] != 0;
+  if (!ge) {
+    ge = true;  // t == p also subtracts
+    for (int i = N - 1; i >= 0; i--)
+      if (t[i] != F::P[i]) {
+        ge = t[i] > F::P[i];
+        break;
+      }
+  }
+  if (ge) {
+    uint64_t br = 0;
+    for (int i = 0; i < N; i++) {
+      const uint64_t d = (uint64_t)t[i] - F::P[i] - br;
+      t[i] = (uint32_t)d;
+      br = (d >> 32) & 1;
+    }
+  }
+  for (int i = 0; i < N; i++) out[i] = t[i];
+}
+
+inline size_t bitrev_host(size_t i, int log_n) {
+  size_t r = 0;
+  for (int b = 0; b < log_n; b++) r |= ((i >> b) & 1) << (log_n - 1 - b);
+  return r;
+}
+
+// the erasure set as the kernels take it; the argument rules of lcpc_rs_erasure_decode_rows
+lcpc_status erasure_check(size_t len, size_t n_per_row, const uint64_t *erased, size_t n_erased,
+                          std::vector<uint32_t> &e32) {
+  if (n_per_row < 1 || n_per_row >= len) return fail(LCPC_ERR_INVALID_ARG, "n_per_row outside [1, len)");
+  if (!erased && n_erased) return fail(LCPC_ERR_INVALID_ARG, "null argument");
+  if (len > ((size_t)1 << 24)) return fail(LCPC_ERR_UNSUPPORTED, "length beyond the NTT range");
+  std::vector<bool> seen(len, false);
+  e32.resize(n_erased);
+  for (size_t i = 0; i < n_erased; i++) {
+    if (erased[i] >= len) return fail(LCPC_ERR_INVALID_ARG, "erased index out of range");
+    if (seen[erased[i]]) return fail(LCPC_ERR_INVALID_ARG, "duplicate erased index");
+    seen[erased[i]] = true;
+    e32[i] = (uint32_t)erased[i];
+  }
+  if (n_erased > len - n_per_row)
+    return fail(LCPC_ERR_UNRECOVERABLE, "more erasures than the code's redundancy (len - n_per_row)");
+  return LCPC_OK;
+}
+
+// Per-call device state of an erasure decode: both plans, the locator's tables, the check flag.
+struct ErasureCtx {
+  int fid = 0, log_n = 0;
+  size_t n = 0, n_erased = 0, deg_bound = 0;
+  hipStream_t s = nullptr;
+  NttPlan fwd, inv;
+  DBuf erased, slot, lambda, dinv, dscale, flag;
+  ~ErasureCtx() {
+    if (s) (void)hipStreamSynchronize(s);
+    ntt_plan_free(fwd);
+    ntt_plan_free(inv);
+  }
+};
+
+lcpc_status erasure_ctx_init(ErasureCtx &c, Device *dev, hipStream_t s, int fid, size_t len, size_t n_per_row,
+                             const std::vector<uint32_t> &e32) {
+  c.fid = fid;
+  c.log_n = (int)log2_np2(len);
+  c.n = len;
+  c.n_erased = e32.size();
+  c.deg_bound = n_per_row + e32.size();
+  c.s = s;
+  const int wb = field_bytes(fid);
+  for (bool inverse : {false, true}) {
+    const hipError_t he = ntt_plan_init(inverse ? c.inv : c.fwd, fid, c.log_n, inverse, s);
+    if (he == hipErrorInvalidValue) return fail(LCPC_ERR_UNSUPPORTED, "length beyond the NTT range");
+    HIP_TRY(he);
+  }
+  HIP_TRY(c.erased.alloc(dev, e32.size() * 4));
+  HIP_TRY(c.slot.alloc(dev, len * 4));
+  HIP_TRY(c.lambda.alloc(dev, len * wb));
+  HIP_TRY(c.dinv.alloc(dev, e32.size() * wb));
+  HIP_TRY(c.dscale.alloc(dev, len * wb));
+  HIP_TRY(c.flag.alloc(dev, 8));
+  HIP_TRY(hipMemsetAsync(c.flag.p, 0, 8, s));
+  if (!e32.empty()) HIP_TRY(hipMemcpyAsync(c.erased.p, e32.data(), e32.size() * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(erasure_locator(fid, c.fwd.d_tw, c.log_n, c.erased.as<uint32_t>(), c.n_erased, c.slot.as<int32_t>(),
+                          c.lambda.as<uint32_t>(), c.dinv.as<uint32_t>(), s));
+  uint32_t inv[8] = {0};
+  inv_pow2_canon(fid, c.log_n, inv);
+  HIP_TRY(erasure_dscale(fid, c.log_n, inv, c.dscale.as<uint32_t>(), s));
+  // (e32 is pageable host memory: the copy above has left it once the stream drains)
+  HIP_TRY(hipStreamSynchronize(s));
+  return LCPC_OK;
+}
+
+// g: B masked rows in the inverse plan's input order (clobbered).  On return h holds P'(x_c) in
+// codeword order (not computed when nothing is erased) and the flag has the degree check's verdict.
+lcpc_status erasure_core(ErasureCtx &c, uint32_t *g, uint32_t *h, size_t B) {
+  HIP_TRY(ntt_rows(c.inv, g, c.n, c.n, h, c.n, B, c.s));
+  HIP_TRY(erasure_deriv(c.fid, h, g, c.log_n, B, c.dscale.as<uint32_t>(), c.deg_bound, c.flag.as<uint32_t>(), c.s));
+  if (c.n_erased) HIP_TRY(ntt_rows(c.fwd, g, c.n, c.n, h, c.n, B, c.s));
+  return LCPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+lcpc_status lcpc_rs_domain_points(lcpc_field f, size_t len, uint64_t *out) {
+  if (!valid_field(f) || !out) return fail(LCPC_ERR_INVALID_ARG, "arguments");
+  lcpc_status st = check_fft_len(f, len);
+  if (st) return st;
+  const int log_n = (int)log2_np2(len);
+  dispatch_field(f, [&]<class F>() {
+    constexpr int N = F::N;
+    // the forward transform's root (ntt_plan_init): ROOT_OF_UNITY^(2^(S - log_n)), or its inverse
+    uint32_t w[N], x[N];
+    for (int i = 0; i < N; i++) w[i] = LCPC_FFT_OMEGA_INVERSE ? F::ROOT_INV[i] : F::ROOT[i];
+    for (int k = 0; k < F::S - log_n; k++) host_mont_mul<F>(w, w, w);
+    for (int i = 0; i < N; i++) x[i] = F::ONE[i];
+    uint32_t *o = reinterpret_cast<uint32_t *>(out);
+    for (size_t e = 0; e < len; e++) {  // x = w^e is the point of position bitrev(e) (or e)
+      const size_t c = LCPC_FFT_OUTPUT_BITREV ? bitrev_host(e, log_n) : e;
+      std::memcpy(o + c * N, x, sizeof(x));
+      host_mont_mul<F>(x, w, x);
+    }
+    return 0;
+  });
+  return LCPC_OK;
+}
+
+lcpc_status lcpc_rs_erasure_decode_rows(lcpc_field f, uint64_t *rows, size_t n_rows, size_t len, size_t n_per_row,
+                                        const uint64_t *erased, size_t n_erased) {
+  if (!valid_field(f) || (!rows && n_rows)) return fail(LCPC_ERR_INVALID_ARG, "arguments");
+  if (!field_gpu_supported(f)) return fail(LCPC_ERR_UNSUPPORTED, "field has no gfx950 kernels");
+  lcpc_status st = check_fft_len(f, len);
+  if (st) return st;
+  std::vector<uint32_t> e32;
+  if ((st = erasure_check(len, n_per_row, erased, n_erased, e32))) return st;
+  if (n_rows == 0) return LCPC_OK;
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  hipStream_t s = lease.s;
+  const size_t wb = (size_t)field_bytes(f), nl = wb / 8;
+  ErasureCtx c;
+  if ((st = erasure_ctx_init(c, dev, s, f, len, n_per_row, e32))) return st;
+  // 16 MiB of row elements per batch (2^21 Ft63 elements still fill the device): 64 rows at the
+  // stored files' 2^15-point shape
+  const size_t bmax = std::max<size_t>(1, std::min(n_rows, ((size_t)16 << 20) / (len * wb)));
+  DBuf a, g, h, vals;
+  HIP_TRY(a.alloc(dev, bmax * len * wb));
+  HIP_TRY(g.alloc(dev, bmax * len * wb));
+  HIP_TRY(h.alloc(dev, bmax * len * wb));
+  HIP_TRY(vals.alloc(dev, bmax * n_erased * wb));
+  // the recovered values of every row stay here until the degree check has passed for all rows
+  std::vector<uint64_t> filled(n_rows * n_erased * nl);
+  for (size_t r0 = 0; r0 < n_rows; r0 += bmax) {
+    const size_t B = std::min(bmax, n_rows - r0);
+    HIP_TRY(hipMemcpyAsync(a.p, rows + r0 * len * nl, B * len * wb, hipMemcpyHostToDevice, s));
+    HIP_TRY(erasure_masked_rows(f, a.as<uint32_t>(), g.as<uint32_t>(), c.log_n, B, c.slot.as<int32_t>(),
+                                c.lambda.as<uint32_t>(), s));
+    if ((st = erasure_core(c, g.as<uint32_t>(), h.as<uint32_t>(), B))) return st;
+    if (n_erased) {
+      HIP_TRY(erasure_fill(f, h.as<uint32_t>(), c.log_n, B, c.erased.as<uint32_t>(), n_erased, c.dinv.as<uint32_t>(),
+                           vals.as<uint32_t>(), nullptr, nullptr, false, s));
+      HIP_TRY(hipMemcpyAsync(filled.data() + r0 * n_erased * nl, vals.p, B * n_erased * wb, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  uint32_t flag = 0;
+  HIP_TRY(hipMemcpyAsync(&flag, c.flag.p, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (flag)
+    return fail(LCPC_ERR_UNRECOVERABLE, "a row is not a codeword on its surviving positions (degree check failed)");
+  // only the erased positions are written: every other limb keeps its bits
+  for (size_t r = 0; r < n_rows; r++)
+    for (size_t j = 0; j < n_erased; j++)
+      std::memcpy(rows + (r * len + e32[j]) * nl, filled.data() + (r * n_erased + j) * nl, wb);
+  return LCPC_OK;
+}
+
+lcpc_status lcpc_pos_scrub_porenc(const uint8_t *porenc, size_t enc, size_t rows_written, size_t row_capacity,
+                                  const uint8_t *leaves, uint8_t *digests, uint8_t *status, size_t *n_bad) {
+  if (enc < 2 || (enc & (enc - 1))) return fail(LCPC_ERR_INVALID_ARG, "encoded width must be a power of 2 (>= 2)");
+  if (!leaves || !status || (!porenc && rows_written)) return fail(LCPC_ERR_INVALID_ARG, "null argument");
+  if (rows_written > row_capacity) return fail(LCPC_ERR_INVALID_ARG, "rows_written > row_capacity");
+  lcpc_status st;
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  hipStream_t s = lease.s;
+  const int fid = POS_FID;
+  const size_t col_bytes = rows_written * POS_WB;
+  const size_t cpb = col_bytes ? std::max<size_t>(1, std::min(enc, POS_STAGE_BYTES / col_bytes)) : enc;
+  DBuf hashes, dleaves, dcols[2], scratch[2], dbad, dstatus;
+  HIP_TRY(hashes.alloc(dev, enc * 32));
+  HIP_TRY(dleaves.alloc(dev, enc * 32));
+  HIP_TRY(dbad.alloc(dev, enc * 4));
+  HIP_TRY(dstatus.alloc(dev, enc));
+  for (int i = 0; i < 2; i++) {
+    HIP_TRY(dcols[i].alloc(dev, cpb * col_bytes));
+    HIP_TRY(scratch[i].alloc(dev, leaf_hash_scratch_bytes(fid, rows_written, cpb)));
+  }
+  HIP_TRY(hipMemsetAsync(dbad.p, 0, enc * 4, s));
+  HIP_TRY(hipMemcpyAsync(dleaves.p, leaves, enc * 32, hipMemcpyHostToDevice, s));
+  Pinned stg[2];
+  Events ev;
+  HIP_TRY(ev.init());
+  if (col_bytes)
+    for (auto &x : stg)
+      if (!x.get(dev, cpb * col_bytes)) return fail(LCPC_ERR_OUT_OF_MEMORY, "pinned host staging");
+  int k = 0;
+  for (size_t c0 = 0; c0 < enc; c0 += cpb, k++) {
+    const size_t nc = std::min(enc, c0 + cpb) - c0;
+    const int slot = k & 1;
+    if (col_bytes) {
+      if (k >= 2) HIP_TRY(hipEventSynchronize(ev.e[slot]));  // its last upload has left it
+      parallel_for(nc, [&](size_t c) {
+        std::memcpy(stg[slot].b() + c * col_bytes, porenc + (c0 + c) * row_capacity * POS_WB, col_bytes);
+      });
+      HIP_TRY(hipMemcpyAsync(dcols[slot].p, stg[slot].p, nc * col_bytes, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipEventRecord(ev.e[slot], s));
+      // a non-canonical element is a finding of its column, not an error of the call
+      HIP_TRY(scrub_col_canon(fid, dcols[slot].as<uint32_t>(), rows_written, nc, dbad.as<uint32_t>() + c0, s));
+    }
+    // the leaves hash canonical bytes: the slice is hashed as it is, without a conversion round trip
+    HIP_TRY(leaf_hashes_cols(fid, dcols[slot].as<uint32_t>(), rows_written, nc, hashes.as<uint8_t>() + c0 * 32,
+                             scratch[slot].p, s, true));
+  }
+  HIP_TRY(scrub_status(hashes.as<uint8_t>(), dleaves.as<uint8_t>(), dbad.as<uint32_t>(), enc, dstatus.as<uint8_t>(), s));
+  HIP_TRY(hipMemcpyAsync(status, dstatus.p, enc, hipMemcpyDeviceToHost, s));
+  if (digests) HIP_TRY(hipMemcpyAsync(digests, hashes.p, enc * 32, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (n_bad) {
+    size_t n = 0;
+    for (size_t c = 0; c < enc; c++) n += status[c] != 0;
+    *n_bad = n;
+  }
+  return LCPC_OK;
+}
+
+lcpc_status lcpc_pos_repair_columns(const uint8_t *porenc, size_t pre, size_t enc, size_t rows_written,
+                                    size_t row_capacity, const uint64_t *bad_cols, size_t n_bad, uint8_t *cols_out,
+                                    uint8_t *digests_out, uint8_t *data_out) {
+  lcpc_status st = pos_dims_check(pre, enc);
+  if (st) return st;
+  if (rows_written > row_capacity) return fail(LCPC_ERR_INVALID_ARG, "rows_written > row_capacity");
+  if (!porenc && rows_written) return fail(LCPC_ERR_INVALID_ARG, "null argument");
+  std::vector<uint32_t> e32;
+  if ((st = erasure_check(enc, pre, bad_cols, n_bad, e32))) return st;
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  hipStream_t s = lease.s;
+  const int fid = POS_FID;
+  const size_t rows = rows_written;
+  ErasureCtx c;
+  if ((st = erasure_ctx_init(c, dev, s, fid, enc, pre, e32))) return st;
+  std::vector<uint8_t> is_bad(enc, 0);
+  for (uint32_t j : e32) is_bad[j] = 1;
+  // batches of whole BLAKE3 chunks of the column messages, as the writer's
+  const size_t rows_per_chunk = 1024 / POS_WB;
+  const size_t n_chunks = leaf_n_chunks(fid, rows);
+  // LCPC_POS_REPAIR_BATCH_ROWS: rows per batch instead of a staging buffer's worth (tests of the
+  // batch seams on small files, A/B runs); rounded down to whole chunks, at least one
+  size_t want_rows = std::max<size_t>(rows_per_chunk, POS_STAGE_BYTES / (enc * POS_WB));
+  if (const char *env = std::getenv("LCPC_POS_REPAIR_BATCH_ROWS")) {
+    const unsigned long long v = std::strtoull(env, nullptr, 10);
+    if (v) want_rows = std::min<size_t>(want_rows, (size_t)v);
+  }
+  const size_t cpb = std::max<size_t>(1, want_rows / rows_per_chunk);
+  const size_t bmax = std::max<size_t>(1, std::min(rows, cpb * rows_per_chunk));
+  const bool want_vals = n_bad && (cols_out || digests_out);
+  DBuf src, a, g, h, vals, cm, dcv, dbytes, dbad;
+  HIP_TRY(src.alloc(dev, bmax * enc * POS_WB));
+  HIP_TRY(g.alloc(dev, bmax * enc * POS_WB));
+  HIP_TRY(h.alloc(dev, bmax * enc * POS_WB));
+  if (data_out) {
+    HIP_TRY(a.alloc(dev, bmax * enc * POS_WB));
+    HIP_TRY(dbytes.alloc(dev, bmax * pre * POS_DB + 64));
+  }
+  HIP_TRY(vals.alloc(dev, bmax * n_bad * POS_WB));
+  HIP_TRY(cm.alloc(dev, bmax * n_bad * POS_WB));
+  HIP_TRY(dcv.alloc(dev, n_chunks * n_bad * 32));
+  HIP_TRY(dbad.alloc(dev, 8));
+  HIP_TRY(hipMemsetAsync(dbad.p, 0, 8, s));
+  Pinned stg[2], ocols, odata;
+  for (auto &x : stg)
+    if (!x.get(dev, bmax * enc * POS_WB)) return fail(LCPC_ERR_OUT_OF_MEMORY, "pinned host staging");
+  if (cols_out && n_bad && !ocols.get(dev, bmax * n_bad * POS_WB)) return fail(LCPC_ERR_OUT_OF_MEMORY, "pinned host staging");
+  if (data_out && !odata.get(dev, bmax * pre * POS_DB)) return fail(LCPC_ERR_OUT_OF_MEMORY, "pinned host staging");
+  uint32_t inv[8] = {0};
+  inv_pow2_canon(fid, c.log_n, inv);
+  auto batch_rows = [&](size_t c_lo, size_t *r0, size_t *B, size_t *c_hi) {
+    *c_hi = std::min(n_chunks, c_lo + cpb);
+    *r0 = std::min(rows, lcpc_leaf_chunk_first_row((lcpc_field)fid, c_lo));
+    const size_t r1 = *c_hi == n_chunks ? rows : std::min(rows, lcpc_leaf_chunk_first_row((lcpc_field)fid, *c_hi));
+    *B = r1 - *r0;
+  };
+  // the damaged columns are never read, neither here nor by the kernels
+  auto stage = [&](int slot, size_t r0, size_t B) {
+    if (!B) return;
+    parallel_for(enc, [&](size_t col) {
+      if (!is_bad[col])
+        std::memcpy(stg[slot].b() + col * B * POS_WB, porenc + (col * row_capacity + r0) * POS_WB, B * POS_WB);
+    });
+  };
+  size_t r0 = 0, B = 0, c_hi = 0;
+  batch_rows(0, &r0, &B, &c_hi);
+  stage(0, r0, B);
+  int k = 0;
+  for (size_t c_lo = 0; c_lo < n_chunks; c_lo = c_hi, k++) {
+    batch_rows(c_lo, &r0, &B, &c_hi);
+    const int slot = k & 1;
+    if (B) {
+      HIP_TRY(hipMemcpyAsync(src.p, stg[slot].p, enc * B * POS_WB, hipMemcpyHostToDevice, s));
+      HIP_TRY(erasure_masked_cols(fid, src.as<uint32_t>(), B, c.log_n, g.as<uint32_t>(),
+                                  data_out ? a.as<uint32_t>() : nullptr, c.slot.as<int32_t>(),
+                                  c.lambda.as<uint32_t>(), dbad.as<uint32_t>(), s));
+      if ((st = erasure_core(c, g.as<uint32_t>(), h.as<uint32_t>(), B))) return st;
+      if (n_bad && (want_vals || data_out))
+        HIP_TRY(erasure_fill(fid, h.as<uint32_t>(), c.log_n, B, c.erased.as<uint32_t>(), n_bad, c.dinv.as<uint32_t>(),
+                             vals.as<uint32_t>(), cols_out ? cm.as<uint32_t>() : nullptr,
+                             data_out ? a.as<uint32_t>() : nullptr, true, s));
+      if (cols_out && n_bad)
+        HIP_TRY(hipMemcpyAsync(ocols.p, cm.p, n_bad * B * POS_WB, hipMemcpyDeviceToHost, s));
+      if (data_out) {
+        // decode of the completed rows: ifft_oi as in lcpc_pos_decode_porenc
+        uint32_t *x = a.as<uint32_t>(), *y = g.as<uint32_t>();
+        if (LCPC_FFT_OUTPUT_BITREV) {
+          HIP_TRY(bitrev_scale(fid, x, y, c.log_n, B, nullptr, s));
+          std::swap(x, y);
+        }
+        uint32_t *z = h.as<uint32_t>();
+        HIP_TRY(ntt_rows(c.inv, x, enc, enc, z, enc, B, s));
+        HIP_TRY(bitrev_scale(fid, z, x, c.log_n, B, inv, s));
+        HIP_TRY(hipMemcpy2DAsync(z, pre * POS_WB, x, enc * POS_WB, pre * POS_WB, B, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(pos_unpack7(reinterpret_cast<const uint64_t *>(z), B * pre, dbytes.as<uint8_t>(), B * pre * POS_DB, s));
+        HIP_TRY(hipMemcpyAsync(odata.p, dbytes.p, B * pre * POS_DB, hipMemcpyDeviceToHost, s));
+      }
+    }
+    // column-digest chunks of the repaired columns' rows (the writer's chunk machinery)
+    if (digests_out && n_bad)
+      HIP_TRY(leaf_chunk_cvs(fid, vals.as<uint32_t>(), r0, rows, n_bad, n_bad, c_lo, c_hi,
+                             dcv.as<uint32_t>() + c_lo * n_bad * 8, s, true));
+    // the next batch's rows gather on the host while this one runs
+    const size_t this_r0 = r0, this_B = B;
+    if (c_hi < n_chunks) {
+      size_t nr0, nB, nchi;
+      batch_rows(c_hi, &nr0, &nB, &nchi);
+      stage((k + 1) & 1, nr0, nB);
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    if (this_B && cols_out && n_bad)
+      parallel_for(n_bad, [&](size_t j) {
+        std::memcpy(cols_out + (j * rows + this_r0) * POS_WB, ocols.b() + j * this_B * POS_WB, this_B * POS_WB);
+      });
+    if (this_B && data_out) par_memcpy(data_out + this_r0 * pre * POS_DB, odata.b(), this_B * pre * POS_DB);
+  }
+  uint32_t flags[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(&flags[0], c.flag.p, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&flags[1], dbad.p, 4, hipMemcpyDeviceToHost, s));
+  if (digests_out && n_bad) {
+    DBuf leaves;
+    HIP_TRY(leaves.alloc(dev, n_bad * 32));
+    HIP_TRY(leaves_from_cvs(dcv.as<uint32_t>(), n_bad, (int)n_chunks, leaves.as<uint8_t>(), s));
+    HIP_TRY(hipMemcpyAsync(digests_out, leaves.p, n_bad * 32, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  if (flags[1])
+    return fail(LCPC_ERR_UNRECOVERABLE, "a column not listed as damaged holds a non-canonical element");
+  if (flags[0])
+    return fail(LCPC_ERR_UNRECOVERABLE, "a row is not a codeword on the columns not listed as damaged (degree check failed)");
+  return LCPC_OK;
+}
+
+}  // extern "C"

@@ -240,6 +240,36 @@ def decode_row(row: np.ndarray, field: int = FT63) -> np.ndarray:
     return ifft_oi_rows(row, field)
 
 
+# ---------------------------------------------------------------- R-S erasure decoding
+# No counterpart in the reference (include/lcpc_mi.h, "R-S erasure decoding, scrub, repair").
+UNRECOVERABLE = 36  # LCPC_ERR_UNRECOVERABLE
+
+
+def rs_domain_points(field: int, length: int) -> np.ndarray:
+    """The evaluation points of an encoded row in codeword order, (length, limbs) Montgomery limbs:
+    position c of a codeword of f is f(points[c]).  Host only."""
+    out = np.zeros((max(length, 1), limbs(field)), np.uint64)
+    _raise(N.load().lcpc_rs_domain_points(field, length, _p64(out)))
+    return out[:length]
+
+
+def erasure_decode_rows(field: int, rows: np.ndarray, n_per_row: int, erased) -> np.ndarray:
+    """rows: (n_rows, len, limbs) or (len, limbs) codewords of messages of n_per_row coefficients
+    whose positions `erased` are unknown (never read).  Returns a copy with those positions filled
+    in; every other limb is the input's.  At most len - n_per_row erasures; with fewer, rows that
+    are no codeword on their surviving positions raise (code UNRECOVERABLE), as too many erasures
+    do.  An empty `erased` is that consistency check alone."""
+    nl = limbs(field)
+    a = np.ascontiguousarray(rows, dtype=np.uint64).copy()
+    shape = a.shape
+    length = shape[-2] if a.ndim >= 2 else a.size // nl
+    a2 = a.reshape(-1, length * nl)
+    e = np.ascontiguousarray(np.asarray(list(erased), dtype=np.uint64).reshape(-1))
+    _raise(N.load().lcpc_rs_erasure_decode_rows(field, _p64(a2), a2.shape[0], length, n_per_row,
+                                                _p64(e) if e.size else None, e.size))
+    return a2.reshape(shape)
+
+
 # ---------------------------------------------------------------- convert_file_data_to_commit
 @dataclass
 class Commit:

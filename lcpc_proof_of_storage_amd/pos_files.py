@@ -16,6 +16,10 @@ formats of the reference's proof-of-storage/src/lcpc_online (names kept):
   ColumnDigestAccumulator, ColumnsToCareAbout   column_digest_accumulator.rs:9-118
   ColumnChunkCache, the `.porcv` sidecar          no counterpart: incremental Merkle updates
                         (FileHandler(chunk_cache=True)), same trees and files as without it
+  ScrubReport, UnrecoverableError, FileHandler.scrub / repair,
+  EncodedFileReader.find_damaged_columns / repair_columns / decode_with_erasures
+                        no counterpart: damaged columns located against the stored leaves and
+                        recomputed by Reed-Solomon erasure decoding
 
 Layout of a `.porenc` file (WriteableFt63): column c occupies row_capacity * 8 bytes starting at
 byte c * row_capacity * 8; its first rows_written elements are the canonical little-endian repr
@@ -54,6 +58,32 @@ def _u8(a: np.ndarray):
 def _bytes_ptr(b) -> Tuple[Optional[C.POINTER(C.c_uint8)], object]:
     arr = np.frombuffer(b, dtype=np.uint8) if len(b) else np.zeros(0, np.uint8)
     return _u8(arr), arr
+
+
+# ---------------------------------------------------------------- scrub / repair results
+LCPC_ERR_UNRECOVERABLE = 36
+
+
+class UnrecoverableError(Exception):
+    """More columns are damaged than the code's redundancy covers (or what was recomputed does not
+    verify against the trust anchor), and no other copy helps.  FileHandler.repair leaves every
+    file as it was when it raises this."""
+
+
+@dataclass
+class ScrubReport:
+    """What FileHandler.scrub found (repair returns the same for the state it met, with
+    repaired_from saying what it then did)."""
+    bad_columns: List[int]            # `.porenc` columns whose digest differs from their stored leaf
+    noncanonical_columns: List[int]   # those among them that hold an element that is not < p
+    tree_consistent: bool             # the stored tree's leaves refold to its parents and root
+    root_ok: Optional[bool]           # stored root == expected_root (None: no expected_root given)
+    raw_ok: bool                      # the raw file re-encodes to the stored tree
+    repaired_from: Optional[str] = None  # repair: "+"-joined of "columns", "tree", "reencode", "raw"
+
+    @property
+    def clean(self) -> bool:
+        return not self.bad_columns and self.tree_consistent and self.root_ok is not False and self.raw_ok
 
 
 # ---------------------------------------------------------------- metadata / Merkle tree
@@ -795,6 +825,62 @@ class EncodedFileReader:
             _u8(a), w, self.rows_written, self.row_capacity, _u8(tree))))
         return MerkleTree(tree)
 
+    # -- scrub and repair (no counterpart in the reference: include/lcpc_mi.h, "R-S erasure decoding")
+    def _scrub(self, leaves: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """(status, digests): status[c] = 0 the column's digest equals leaves[c], 1 it differs, 2 the
+        column holds a non-canonical element (its digest is then zeros)."""
+        w = self.encoded_size
+        lv = np.ascontiguousarray(leaves, dtype=np.uint8).reshape(-1)
+        if lv.size != w * DIGEST_BYTES:
+            raise ValueError("one 32-byte leaf per encoded column is needed")
+        status = np.zeros(w, np.uint8)
+        digests = np.zeros((w, DIGEST_BYTES), np.uint8)
+        n_bad = C.c_size_t()
+        self._with_map(lambda a: _raise(N.load().lcpc_pos_scrub_porenc(
+            _u8(a), w, self.rows_written, self.row_capacity, _u8(lv), _u8(digests), _u8(status), C.byref(n_bad))))
+        return status, digests
+
+    def find_damaged_columns(self, tree: MerkleTree) -> Tuple[List[int], List[int]]:
+        """(bad, noncanonical): the columns whose digest differs from their leaf of `tree` (those
+        that hold a non-canonical element included), and the non-canonical ones among them.  Rows
+        past rows_written are not looked at."""
+        status, _ = self._scrub(tree.digests[:self.encoded_size])
+        return [int(c) for c in np.flatnonzero(status)], [int(c) for c in np.flatnonzero(status == 2)]
+
+    def _repair(self, columns, want_cols: bool, want_digests: bool, want_data: bool):
+        cols_idx = np.ascontiguousarray(np.asarray(list(columns), dtype=np.uint64).reshape(-1))
+        k, rows = cols_idx.size, self.rows_written
+        cols = np.zeros((k, rows), "<u8") if want_cols else None
+        digests = np.zeros((k, DIGEST_BYTES), np.uint8) if want_digests else None
+        data = np.zeros(rows * self.pre_encoded_size * DATA_BYTE_CAPACITY, np.uint8) if want_data else None
+
+        def ptr(a):
+            return a.ctypes.data_as(N.u8p) if a is not None and a.size else None
+
+        def run(a):
+            code = N.load().lcpc_pos_repair_columns(
+                _u8(a), self.pre_encoded_size, self.encoded_size, rows, self.row_capacity,
+                cols_idx.ctypes.data_as(N.u64p) if k else None, k, ptr(cols), ptr(digests), ptr(data))
+            if code == LCPC_ERR_UNRECOVERABLE:
+                raise UnrecoverableError(N.last_error())
+            _raise(code)
+        self._with_map(run)
+        return cols, digests, data
+
+    def repair_columns(self, columns) -> Tuple[np.ndarray, np.ndarray]:
+        """The listed columns recomputed from all the others (which alone are read): (cols, digests),
+        cols[k] = the rows_written canonical u64 values of column columns[k] as they belong in the
+        file, digests[k] its 32-byte column digest.  At most encoded_size - pre_encoded_size columns;
+        UnrecoverableError beyond that, or when the other columns do not form codewords.  The file
+        is not written."""
+        cols, digests, _ = self._repair(columns, True, True, False)
+        return cols, digests
+
+    def decode_with_erasures(self, columns) -> bytes:
+        """decode_to_target_file's bytes (rows_written * pre_encoded_size * 7) without reading the
+        listed columns: the recovery path for a download from a damaged replica."""
+        return self._repair(columns, False, False, True)[2].tobytes()
+
     def set_new_capacity(self, new_row_capacity: int) -> None:
         if new_row_capacity < self.rows_written:
             raise ValueError("Cannot set capacity to fewer than rows are written.")
@@ -1203,6 +1289,134 @@ class FileHandler:
     def recalculate_tree_only(self) -> MerkleTree:
         with open(self.encoded_file_handle, "rb") as f:
             return self._reader(f).process_file_to_merkle_tree()
+
+    # -- scrub and repair (no counterpart in the reference, whose verify_all_files_agree can only
+    # say that the trees differ): the damaged `.porenc` columns are located against the stored
+    # leaves and recomputed from the code's own redundancy
+    def _stored_tree(self) -> MerkleTree:
+        """The `.portree` as it is on disk now (damage may be newer than this handler)."""
+        with open(self.merkle_tree_file_handle, "rb") as f:
+            data = f.read()
+        want = (2 * self.encoded_size - 1) * DIGEST_BYTES
+        if len(data) != want:
+            raise UnrecoverableError("the stored tree file has the wrong length")
+        return MerkleTree(np.frombuffer(data, np.uint8).copy())
+
+    def _raw_file_tree(self) -> Optional[MerkleTree]:
+        """The tree of a fresh encode of the raw file (a digest-only writer: no image is kept);
+        None if the raw file is missing or does not hold total_data_bytes."""
+        try:
+            if os.path.getsize(self.unencoded_file_handle) != self.total_data_bytes:
+                return None
+            data = np.fromfile(self.unencoded_file_handle, np.uint8)
+        except OSError:
+            return None
+        lib, h = N.load(), N.vp()
+        _raise(lib.lcpc_pos_writer_new(self.pre_encoded_size, self.encoded_size, None, 0, 0, C.byref(h)))
+        try:
+            _raise(lib.lcpc_pos_writer_push_bytes(h, _u8(data), data.size))
+            tree = np.zeros((2 * self.encoded_size - 1, DIGEST_BYTES), np.uint8)
+            rows, nbytes = C.c_size_t(), C.c_size_t()
+            _raise(lib.lcpc_pos_writer_finalize(h, None, _u8(tree), C.byref(rows), C.byref(nbytes)))
+        finally:
+            lib.lcpc_pos_writer_free(h)
+        return MerkleTree(tree)
+
+    def _scrub_state(self, expected_root: Optional[bytes]):
+        tree = self._stored_tree()
+        w = self.encoded_size
+        consistent = MerkleTree.new(tree.digests[:w]) == tree
+        with open(self.encoded_file_handle, "rb") as f:
+            status, digests = self._reader(f)._scrub(tree.digests[:w])
+        raw_tree = self._raw_file_tree()
+        report = ScrubReport(
+            bad_columns=[int(c) for c in np.flatnonzero(status)],
+            noncanonical_columns=[int(c) for c in np.flatnonzero(status == 2)],
+            tree_consistent=bool(consistent),
+            root_ok=None if expected_root is None else tree.root() == bytes(expected_root),
+            raw_ok=raw_tree is not None and raw_tree == tree)
+        return report, tree, digests, raw_tree
+
+    def scrub(self, expected_root: Optional[bytes] = None) -> ScrubReport:
+        """Read-only health check of the four files against each other (and against expected_root,
+        the root the client holds, if given): which `.porenc` columns differ from their stored
+        leaves, whether the stored tree refolds, whether the raw file still encodes to it."""
+        return self._scrub_state(expected_root)[0]
+
+    def repair(self, expected_root: Optional[bytes] = None) -> ScrubReport:
+        """Mend what scrub finds.  Everything written is first verified against the trust anchor:
+        expected_root if given, otherwise the stored tree's root provided the stored tree is
+        self-consistent.  Up to encoded_size - pre_encoded_size damaged columns are recomputed from
+        the others (erasure decoding); they -- and a tree rebuilt from the column digests, where the
+        stored one was what was damaged -- are written only if the resulting root is the anchor.
+        With more damage the raw file is encoded again, accepted only if its root is the anchor.  A
+        sound `.porenc` rewrites a damaged raw file from its decode.  UnrecoverableError if nothing
+        verifies; every file is then byte for byte what it was."""
+        report, tree, digests, raw_tree = self._scrub_state(expected_root)
+        w, pre = self.encoded_size, self.pre_encoded_size
+        if expected_root is not None:
+            anchor = bytes(expected_root)
+        elif report.tree_consistent:
+            anchor = tree.root()
+        else:
+            raise UnrecoverableError("the stored tree is not self-consistent and no expected_root was given")
+        done: List[str] = []
+        bad = report.bad_columns
+        new_tree, cols = None, None
+        if len(bad) <= w - pre:
+            try:
+                if bad:
+                    with open(self.encoded_file_handle, "rb") as f:
+                        cols, rdig = self._reader(f).repair_columns(bad)
+                    digests = digests.copy()
+                    digests[bad] = rdig
+                # a repaired column whose digest is not its leaf is a damaged leaf (or damage this
+                # cannot mend): either way only a tree over the digests that folds to the anchor counts
+                cand = tree if (report.tree_consistent and np.array_equal(digests, tree.digests[:w])) \
+                    else MerkleTree.new(digests)
+                if cand.root() == anchor:
+                    new_tree = cand
+            except UnrecoverableError:
+                new_tree = None
+        if new_tree is not None:
+            if bad:  # (a column whose leaf was what was damaged repairs to itself: nothing to write)
+                wb, wrote = WRITTEN_BYTES_WIDTH, False
+                with open(self.encoded_file_handle, "r+b") as f:
+                    for k, c in enumerate(bad):
+                        new = cols[k].tobytes()
+                        f.seek(c * self.row_capacity * wb)
+                        if f.read(len(new)) != new:
+                            f.seek(c * self.row_capacity * wb)
+                            f.write(new)
+                            wrote = True
+                    f.flush()
+                if wrote:
+                    done.append("columns")
+            if new_tree != tree:
+                self.write_tree(new_tree)
+                done.append("tree")
+            self.merkle_tree = new_tree
+            if raw_tree is None or raw_tree != new_tree:  # the encoded file is sound, the raw one is not
+                with open(self.encoded_file_handle, "rb") as f:
+                    data = self._reader(f)._decode(0, self.rows_written) if self.rows_written else b""
+                with open(self.unencoded_file_handle, "wb") as f:
+                    f.write(data[:self.total_data_bytes])
+                done.append("raw")
+        elif raw_tree is not None and raw_tree.root() == anchor:
+            self.reencode_unencoded_file()  # (rebuilds the chunk-CV cache itself)
+            done = ["reencode"]
+        else:
+            raise UnrecoverableError(
+                f"{len(bad)} damaged columns (at most {w - pre} can be recomputed) and the raw file "
+                "does not encode to the trusted root")
+        if self.chunk_cache is not None and done and done != ["reencode"]:
+            cache = self._rebuild_chunk_cache()
+            write_chunk_cv_sidecar(self.chunk_cv_file_handle, w, self.rows_written, cache.tree().root(),
+                                   cache.copy_cvs())
+            self.chunk_cache.close()
+            self.chunk_cache = cache
+        report.repaired_from = "+".join(done) if done else None
+        return report
 
     def delete_all_files(self) -> None:
         """:678-694"""
