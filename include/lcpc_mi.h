@@ -31,7 +31,9 @@ extern "C" {
 #endif
 
 /* 2: the PoS column chunk-CV cache (lcpc_pos_chunk_cache_*); 3: R-S erasure decoding, scrub and
- * repair of stored files (lcpc_rs_*, lcpc_pos_scrub_porenc, lcpc_pos_repair_columns) */
+ * repair of stored files (lcpc_rs_*, lcpc_pos_scrub_porenc, lcpc_pos_repair_columns).  The R-S
+ * error location block (lcpc_rs_locate_*, lcpc_rs_decode_rows, lcpc_pos_locate_porenc) is additive
+ * within version 3: new symbols only, nothing existing changed. */
 #define LCPC_ABI_VERSION 3
 
 typedef enum lcpc_status {
@@ -768,6 +770,54 @@ lcpc_status lcpc_pos_scrub_porenc(const uint8_t *porenc, size_t enc, size_t rows
 lcpc_status lcpc_pos_repair_columns(const uint8_t *porenc, size_t pre, size_t enc, size_t rows_written,
                                     size_t row_capacity, const uint64_t *bad_cols, size_t n_bad,
                                     uint8_t *cols_out, uint8_t *digests_out, uint8_t *data_out);
+
+/* ------------------------------------------------------------------ R-S error location by syndromes
+ * NO COUNTERPART IN THE REFERENCE.  Additive within LCPC_ABI_VERSION 3.  The erasure decoder above
+ * must be told which positions are damaged; these entry points find them from the row alone.  With
+ * the known erasures masked as above, the coefficients of P at index k' = n_per_row + n_erased and
+ * above -- the ones the degree check tests for zero -- are the power sums S_i = sum_{c wrong}
+ * a_c x_c^-i, i < N = len - k'.  Inversion-free Berlekamp-Massey finds their shortest recurrence;
+ * its connection polynomial C(z) = prod (1 - z / x_c) has the evaluation points of the wrong
+ * positions as its roots, so one forward transform of C's zero-padded coefficients has its zeros
+ * exactly there.  Unique whenever 2 t <= N for t wrong positions.  The evaluation points are the
+ * forward plan's table under lcpc_fft_convention.h, as for the erasure decoder. */
+/* The largest number of wrong positions per row that can be located for field f (the
+ * Berlekamp-Massey kernel keeps its polynomials in LDS); at least 256 for every field.  Host only. */
+size_t lcpc_rs_locate_max_errors(lcpc_field f);
+
+/* rows as lcpc_rs_erasure_decode_rows (host, row-major, Montgomery; erased positions never read).
+ * row_status[r] = 0: the surviving positions are those of a codeword; 1: located; 2: not locatable
+ * (more than (len - n_per_row - n_erased)/2 wrong positions, or more than the cap).
+ * row_n_errors (n_rows, may be NULL), err_mask (n_rows x len bytes, may be NULL: 1 at the located
+ * positions of status-1 rows), col_any (len bytes, may be NULL: OR over status-1 rows).
+ * A status-2 row is a finding: the call returns LCPC_OK.  Argument errors as the erasure decoder;
+ * n_erased > len - n_per_row: LCPC_ERR_UNRECOVERABLE.  n_erased == len - n_per_row leaves no
+ * syndromes: every row is status 0.  Nothing in rows is written. */
+lcpc_status lcpc_rs_locate_errors_rows(lcpc_field f, const uint64_t *rows, size_t n_rows, size_t len,
+                                       size_t n_per_row, const uint64_t *erased, size_t n_erased,
+                                       uint8_t *row_status, uint32_t *row_n_errors, uint8_t *err_mask,
+                                       uint8_t *col_any);
+
+/* Errors-and-erasures correction in place: the located and the erased positions of every row get
+ * fully reduced Montgomery values, every other limb keeps its bits.  Any status-2 row:
+ * LCPC_ERR_UNRECOVERABLE, no row written, row_status (may be NULL) still filled.  The values come
+ * from the erasure decoder with the known and the located positions as the erasure set; consecutive
+ * rows share one set while its size fits len - n_per_row. */
+lcpc_status lcpc_rs_decode_rows(lcpc_field f, uint64_t *rows, size_t n_rows, size_t len,
+                                size_t n_per_row, const uint64_t *erased, size_t n_erased,
+                                uint8_t *row_status);
+
+/* A `.porenc` image: col_status[c] = 0 nothing found, 1 a wrong element located in at least one row,
+ * 2 holds an element that is not < p (treated as an erasure while the rest is located), 3 listed
+ * in known_bad (never read).  *n_bad_cols = the number of non-zero status bytes, *n_dirty_rows = the
+ * rows that are not codewords on the columns read, *n_unlocatable_rows those among them whose wrong
+ * elements could not be located (their columns are NOT in col_status): > 0 is a finding (LCPC_OK).
+ * Known plus non-canonical columns > enc - pre: LCPC_ERR_UNRECOVERABLE.  Row batches as
+ * lcpc_pos_repair_columns (LCPC_POS_REPAIR_BATCH_ROWS).  The counters may be NULL. */
+lcpc_status lcpc_pos_locate_porenc(const uint8_t *porenc, size_t pre, size_t enc, size_t rows_written,
+                                   size_t row_capacity, const uint64_t *known_bad, size_t n_known,
+                                   uint8_t *col_status, size_t *n_bad_cols, size_t *n_dirty_rows,
+                                   size_t *n_unlocatable_rows);
 
 /* ------------------------------------------------------------------ diagnostics
  * On-device check of the stream-ordered buffer pool the commit / prove / shard paths share

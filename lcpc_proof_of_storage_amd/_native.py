@@ -207,6 +207,10 @@ SIGNATURES = {
     "lcpc_rs_erasure_decode_rows": (i32, [i32, u64p, sz, sz, sz, u64p, sz]),
     "lcpc_pos_scrub_porenc": (i32, [u8p, sz, sz, sz, u8p, u8p, u8p, szp]),
     "lcpc_pos_repair_columns": (i32, [u8p, sz, sz, sz, sz, u64p, sz, u8p, u8p, u8p]),
+    "lcpc_rs_locate_max_errors": (sz, [i32]),
+    "lcpc_rs_locate_errors_rows": (i32, [i32, u64p, sz, sz, sz, u64p, sz, u8p, u32p, u8p, u8p]),
+    "lcpc_rs_decode_rows": (i32, [i32, u64p, sz, sz, sz, u64p, sz, u8p]),
+    "lcpc_pos_locate_porenc": (i32, [u8p, sz, sz, sz, sz, u64p, sz, u8p, szp, szp, szp]),
     "lcpc_challenge_tensor": (i32, [vp, i32, sz, u64p]),
     "lcpc_transcript_append_field_elems": (i32, [vp, u8p, sz, i32, u64p, sz]),
     "lcpc_challenge_columns": (i32, [vp, sz, sz, u64p]),

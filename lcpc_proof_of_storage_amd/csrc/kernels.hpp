@@ -206,4 +206,29 @@ hipError_t scrub_col_canon(int fid, const uint32_t *cols, size_t n_rows, size_t 
 hipError_t scrub_status(uint8_t *digests, const uint8_t *leaves, const uint32_t *col_bad, size_t n_cols,
                         uint8_t *status, hipStream_t s);
 
+// ------------------------------------------------------------------ R-S error location (rs_locate.hip)
+// h = the inverse plan's output of masked rows (as erasure_deriv takes it), deg_bound = n_per_row +
+// n_erased, n_synd = n - deg_bound syndromes per row.
+// the largest recurrence length Berlekamp-Massey keeps in LDS for field fid (>= 256)
+size_t rs_locate_cap(int fid);
+// row_flag[r] = 1 (never cleared here) if a coefficient at index >= deg_bound of row r is not zero
+hipError_t rs_locate_scan(int fid, const uint32_t *h, int log_n, size_t n_rows, size_t deg_bound, uint8_t *row_flag,
+                          hipStream_t s);
+// synd[d][i] = coefficient deg_bound + i of row dirty[d], natural order, fully reduced
+hipError_t rs_locate_gather(int fid, const uint32_t *h, int log_n, const uint32_t *dirty, size_t n_dirty,
+                            size_t deg_bound, size_t n_synd, uint32_t *synd, hipStream_t s);
+// coef[d][0..n) = the connection polynomial of synd[d] zero-padded (natural order, the forward plan's
+// input), bm_len[d] = its degree L; >= 0xfffffffe and zeros when L would pass min(cap, n_synd / 2)
+hipError_t rs_locate_bm(int fid, const uint32_t *synd, size_t n_dirty, size_t n_synd, int log_n, uint32_t *coef,
+                        uint32_t *bm_len, hipStream_t s);
+// e = the forward plan's output of coef: mask[d][c] = 1 where e[d][c] is zero, n_zero[d] their number,
+// on_erased[d] = 1 if one of them is an erased position (slot[c] >= 0)
+hipError_t rs_locate_zeros(int fid, const uint32_t *e, int log_n, size_t n_dirty, const int32_t *slot, uint8_t *mask,
+                           uint32_t *n_zero, uint32_t *on_erased, hipStream_t s);
+// dstatus[d] = row_status[dirty[d]] = 1 (located: bm_len[d] zeros, none erased) or 2; row_n_errors[dirty[d]]
+// = the number of located positions; mask rows of status 2 are cleared, the others ORed into col_any[c]
+hipError_t rs_locate_finish(const uint32_t *dirty, size_t n_dirty, int log_n, const uint32_t *bm_len,
+                            const uint32_t *n_zero, const uint32_t *on_erased, uint8_t *dstatus, uint8_t *mask,
+                            uint8_t *row_status, uint32_t *row_n_errors, uint8_t *col_any, hipStream_t s);
+
 }  // namespace lcpc

@@ -3166,6 +3166,45 @@ lcpc_status erasure_core(ErasureCtx &c, uint32_t *g, uint32_t *h, size_t B) {
   return LCPC_OK;
 }
 
+// The values of the erased positions e32 of every row (filled[r][j], Montgomery), rows untouched;
+// LCPC_ERR_UNRECOVERABLE if a row fails the degree check.
+lcpc_status erasure_decode_values(Device *dev, hipStream_t s, int f, const uint64_t *rows, size_t n_rows, size_t len,
+                                  size_t n_per_row, const std::vector<uint32_t> &e32, std::vector<uint64_t> &filled) {
+  lcpc_status st;
+  const size_t n_erased = e32.size();
+  const size_t wb = (size_t)field_bytes(f), nl = wb / 8;
+  ErasureCtx c;
+  if ((st = erasure_ctx_init(c, dev, s, f, len, n_per_row, e32))) return st;
+  // 16 MiB of row elements per batch (2^21 Ft63 elements still fill the device): 64 rows at the
+  // stored files' 2^15-point shape
+  const size_t bmax = std::max<size_t>(1, std::min(n_rows, ((size_t)16 << 20) / (len * wb)));
+  DBuf a, g, h, vals;
+  HIP_TRY(a.alloc(dev, bmax * len * wb));
+  HIP_TRY(g.alloc(dev, bmax * len * wb));
+  HIP_TRY(h.alloc(dev, bmax * len * wb));
+  HIP_TRY(vals.alloc(dev, bmax * n_erased * wb));
+  filled.assign(n_rows * n_erased * nl, 0);
+  for (size_t r0 = 0; r0 < n_rows; r0 += bmax) {
+    const size_t B = std::min(bmax, n_rows - r0);
+    HIP_TRY(hipMemcpyAsync(a.p, rows + r0 * len * nl, B * len * wb, hipMemcpyHostToDevice, s));
+    HIP_TRY(erasure_masked_rows(f, a.as<uint32_t>(), g.as<uint32_t>(), c.log_n, B, c.slot.as<int32_t>(),
+                                c.lambda.as<uint32_t>(), s));
+    if ((st = erasure_core(c, g.as<uint32_t>(), h.as<uint32_t>(), B))) return st;
+    if (n_erased) {
+      HIP_TRY(erasure_fill(f, h.as<uint32_t>(), c.log_n, B, c.erased.as<uint32_t>(), n_erased, c.dinv.as<uint32_t>(),
+                           vals.as<uint32_t>(), nullptr, nullptr, false, s));
+      HIP_TRY(hipMemcpyAsync(filled.data() + r0 * n_erased * nl, vals.p, B * n_erased * wb, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  uint32_t flag = 0;
+  HIP_TRY(hipMemcpyAsync(&flag, c.flag.p, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (flag)
+    return fail(LCPC_ERR_UNRECOVERABLE, "a row is not a codeword on its surviving positions (degree check failed)");
+  return LCPC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3206,38 +3245,10 @@ lcpc_status lcpc_rs_erasure_decode_rows(lcpc_field f, uint64_t *rows, size_t n_r
   if (!dev) return st;
   Lease lease(dev);
   HIP_TRY(hipSetDevice(dev->id));
-  hipStream_t s = lease.s;
   const size_t wb = (size_t)field_bytes(f), nl = wb / 8;
-  ErasureCtx c;
-  if ((st = erasure_ctx_init(c, dev, s, f, len, n_per_row, e32))) return st;
-  // 16 MiB of row elements per batch (2^21 Ft63 elements still fill the device): 64 rows at the
-  // stored files' 2^15-point shape
-  const size_t bmax = std::max<size_t>(1, std::min(n_rows, ((size_t)16 << 20) / (len * wb)));
-  DBuf a, g, h, vals;
-  HIP_TRY(a.alloc(dev, bmax * len * wb));
-  HIP_TRY(g.alloc(dev, bmax * len * wb));
-  HIP_TRY(h.alloc(dev, bmax * len * wb));
-  HIP_TRY(vals.alloc(dev, bmax * n_erased * wb));
   // the recovered values of every row stay here until the degree check has passed for all rows
-  std::vector<uint64_t> filled(n_rows * n_erased * nl);
-  for (size_t r0 = 0; r0 < n_rows; r0 += bmax) {
-    const size_t B = std::min(bmax, n_rows - r0);
-    HIP_TRY(hipMemcpyAsync(a.p, rows + r0 * len * nl, B * len * wb, hipMemcpyHostToDevice, s));
-    HIP_TRY(erasure_masked_rows(f, a.as<uint32_t>(), g.as<uint32_t>(), c.log_n, B, c.slot.as<int32_t>(),
-                                c.lambda.as<uint32_t>(), s));
-    if ((st = erasure_core(c, g.as<uint32_t>(), h.as<uint32_t>(), B))) return st;
-    if (n_erased) {
-      HIP_TRY(erasure_fill(f, h.as<uint32_t>(), c.log_n, B, c.erased.as<uint32_t>(), n_erased, c.dinv.as<uint32_t>(),
-                           vals.as<uint32_t>(), nullptr, nullptr, false, s));
-      HIP_TRY(hipMemcpyAsync(filled.data() + r0 * n_erased * nl, vals.p, B * n_erased * wb, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-  }
-  uint32_t flag = 0;
-  HIP_TRY(hipMemcpyAsync(&flag, c.flag.p, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (flag)
-    return fail(LCPC_ERR_UNRECOVERABLE, "a row is not a codeword on its surviving positions (degree check failed)");
+  std::vector<uint64_t> filled;
+  if ((st = erasure_decode_values(dev, lease.s, f, rows, n_rows, len, n_per_row, e32, filled))) return st;
   // only the erased positions are written: every other limb keeps its bits
   for (size_t r = 0; r < n_rows; r++)
     for (size_t j = 0; j < n_erased; j++)
@@ -3440,6 +3451,394 @@ lcpc_status lcpc_pos_repair_columns(const uint8_t *porenc, size_t pre, size_t en
     return fail(LCPC_ERR_UNRECOVERABLE, "a column not listed as damaged holds a non-canonical element");
   if (flags[0])
     return fail(LCPC_ERR_UNRECOVERABLE, "a row is not a codeword on the columns not listed as damaged (degree check failed)");
+  return LCPC_OK;
+}
+
+}  // extern "C"
+
+// ================================================================= R-S error location by syndromes
+// No counterpart in the reference.  The erasure decoder above needs to be told where the damage is;
+// here the rows say it themselves: the coefficients its degree check tests for zero are power sums
+// of the wrong positions, Berlekamp-Massey finds their shortest recurrence and one forward
+// transform of its connection polynomial has its zeros at the wrong positions.  Kernels: rs_locate.hip.
+namespace {
+
+// Per-call device state of the locator, for batches of at most bmax rows.
+struct LocateCtx {
+  size_t bmax = 0, n_synd = 0;
+  DBuf flag, dirty, bm_len, n_zero, on_erased, dstatus, mask, status, nerr, col_any, coef;
+  std::vector<uint8_t> hflag;
+  std::vector<uint32_t> hdirty;  // the batch's rows with a non-zero syndrome, ascending
+};
+
+lcpc_status locate_ctx_init(LocateCtx &lc, const ErasureCtx &c, Device *dev, size_t bmax) {
+  lc.bmax = bmax;
+  lc.n_synd = c.n - c.deg_bound;
+  const size_t wb = (size_t)field_bytes(c.fid);
+  HIP_TRY(lc.flag.alloc(dev, bmax));
+  HIP_TRY(lc.dirty.alloc(dev, bmax * 4));
+  HIP_TRY(lc.bm_len.alloc(dev, bmax * 4));
+  HIP_TRY(lc.n_zero.alloc(dev, bmax * 4));
+  HIP_TRY(lc.on_erased.alloc(dev, bmax * 4));
+  HIP_TRY(lc.dstatus.alloc(dev, bmax));
+  HIP_TRY(lc.status.alloc(dev, bmax));
+  HIP_TRY(lc.nerr.alloc(dev, bmax * 4));
+  HIP_TRY(lc.col_any.alloc(dev, c.n));
+  HIP_TRY(hipMemsetAsync(lc.col_any.p, 0, c.n, c.s));
+  if (lc.n_synd) {
+    HIP_TRY(lc.mask.alloc(dev, bmax * c.n));
+    HIP_TRY(lc.coef.alloc(dev, bmax * c.n * wb));
+  }
+  lc.hflag.assign(bmax, 0);
+  return LCPC_OK;
+}
+
+// g: B masked rows in the inverse plan's input order; h: B rows of room.  Queues the inverse
+// transform, the syndrome scan and the copy of the row flags to lc.hflag; the caller drains the
+// stream before locate_dirty.
+lcpc_status locate_scan(ErasureCtx &c, LocateCtx &lc, uint32_t *g, uint32_t *h, size_t B) {
+  HIP_TRY(hipMemsetAsync(lc.status.p, 0, B, c.s));
+  HIP_TRY(hipMemsetAsync(lc.nerr.p, 0, B * 4, c.s));
+  if (!lc.n_synd) return LCPC_OK;
+  HIP_TRY(hipMemsetAsync(lc.flag.p, 0, B, c.s));
+  HIP_TRY(ntt_rows(c.inv, g, c.n, c.n, h, c.n, B, c.s));
+  HIP_TRY(rs_locate_scan(c.fid, h, c.log_n, B, c.deg_bound, lc.flag.as<uint8_t>(), c.s));
+  HIP_TRY(hipMemcpyAsync(lc.hflag.data(), lc.flag.p, B, hipMemcpyDeviceToHost, c.s));
+  return LCPC_OK;
+}
+
+// After locate_scan and a drained stream: the flagged rows go through gather, Berlekamp-Massey, the
+// root transform and the zero scan (g and h are clobbered).  On return the stream is drained,
+// lc.hdirty lists the flagged rows, lc.status / lc.nerr hold the batch's verdicts, lc.mask[d] the
+// located positions of row lc.hdirty[d], and lc.col_any has accumulated them.
+lcpc_status locate_dirty(ErasureCtx &c, LocateCtx &lc, uint32_t *g, uint32_t *h, size_t B) {
+  lc.hdirty.clear();
+  if (!lc.n_synd) return LCPC_OK;
+  for (size_t r = 0; r < B; r++)
+    if (lc.hflag[r]) lc.hdirty.push_back((uint32_t)r);
+  const size_t nd = lc.hdirty.size();
+  if (!nd) return LCPC_OK;  // codewords: nothing more to pay
+  HIP_TRY(hipMemcpyAsync(lc.dirty.p, lc.hdirty.data(), nd * 4, hipMemcpyHostToDevice, c.s));
+  HIP_TRY(rs_locate_gather(c.fid, h, c.log_n, lc.dirty.as<uint32_t>(), nd, c.deg_bound, lc.n_synd, g, c.s));
+  HIP_TRY(rs_locate_bm(c.fid, g, nd, lc.n_synd, c.log_n, lc.coef.as<uint32_t>(), lc.bm_len.as<uint32_t>(), c.s));
+  {
+    prof::Scope ps("rs_locate_root_ntt", c.s);
+    HIP_TRY(ntt_rows(c.fwd, lc.coef.as<uint32_t>(), c.n, c.n, h, c.n, nd, c.s));
+  }
+  HIP_TRY(rs_locate_zeros(c.fid, h, c.log_n, nd, c.slot.as<int32_t>(), lc.mask.as<uint8_t>(),
+                          lc.n_zero.as<uint32_t>(), lc.on_erased.as<uint32_t>(), c.s));
+  HIP_TRY(rs_locate_finish(lc.dirty.as<uint32_t>(), nd, c.log_n, lc.bm_len.as<uint32_t>(), lc.n_zero.as<uint32_t>(),
+                           lc.on_erased.as<uint32_t>(), lc.dstatus.as<uint8_t>(), lc.mask.as<uint8_t>(),
+                           lc.status.as<uint8_t>(), lc.nerr.as<uint32_t>(), lc.col_any.as<uint8_t>(), c.s));
+  HIP_TRY(hipStreamSynchronize(c.s));
+  return LCPC_OK;
+}
+
+// lcpc_rs_locate_errors_rows after its argument checks; every output may be null
+lcpc_status locate_rows(Device *dev, hipStream_t s, int f, const uint64_t *rows, size_t n_rows, size_t len,
+                        size_t n_per_row, const std::vector<uint32_t> &e32, uint8_t *row_status,
+                        uint32_t *row_n_errors, uint8_t *err_mask, uint8_t *col_any) {
+  lcpc_status st;
+  const size_t wb = (size_t)field_bytes(f), nl = wb / 8;
+  ErasureCtx c;
+  if ((st = erasure_ctx_init(c, dev, s, f, len, n_per_row, e32))) return st;
+  const size_t bmax = std::max<size_t>(1, std::min(n_rows, ((size_t)16 << 20) / (len * wb)));
+  LocateCtx lc;
+  if ((st = locate_ctx_init(lc, c, dev, bmax))) return st;
+  DBuf a, g, h;
+  HIP_TRY(a.alloc(dev, bmax * len * wb));
+  HIP_TRY(g.alloc(dev, bmax * len * wb));
+  HIP_TRY(h.alloc(dev, bmax * len * wb));
+  std::vector<uint8_t> hmask;
+  for (size_t r0 = 0; r0 < n_rows; r0 += bmax) {
+    const size_t B = std::min(bmax, n_rows - r0);
+    HIP_TRY(hipMemcpyAsync(a.p, rows + r0 * len * nl, B * len * wb, hipMemcpyHostToDevice, s));
+    HIP_TRY(erasure_masked_rows(f, a.as<uint32_t>(), g.as<uint32_t>(), c.log_n, B, c.slot.as<int32_t>(),
+                                c.lambda.as<uint32_t>(), s));
+    if ((st = locate_scan(c, lc, g.as<uint32_t>(), h.as<uint32_t>(), B))) return st;
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((st = locate_dirty(c, lc, g.as<uint32_t>(), h.as<uint32_t>(), B))) return st;
+    const size_t nd = lc.hdirty.size();
+    if (row_status) HIP_TRY(hipMemcpyAsync(row_status + r0, lc.status.p, B, hipMemcpyDeviceToHost, s));
+    if (row_n_errors) HIP_TRY(hipMemcpyAsync(row_n_errors + r0, lc.nerr.p, B * 4, hipMemcpyDeviceToHost, s));
+    if (err_mask) {
+      std::memset(err_mask + r0 * len, 0, B * len);
+      if (nd) {
+        hmask.resize(nd * len);
+        HIP_TRY(hipMemcpyAsync(hmask.data(), lc.mask.p, nd * len, hipMemcpyDeviceToHost, s));
+      }
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    if (err_mask)
+      for (size_t d = 0; d < nd; d++) std::memcpy(err_mask + (r0 + lc.hdirty[d]) * len, hmask.data() + d * len, len);
+  }
+  if (col_any) HIP_TRY(hipMemcpyAsync(col_any, lc.col_any.p, len, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return LCPC_OK;
+}
+
+lcpc_status locate_args(lcpc_field f, const void *rows, size_t n_rows, size_t len, size_t n_per_row,
+                        const uint64_t *erased, size_t n_erased, std::vector<uint32_t> &e32) {
+  if (!valid_field(f) || (!rows && n_rows)) return fail(LCPC_ERR_INVALID_ARG, "arguments");
+  if (!field_gpu_supported(f)) return fail(LCPC_ERR_UNSUPPORTED, "field has no gfx950 kernels");
+  lcpc_status st = check_fft_len(f, len);
+  if (st) return st;
+  return erasure_check(len, n_per_row, erased, n_erased, e32);
+}
+
+// One pass of lcpc_pos_locate_porenc over the image with the columns e32 never read.  col_any[c] = 1
+// where a row located a wrong element; *noncanon = 1 if a column that was read holds an element
+// that is not < p (the verdicts are then void: such elements were taken as zero).
+lcpc_status pos_locate_pass(Device *dev, hipStream_t s, const uint8_t *porenc, size_t pre, size_t enc, size_t rows,
+                            size_t row_capacity, const std::vector<uint32_t> &e32, uint8_t *col_any, size_t *n_dirty,
+                            size_t *n_unlocatable, uint32_t *noncanon) {
+  lcpc_status st;
+  const int fid = POS_FID;
+  ErasureCtx c;
+  if ((st = erasure_ctx_init(c, dev, s, fid, enc, pre, e32))) return st;
+  std::vector<uint8_t> is_bad(enc, 0);
+  for (uint32_t j : e32) is_bad[j] = 1;
+  // batches of whole BLAKE3 chunks of the column messages, as lcpc_pos_repair_columns
+  const size_t rows_per_chunk = 1024 / POS_WB;
+  const size_t n_chunks = leaf_n_chunks(fid, rows);
+  size_t want_rows = std::max<size_t>(rows_per_chunk, POS_STAGE_BYTES / (enc * POS_WB));
+  if (const char *env = std::getenv("LCPC_POS_REPAIR_BATCH_ROWS")) {
+    const unsigned long long v = std::strtoull(env, nullptr, 10);
+    if (v) want_rows = std::min<size_t>(want_rows, (size_t)v);
+  }
+  const size_t cpb = std::max<size_t>(1, want_rows / rows_per_chunk);
+  const size_t bmax = std::max<size_t>(1, std::min(rows, cpb * rows_per_chunk));
+  LocateCtx lc;
+  if ((st = locate_ctx_init(lc, c, dev, bmax))) return st;
+  DBuf src, g, h, dbad;
+  HIP_TRY(src.alloc(dev, bmax * enc * POS_WB));
+  HIP_TRY(g.alloc(dev, bmax * enc * POS_WB));
+  HIP_TRY(h.alloc(dev, bmax * enc * POS_WB));
+  HIP_TRY(dbad.alloc(dev, 8));
+  HIP_TRY(hipMemsetAsync(dbad.p, 0, 8, s));
+  Pinned stg[2];
+  for (auto &x : stg)
+    if (!x.get(dev, bmax * enc * POS_WB)) return fail(LCPC_ERR_OUT_OF_MEMORY, "pinned host staging");
+  auto batch_rows = [&](size_t c_lo, size_t *r0, size_t *B, size_t *c_hi) {
+    *c_hi = std::min(n_chunks, c_lo + cpb);
+    *r0 = std::min(rows, lcpc_leaf_chunk_first_row((lcpc_field)fid, c_lo));
+    const size_t r1 = *c_hi == n_chunks ? rows : std::min(rows, lcpc_leaf_chunk_first_row((lcpc_field)fid, *c_hi));
+    *B = r1 - *r0;
+  };
+  // the known columns are never read, neither here nor by the kernels
+  auto stage = [&](int slot, size_t r0, size_t B) {
+    if (!B) return;
+    parallel_for(enc, [&](size_t col) {
+      if (!is_bad[col])
+        std::memcpy(stg[slot].b() + col * B * POS_WB, porenc + (col * row_capacity + r0) * POS_WB, B * POS_WB);
+    });
+  };
+  std::vector<uint8_t> hstatus(bmax);
+  size_t nd_total = 0, nu_total = 0;
+  size_t r0 = 0, B = 0, c_hi = 0;
+  batch_rows(0, &r0, &B, &c_hi);
+  stage(0, r0, B);
+  int k = 0;
+  for (size_t c_lo = 0; c_lo < n_chunks; c_lo = c_hi, k++) {
+    batch_rows(c_lo, &r0, &B, &c_hi);
+    const int slot = k & 1;
+    if (B) {
+      HIP_TRY(hipMemcpyAsync(src.p, stg[slot].p, enc * B * POS_WB, hipMemcpyHostToDevice, s));
+      HIP_TRY(erasure_masked_cols(fid, src.as<uint32_t>(), B, c.log_n, g.as<uint32_t>(), nullptr,
+                                  c.slot.as<int32_t>(), c.lambda.as<uint32_t>(), dbad.as<uint32_t>(), s));
+      if ((st = locate_scan(c, lc, g.as<uint32_t>(), h.as<uint32_t>(), B))) return st;
+    }
+    // the next batch's rows gather on the host while this one runs
+    if (c_hi < n_chunks) {
+      size_t nr0, nB, nchi;
+      batch_rows(c_hi, &nr0, &nB, &nchi);
+      stage((k + 1) & 1, nr0, nB);
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    if (!B) continue;
+    if ((st = locate_dirty(c, lc, g.as<uint32_t>(), h.as<uint32_t>(), B))) return st;
+    if (!lc.hdirty.empty()) {
+      HIP_TRY(hipMemcpyAsync(hstatus.data(), lc.status.p, B, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      nd_total += lc.hdirty.size();
+      for (uint32_t r : lc.hdirty) nu_total += hstatus[r] == 2;
+    }
+  }
+  HIP_TRY(hipMemcpyAsync(noncanon, dbad.p, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(col_any, lc.col_any.p, enc, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *n_dirty = nd_total;
+  *n_unlocatable = nu_total;
+  return LCPC_OK;
+}
+
+// col_bad[c] = 1 for the columns not in `skip` that hold an element that is not < p
+lcpc_status pos_noncanonical_columns(Device *dev, hipStream_t s, const uint8_t *porenc, size_t enc, size_t rows,
+                                     size_t row_capacity, const std::vector<uint8_t> &skip,
+                                     std::vector<uint32_t> &col_bad) {
+  col_bad.assign(enc, 0);
+  const size_t col_bytes = rows * POS_WB;
+  if (!col_bytes) return LCPC_OK;
+  const size_t cpb = std::max<size_t>(1, std::min(enc, POS_STAGE_BYTES / col_bytes));
+  DBuf dcols, dbad;
+  HIP_TRY(dcols.alloc(dev, cpb * col_bytes));
+  HIP_TRY(dbad.alloc(dev, enc * 4));
+  HIP_TRY(hipMemsetAsync(dbad.p, 0, enc * 4, s));
+  Pinned stg;
+  if (!stg.get(dev, cpb * col_bytes)) return fail(LCPC_ERR_OUT_OF_MEMORY, "pinned host staging");
+  for (size_t c0 = 0; c0 < enc; c0 += cpb) {
+    const size_t nc = std::min(enc, c0 + cpb) - c0;
+    parallel_for(nc, [&](size_t c) {
+      if (skip[c0 + c])  // never read: zeros are canonical
+        std::memset(stg.b() + c * col_bytes, 0, col_bytes);
+      else
+        std::memcpy(stg.b() + c * col_bytes, porenc + (c0 + c) * row_capacity * POS_WB, col_bytes);
+    });
+    HIP_TRY(hipMemcpyAsync(dcols.p, stg.p, nc * col_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(scrub_col_canon(POS_FID, dcols.as<uint32_t>(), rows, nc, dbad.as<uint32_t>() + c0, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  HIP_TRY(hipMemcpyAsync(col_bad.data(), dbad.p, enc * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return LCPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t lcpc_rs_locate_max_errors(lcpc_field f) { return valid_field(f) ? rs_locate_cap(f) : 0; }
+
+lcpc_status lcpc_rs_locate_errors_rows(lcpc_field f, const uint64_t *rows, size_t n_rows, size_t len, size_t n_per_row,
+                                       const uint64_t *erased, size_t n_erased, uint8_t *row_status,
+                                       uint32_t *row_n_errors, uint8_t *err_mask, uint8_t *col_any) {
+  std::vector<uint32_t> e32;
+  lcpc_status st = locate_args(f, rows, n_rows, len, n_per_row, erased, n_erased, e32);
+  if (st) return st;
+  if (!row_status && n_rows) return fail(LCPC_ERR_INVALID_ARG, "null argument");
+  if (n_rows == 0) {
+    if (col_any) std::memset(col_any, 0, len);
+    return LCPC_OK;
+  }
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  return locate_rows(dev, lease.s, f, rows, n_rows, len, n_per_row, e32, row_status, row_n_errors, err_mask, col_any);
+}
+
+lcpc_status lcpc_rs_decode_rows(lcpc_field f, uint64_t *rows, size_t n_rows, size_t len, size_t n_per_row,
+                                const uint64_t *erased, size_t n_erased, uint8_t *row_status) {
+  std::vector<uint32_t> e32;
+  lcpc_status st = locate_args(f, rows, n_rows, len, n_per_row, erased, n_erased, e32);
+  if (st) return st;
+  if (n_rows == 0) return LCPC_OK;
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  hipStream_t s = lease.s;
+  const size_t wb = (size_t)field_bytes(f), nl = wb / 8;
+  std::vector<uint8_t> status(n_rows), mask(n_rows * len);
+  if ((st = locate_rows(dev, s, f, rows, n_rows, len, n_per_row, e32, status.data(), nullptr, mask.data(), nullptr)))
+    return st;
+  if (row_status) std::memcpy(row_status, status.data(), n_rows);
+  for (size_t r = 0; r < n_rows; r++)
+    if (status[r] == 2)
+      return fail(LCPC_ERR_UNRECOVERABLE, "a row has more wrong positions than can be located (row " +
+                                              std::to_string(r) + ")");
+  // Erasure decoding with the known and the located positions as the erasure set: the same codeword,
+  // which any n_per_row positions fix.  Consecutive rows share a set while its size fits the code's
+  // redundancy; a row alone always fits (n_erased + its errors <= n_erased + (len - n_per_row - n_erased) / 2).
+  struct Write {
+    size_t r, pos;
+    size_t val;  // index of the value's first limb in `vals`
+  };
+  std::vector<Write> writes;
+  std::vector<uint64_t> vals, filled;
+  const size_t room = len - n_per_row;
+  std::vector<uint8_t> in_union(len);
+  size_t lo = 0;
+  while (lo < n_rows) {
+    std::fill(in_union.begin(), in_union.end(), 0);
+    for (uint32_t j : e32) in_union[j] = 1;
+    size_t count = n_erased, hi = lo;
+    std::vector<uint32_t> set = e32;
+    for (; hi < n_rows; hi++) {
+      const uint8_t *m = mask.data() + hi * len;
+      size_t extra = 0;
+      for (size_t p = 0; p < len; p++) extra += m[p] && !in_union[p];
+      if (hi > lo && count + extra > room) break;
+      for (size_t p = 0; p < len; p++)
+        if (m[p] && !in_union[p]) {
+          in_union[p] = 1;
+          set.push_back((uint32_t)p);
+        }
+      count += extra;
+    }
+    if ((st = erasure_decode_values(dev, s, f, rows + lo * len * nl, hi - lo, len, n_per_row, set, filled))) return st;
+    for (size_t r = lo; r < hi; r++)
+      for (size_t j = 0; j < set.size(); j++)
+        if (j < n_erased || mask[r * len + set[j]]) {
+          writes.push_back({r, set[j], vals.size()});
+          const uint64_t *v = filled.data() + ((r - lo) * set.size() + j) * nl;
+          vals.insert(vals.end(), v, v + nl);
+        }
+    lo = hi;
+  }
+  // nothing was written so far: only the located and the erased positions are, every other limb keeps its bits
+  for (const Write &w : writes) std::memcpy(rows + (w.r * len + w.pos) * nl, vals.data() + w.val, wb);
+  return LCPC_OK;
+}
+
+lcpc_status lcpc_pos_locate_porenc(const uint8_t *porenc, size_t pre, size_t enc, size_t rows_written,
+                                   size_t row_capacity, const uint64_t *known_bad, size_t n_known, uint8_t *col_status,
+                                   size_t *n_bad_cols, size_t *n_dirty_rows, size_t *n_unlocatable_rows) {
+  lcpc_status st = pos_dims_check(pre, enc);
+  if (st) return st;
+  if (rows_written > row_capacity) return fail(LCPC_ERR_INVALID_ARG, "rows_written > row_capacity");
+  if (!col_status || (!porenc && rows_written)) return fail(LCPC_ERR_INVALID_ARG, "null argument");
+  std::vector<uint32_t> e32;
+  if ((st = erasure_check(enc, pre, known_bad, n_known, e32))) return st;
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  hipStream_t s = lease.s;
+  std::vector<uint8_t> col_any(enc, 0), is_known(enc, 0), is_noncanon(enc, 0);
+  for (uint32_t j : e32) is_known[j] = 1;
+  size_t n_dirty = 0, n_unloc = 0;
+  if (rows_written) {
+    // optimistic: the masked load's flag says whether any column it read is non-canonical; only then
+    // the image is scanned to name those columns, which join the erasure set for a second pass
+    uint32_t noncanon = 0;
+    if ((st = pos_locate_pass(dev, s, porenc, pre, enc, rows_written, row_capacity, e32, col_any.data(), &n_dirty,
+                              &n_unloc, &noncanon)))
+      return st;
+    if (noncanon) {
+      std::vector<uint32_t> col_bad;
+      if ((st = pos_noncanonical_columns(dev, s, porenc, enc, rows_written, row_capacity, is_known, col_bad)))
+        return st;
+      for (size_t c = 0; c < enc; c++)
+        if (col_bad[c] && !is_known[c]) {
+          is_noncanon[c] = 1;
+          e32.push_back((uint32_t)c);
+        }
+      if (e32.size() > enc - pre)
+        return fail(LCPC_ERR_UNRECOVERABLE, "more known and non-canonical columns than the code's redundancy (enc - pre)");
+      if ((st = pos_locate_pass(dev, s, porenc, pre, enc, rows_written, row_capacity, e32, col_any.data(), &n_dirty,
+                                &n_unloc, &noncanon)))
+        return st;
+    }
+  }
+  size_t n_bad = 0;
+  for (size_t c = 0; c < enc; c++) {
+    col_status[c] = is_known[c] ? 3 : is_noncanon[c] ? 2 : col_any[c] ? 1 : 0;
+    n_bad += col_status[c] != 0;
+  }
+  if (n_bad_cols) *n_bad_cols = n_bad;
+  if (n_dirty_rows) *n_dirty_rows = n_dirty;
+  if (n_unlocatable_rows) *n_unlocatable_rows = n_unloc;
   return LCPC_OK;
 }
 

@@ -270,6 +270,51 @@ def erasure_decode_rows(field: int, rows: np.ndarray, n_per_row: int, erased) ->
     return a2.reshape(shape)
 
 
+def rs_locate_max_errors(field: int) -> int:
+    """The most wrong positions per row the locator can name for this field (at least 256)."""
+    return int(N.load().lcpc_rs_locate_max_errors(field))
+
+
+def _rows_and_erasures(field: int, rows, erased):
+    nl = limbs(field)
+    a = np.ascontiguousarray(rows, dtype=np.uint64).copy()
+    shape = a.shape
+    length = shape[-2] if a.ndim >= 2 else a.size // nl
+    a2 = a.reshape(-1, length * nl)
+    e = np.ascontiguousarray(np.asarray(list(erased), dtype=np.uint64).reshape(-1))
+    return a2, shape, length, e
+
+
+def locate_errors_rows(field: int, rows: np.ndarray, n_per_row: int, erased=()):
+    """Which positions of each row are wrong, from the row alone (syndromes, Berlekamp-Massey, root
+    search).  rows as erasure_decode_rows; the positions `erased` are known to be missing and never
+    read.  Returns (row_status, row_n_errors, err_mask, col_any): row_status[r] = 0 the row is a
+    codeword on its surviving positions, 1 its wrong positions are located (err_mask[r, c] = 1
+    there), 2 not locatable: more than (len - n_per_row - len(erased)) // 2 of them, or more than
+    rs_locate_max_errors(field).  col_any[c] = 1 if any located row names position c."""
+    a2, _, length, e = _rows_and_erasures(field, rows, erased)
+    n = a2.shape[0]
+    status = np.zeros(max(n, 1), np.uint8)
+    n_err = np.zeros(max(n, 1), np.uint32)
+    mask = np.zeros((max(n, 1), length), np.uint8)
+    col_any = np.zeros(length, np.uint8)
+    _raise(N.load().lcpc_rs_locate_errors_rows(
+        field, _p64(a2), n, length, n_per_row, _p64(e) if e.size else None, e.size,
+        status.ctypes.data_as(N.u8p), n_err.ctypes.data_as(N.u32p), mask.ctypes.data_as(N.u8p),
+        col_any.ctypes.data_as(N.u8p)))
+    return status[:n], n_err[:n], mask[:n], col_any
+
+
+def decode_rows(field: int, rows: np.ndarray, n_per_row: int, erased=()) -> np.ndarray:
+    """Errors-and-erasures correction: a copy of rows with the erased and the located wrong positions
+    holding the codeword's values; every other limb is the input's.  Raises (code UNRECOVERABLE)
+    if any row is not locatable; nothing is corrected then."""
+    a2, shape, length, e = _rows_and_erasures(field, rows, erased)
+    _raise(N.load().lcpc_rs_decode_rows(field, _p64(a2), a2.shape[0], length, n_per_row,
+                                        _p64(e) if e.size else None, e.size, None))
+    return a2.reshape(shape)
+
+
 # ---------------------------------------------------------------- convert_file_data_to_commit
 @dataclass
 class Commit:

@@ -20,6 +20,9 @@ formats of the reference's proof-of-storage/src/lcpc_online (names kept):
   EncodedFileReader.find_damaged_columns / repair_columns / decode_with_erasures
                         no counterpart: damaged columns located against the stored leaves and
                         recomputed by Reed-Solomon erasure decoding
+  EncodedFileReader.locate_damaged_columns, FileHandler.scrub / repair (locate=True)
+                        no counterpart: damaged columns located by the code's own syndromes where
+                        the tree cannot say
 
 Layout of a `.porenc` file (WriteableFt63): column c occupies row_capacity * 8 bytes starting at
 byte c * row_capacity * 8; its first rows_written elements are the canonical little-endian repr
@@ -80,6 +83,10 @@ class ScrubReport:
     root_ok: Optional[bool]           # stored root == expected_root (None: no expected_root given)
     raw_ok: bool                      # the raw file re-encodes to the stored tree
     repaired_from: Optional[str] = None  # repair: "+"-joined of "columns", "tree", "reencode", "raw"
+    # locate=True only: the columns the code's own syndromes name (no tree needed), and the rows whose
+    # wrong elements are too many to be located
+    located_columns: Optional[List[int]] = None
+    unlocatable_rows: Optional[int] = None
 
     @property
     def clean(self) -> bool:
@@ -847,6 +854,36 @@ class EncodedFileReader:
         status, _ = self._scrub(tree.digests[:self.encoded_size])
         return [int(c) for c in np.flatnonzero(status)], [int(c) for c in np.flatnonzero(status == 2)]
 
+    def _locate(self, known_bad=()) -> Tuple[np.ndarray, int, int]:
+        """(col_status, dirty_rows, unlocatable_rows) of lcpc_pos_locate_porenc."""
+        w = self.encoded_size
+        known = np.ascontiguousarray(np.asarray(list(known_bad), dtype=np.uint64).reshape(-1))
+        status = np.zeros(w, np.uint8)
+        n_bad, n_dirty, n_unloc = C.c_size_t(), C.c_size_t(), C.c_size_t()
+
+        def run(a):
+            code = N.load().lcpc_pos_locate_porenc(
+                _u8(a), self.pre_encoded_size, w, self.rows_written, self.row_capacity,
+                known.ctypes.data_as(N.u64p) if known.size else None, known.size, _u8(status),
+                C.byref(n_bad), C.byref(n_dirty), C.byref(n_unloc))
+            if code == LCPC_ERR_UNRECOVERABLE:
+                raise UnrecoverableError(N.last_error())
+            _raise(code)
+        self._with_map(run)
+        return status, int(n_dirty.value), int(n_unloc.value)
+
+    def locate_damaged_columns(self, known_bad=()) -> Tuple[np.ndarray, int]:
+        """The damaged columns by the code's own redundancy, without a tree: every row's syndromes,
+        Berlekamp-Massey and a root search name the wrong elements of up to
+        (encoded_size - pre_encoded_size - erasures) // 2 columns per row.  Returns (col_status,
+        unlocatable_rows): col_status[c] = 0 nothing found, 1 a wrong element was located in some
+        row, 2 the column holds an element that is not < p, 3 listed in known_bad (never read).
+        unlocatable_rows > 0: some rows hold more wrong elements than can be located, and their
+        columns are not named.  UnrecoverableError if the known and the non-canonical columns
+        outnumber the code's redundancy."""
+        status, _, n_unloc = self._locate(known_bad)
+        return status, n_unloc
+
     def _repair(self, columns, want_cols: bool, want_digests: bool, want_data: bool):
         cols_idx = np.ascontiguousarray(np.asarray(list(columns), dtype=np.uint64).reshape(-1))
         k, rows = cols_idx.size, self.rows_written
@@ -1337,13 +1374,124 @@ class FileHandler:
             raw_ok=raw_tree is not None and raw_tree == tree)
         return report, tree, digests, raw_tree
 
-    def scrub(self, expected_root: Optional[bytes] = None) -> ScrubReport:
+    def _locate_into(self, report: ScrubReport) -> np.ndarray:
+        """Fills report.located_columns / unlocatable_rows from the code's own syndromes."""
+        with open(self.encoded_file_handle, "rb") as f:
+            status, n_unloc = self._reader(f).locate_damaged_columns()
+        report.located_columns = [int(c) for c in np.flatnonzero(status)]
+        report.unlocatable_rows = n_unloc
+        return status
+
+    def _scrub_state_located(self, expected_root: Optional[bytes]) -> ScrubReport:
+        """scrub(locate=True): as _scrub_state, but a tree file that is missing or has the wrong
+        length is a finding (no bad_columns, tree_consistent False), not an error."""
+        try:
+            report = self._scrub_state(expected_root)[0]
+        except (UnrecoverableError, OSError):
+            report = ScrubReport(bad_columns=[], noncanonical_columns=[], tree_consistent=False,
+                                 root_ok=None if expected_root is None else False, raw_ok=False)
+        try:
+            status = self._locate_into(report)
+            if not report.bad_columns and not report.tree_consistent:
+                report.noncanonical_columns = [int(c) for c in np.flatnonzero(status == 2)]
+        except UnrecoverableError:  # more non-canonical columns than the code's redundancy
+            report.located_columns, report.unlocatable_rows = [], self.rows_written
+        return report
+
+    def scrub(self, expected_root: Optional[bytes] = None, locate: bool = False) -> ScrubReport:
         """Read-only health check of the four files against each other (and against expected_root,
         the root the client holds, if given): which `.porenc` columns differ from their stored
-        leaves, whether the stored tree refolds, whether the raw file still encodes to it."""
+        leaves, whether the stored tree refolds, whether the raw file still encodes to it.
+        locate=True also asks the code itself (EncodedFileReader.locate_damaged_columns): the report
+        gains located_columns and unlocatable_rows, and a tree file that is missing or has the wrong
+        length no longer raises (bad_columns is then empty and tree_consistent False)."""
+        if locate:
+            return self._scrub_state_located(expected_root)
         return self._scrub_state(expected_root)[0]
 
-    def repair(self, expected_root: Optional[bytes] = None) -> ScrubReport:
+    def _repair_located(self, expected_root: Optional[bytes]) -> ScrubReport:
+        """repair(locate=True) where the tree cannot say where the damage is: the columns the code's
+        syndromes name are recomputed, and the result is written only if the tree over all column
+        digests folds to expected_root -- or, with no expected_root, equals the tree of a fresh
+        encode of the raw file.  The code's self-consistency alone is never an anchor."""
+        w, pre = self.encoded_size, self.pre_encoded_size
+        report = self._scrub_state_located(expected_root)
+        raw_tree = self._raw_file_tree()
+        if report.unlocatable_rows:
+            raise UnrecoverableError(f"{report.unlocatable_rows} rows hold more wrong elements than can be located")
+        bad = report.located_columns
+        if len(bad) > w - pre:
+            raise UnrecoverableError(f"{len(bad)} columns located as damaged (at most {w - pre} can be recomputed)")
+        if expected_root is None and raw_tree is None:
+            raise UnrecoverableError("no expected_root was given and the raw file cannot vouch for the repair")
+        with open(self.encoded_file_handle, "rb") as f:
+            reader = self._reader(f)
+            cols, rdig = reader.repair_columns(bad) if bad else (None, None)
+            # the digests of every column as the file holds it; the located ones are replaced below
+            _, digests = reader._scrub(np.zeros((w, DIGEST_BYTES), np.uint8))
+        digests = digests.copy()
+        if bad:
+            digests[bad] = rdig
+        new_tree = MerkleTree.new(digests)
+        if expected_root is not None:
+            if new_tree.root() != bytes(expected_root):
+                raise UnrecoverableError("the located repair does not fold to expected_root")
+        elif raw_tree != new_tree:
+            raise UnrecoverableError("the located repair and the raw file do not agree")
+        done = ["located"]
+        if bad:
+            wb, wrote = WRITTEN_BYTES_WIDTH, False
+            with open(self.encoded_file_handle, "r+b") as f:
+                for k, c in enumerate(bad):
+                    new = cols[k].tobytes()
+                    f.seek(c * self.row_capacity * wb)
+                    if f.read(len(new)) != new:
+                        f.seek(c * self.row_capacity * wb)
+                        f.write(new)
+                        wrote = True
+                f.flush()
+            if wrote:
+                done.append("columns")
+        try:
+            with open(self.merkle_tree_file_handle, "rb") as f:
+                tree_same = f.read() == new_tree.to_bytes()
+        except OSError:
+            tree_same = False
+        if not tree_same:
+            self.write_tree(new_tree)
+            done.append("tree")
+        self.merkle_tree = new_tree
+        if raw_tree is None or raw_tree != new_tree:
+            with open(self.encoded_file_handle, "rb") as f:
+                data = self._reader(f)._decode(0, self.rows_written) if self.rows_written else b""
+            with open(self.unencoded_file_handle, "wb") as f:
+                f.write(data[:self.total_data_bytes])
+            done.append("raw")
+        if self.chunk_cache is not None:
+            cache = self._rebuild_chunk_cache()
+            write_chunk_cv_sidecar(self.chunk_cv_file_handle, w, self.rows_written, cache.tree().root(),
+                                   cache.copy_cvs())
+            self.chunk_cache.close()
+            self.chunk_cache = cache
+        report.repaired_from = "+".join(done)
+        return report
+
+    def repair(self, expected_root: Optional[bytes] = None, locate: bool = False) -> ScrubReport:
+        """Mend what scrub finds; see _repair_by_tree.  locate=True: that path runs first, unchanged;
+        only where it raises UnrecoverableError -- the tree file is missing or has the wrong length,
+        it does not refold and no expected_root was given, or the leaves name too many columns and the
+        raw file does not verify -- the damaged columns are located by the code's own syndromes
+        (_repair_located; repaired_from then starts with "located").  That result is written only
+        if it verifies against expected_root, or, without one, against a fresh encode of the raw
+        file; otherwise UnrecoverableError with every file byte for byte what it was."""
+        if not locate:
+            return self._repair_by_tree(expected_root)
+        try:
+            return self._repair_by_tree(expected_root)
+        except (UnrecoverableError, FileNotFoundError):
+            return self._repair_located(expected_root)
+
+    def _repair_by_tree(self, expected_root: Optional[bytes] = None) -> ScrubReport:
         """Mend what scrub finds.  Everything written is first verified against the trust anchor:
         expected_root if given, otherwise the stored tree's root provided the stored tree is
         self-consistent.  Up to encoded_size - pre_encoded_size damaged columns are recomputed from

@@ -14,6 +14,6 @@ export LCPC_ORACLE_LIB=$PWD/oracle/build/omega_inv_natural/liblcpc_oracle.so
 test -f $LCPC_MI_LIB && test -f $LCPC_ORACLE_LIB || { echo "variant builds missing"; exit 1; }
 timeout -k 10 600 python -u -m pytest -x -v --timeout 200 --timeout-method thread -m gpu \
   tests/test_gpu_parity.py tests/test_gpu_pos.py tests/test_gpu_ntt_row1.py tests/test_gpu_host_input.py \
-  tests/test_gpu_rs_erasure.py tests/test_gpu_pos_repair.py \
+  tests/test_gpu_rs_erasure.py tests/test_gpu_pos_repair.py tests/test_gpu_rs_locate.py tests/test_gpu_pos_locate.py \
   -k "not golden" > $O/pytest.log 2>&1 || { tail -40 $O/pytest.log; exit 1; }
 tail -3 $O/pytest.log
