@@ -33,7 +33,9 @@ extern "C" {
 /* 2: the PoS column chunk-CV cache (lcpc_pos_chunk_cache_*); 3: R-S erasure decoding, scrub and
  * repair of stored files (lcpc_rs_*, lcpc_pos_scrub_porenc, lcpc_pos_repair_columns).  The R-S
  * error location block (lcpc_rs_locate_*, lcpc_rs_decode_rows, lcpc_pos_locate_porenc) is additive
- * within version 3: new symbols only, nothing existing changed. */
+ * within version 3: new symbols only, nothing existing changed.  So is the digest block (lcpc_digest,
+ * lcpc_encoding_set_digest, lcpc_commit_digest and the *_d functions): every existing symbol keeps
+ * its signature and its BLAKE3 meaning. */
 #define LCPC_ABI_VERSION 3
 
 typedef enum lcpc_status {
@@ -77,6 +79,17 @@ typedef enum lcpc_field {
   LCPC_FT255 = 3,     /* lcpc-test-fields/src/lib.rs:65-69 */
   LCPC_FT253_192 = 4  /* proof-of-storage/src/fields/ft253_192.rs:6-10 (big-endian repr) */
 } lcpc_field;
+
+/* The commitment's digest: the reference's type parameter D: Digest of LcCommit<D, E>, LcRoot<D, E>,
+ * LcColumn<D, E> and LcEvalProof<D, E> (lcpc-2d/src/lib.rs:174-191).  All four have 32-byte outputs,
+ * so no buffer of this ABI changes size with D.  Keccak-256 is SHA3-256's permutation and rate with
+ * the pre-standard padding byte 0x01 instead of 0x06 (the EVM's keccak256). */
+typedef enum lcpc_digest {
+  LCPC_DIGEST_BLAKE3 = 0,    /* blake3::Hasher (the default; the only D of the proof-of-storage paths) */
+  LCPC_DIGEST_SHA256 = 1,    /* sha2::Sha256 */
+  LCPC_DIGEST_SHA3_256 = 2,  /* sha3::Sha3_256 */
+  LCPC_DIGEST_KECCAK256 = 3  /* sha3::Keccak256 */
+} lcpc_digest;
 
 typedef struct lcpc_encoding lcpc_encoding;
 typedef struct lcpc_commit lcpc_commit;
@@ -158,6 +171,24 @@ size_t lcpc_encoding_n_cols(const lcpc_encoding *e);
 #define LCPC_ROW_KERNEL_FOURSTEP 1
 #define LCPC_ROW_KERNEL_ONEPASS 2
 lcpc_status lcpc_encoding_set_row_kernel(lcpc_encoding *e, int kernel);
+/* "BLAKE3", "SHA-256", "SHA3-256", "Keccak-256"; NULL for an unknown value.  Host only. */
+const char *lcpc_digest_name(lcpc_digest d);
+/* The digest D of everything made or checked under e: with D substituted, merkleize (lcpc-2d/src/
+ * lib.rs:720-734) hashes leaf j = D(32 zero bytes || to_repr(comm[0][j]) || .. || to_repr(comm[n_rows-1][j]))
+ * (hash_columns :736-775) and node = D(left || right) (:777-815), and verify_column_path (:985-1012)
+ * checks against them.  lcpc_commit_new* build the tree with it, lcpc_prove* / lcpc_check_comm need
+ * a commitment of the same digest (else LCPC_ERR_INVALID_ARG), and lcpc_verify* take it from e: the
+ * verifier, not the proof, says which digest the root belongs to.  The prover's transcript absorbs
+ * no digest (:1057, :1075-1077, :1096-1104), so a proof under another D differs from the BLAKE3
+ * proof of the same polynomial and transcript only in its Merkle paths.  Configuration, with
+ * lcpc_encoding_set_row_kernel's contract: set right after creation, read without synchronisation.
+ * BLAKE3-only, because the reference fixes PoSCommit = LcCommit<Blake3, ..> (proof-of-storage/src/
+ * lib.rs:21) and the sharded engine exchanges BLAKE3 chunk chaining values: lcpc_pos_commit_bytes*,
+ * lcpc_pos_commit_eval_bytes_device, lcpc_pos_columns, lcpc_shard_new* and lcpc_sharded_* return
+ * LCPC_ERR_UNSUPPORTED, naming the digest, for an encoding set to another one; the stored-file
+ * formats, the chunk-CV cache and lcpc_column_digests_* take no encoding and are BLAKE3. */
+lcpc_status lcpc_encoding_set_digest(lcpc_encoding *e, lcpc_digest d);
+lcpc_digest lcpc_encoding_digest(const lcpc_encoding *e);
 /* Pre-allocates the calling thread's page-locked staging for lcpc_prove on commitments of
  * n_rows rows under e (host only).  Optional: a thread's first prove otherwise pays the
  * hipHostMalloc.  No reference counterpart (rayon threads have no device staging). */
@@ -201,6 +232,8 @@ size_t lcpc_commit_n_rows(const lcpc_commit *c);      /* get_n_rows   :309-311 *
 size_t lcpc_commit_n_cols(const lcpc_commit *c);      /* get_n_cols   :304-306 */
 size_t lcpc_commit_n_per_row(const lcpc_commit *c);   /* get_n_per_row :299-301 */
 size_t lcpc_commit_n_hashes(const lcpc_commit *c);
+/* the digest its tree was built with (the encoding's at commit time, or from_parts_d's) */
+lcpc_digest lcpc_commit_digest(const lcpc_commit *c);
 /* LcCommit's serde Deserialize (WrappedLcCommit, lib.rs:193-229): a commitment from its fields --
  * comm (n_rows x n_cols) and coeffs (n_rows x n_per_row) as row-major Montgomery limbs, the
  * n_hashes = 2 next_pow2(n_cols) - 1 digests in commit order (root last) -- loaded into HBM so
@@ -208,6 +241,11 @@ size_t lcpc_commit_n_hashes(const lcpc_commit *c);
 lcpc_status lcpc_commit_from_parts(lcpc_field f, size_t n_rows, size_t n_cols, size_t n_per_row,
                                    const uint64_t *comm, const uint64_t *coeffs, const uint8_t *hashes,
                                    size_t n_hashes, lcpc_commit **out);
+/* The same for an LcCommit<D, E>: the hashes were made with digest d (the serialized fields do not
+ * say which; they are digest-agnostic for 32-byte outputs).  lcpc_commit_from_parts is d = BLAKE3. */
+lcpc_status lcpc_commit_from_parts_d(lcpc_digest d, lcpc_field f, size_t n_rows, size_t n_cols, size_t n_per_row,
+                                     const uint64_t *comm, const uint64_t *coeffs, const uint8_t *hashes,
+                                     size_t n_hashes, lcpc_commit **out);
 /* copies of the public fields comm / coeffs / hashes (:180-190) to host memory */
 lcpc_status lcpc_commit_copy_comm(const lcpc_commit *c, uint64_t *out);
 lcpc_status lcpc_commit_copy_coeffs(const lcpc_commit *c, uint64_t *out);
@@ -322,6 +360,13 @@ int lcpc_verify_column_value(lcpc_field f, const uint64_t *col, const uint64_t *
 /* leaf digests of every column of a host matrix (hash_columns, :736-775) */
 lcpc_status lcpc_hash_columns(lcpc_field f, const uint64_t *comm, size_t n_rows, size_t n_cols,
                               uint8_t *out);
+/* merkle_tree, verify_column_path and hash_columns with D = d (the names above are d = BLAKE3) */
+lcpc_status lcpc_merkle_tree_d(lcpc_digest d, const uint8_t *ins, size_t n_ins, uint8_t *outs);
+int lcpc_verify_column_path_d(lcpc_digest d, lcpc_field f, const uint64_t *col, size_t n_rows,
+                              const uint8_t *path, size_t path_len, size_t col_num,
+                              const uint8_t root[32]);
+lcpc_status lcpc_hash_columns_d(lcpc_digest d, lcpc_field f, const uint64_t *comm, size_t n_rows, size_t n_cols,
+                                uint8_t *out);
 
 /* ------------------------------------------------------------------ proof-of-storage producers
  * (proof-of-storage/src; the field is WriteableFt63 = LCPC_FT63's modulus and arithmetic) */

@@ -6,6 +6,7 @@ include/lcpc_mi.h, implemented by liblcpc_mi.so (gfx950 HIP kernels + C++ host).
 """
 from .lcpc2d import (  # noqa: F401
     FT63, FT127, FT191, FT255, FT253_192, FIELD_NAMES,
+    BLAKE3, SHA256, SHA3_256, KECCAK256, digest_name,
     LcpcError, ProverError, VerifierError, FFTError, DeviceError,
     Transcript, CallerTranscript, LcEncoding, LigeroEncoding, RsEncoding, SdigEncoding, LcCommit, LcEvalProof, LcColumn,
     collapse_columns, merkle_tree, hash_columns, verify_column_path, verify_column_value,

@@ -91,6 +91,9 @@ SIGNATURES = {
     "lcpc_encoding_n_per_row": (sz, [vp]),
     "lcpc_encoding_n_cols": (sz, [vp]),
     "lcpc_encoding_set_row_kernel": (i32, [vp, i32]),
+    "lcpc_digest_name": (C.c_char_p, [i32]),
+    "lcpc_encoding_set_digest": (i32, [vp, i32]),
+    "lcpc_encoding_digest": (i32, [vp]),
     "lcpc_encode": (i32, [vp, u64p, sz]),
     "lcpc_encode_rows": (i32, [vp, u64p, sz, sz]),
     "lcpc_encode_rows_device": (i32, [vp, vp, sz, sz, vp, sz, sz, vp]),
@@ -103,6 +106,8 @@ SIGNATURES = {
     "lcpc_commit_n_per_row": (sz, [vp]),
     "lcpc_commit_n_hashes": (sz, [vp]),
     "lcpc_commit_from_parts": (i32, [i32, sz, sz, sz, u64p, u64p, u8p, sz, C.POINTER(vp)]),
+    "lcpc_commit_digest": (i32, [vp]),
+    "lcpc_commit_from_parts_d": (i32, [i32, i32, sz, sz, sz, u64p, u64p, u8p, sz, C.POINTER(vp)]),
     "lcpc_commit_copy_comm": (i32, [vp, u64p]),
     "lcpc_commit_copy_coeffs": (i32, [vp, u64p]),
     "lcpc_commit_copy_hashes": (i32, [vp, u8p]),
@@ -141,6 +146,9 @@ SIGNATURES = {
     "lcpc_verify_column_path": (i32, [i32, u64p, sz, u8p, sz, sz, u8p]),
     "lcpc_verify_column_value": (i32, [i32, u64p, u64p, sz, u64p]),
     "lcpc_hash_columns": (i32, [i32, u64p, sz, sz, u8p]),
+    "lcpc_merkle_tree_d": (i32, [i32, u8p, sz, u8p]),
+    "lcpc_verify_column_path_d": (i32, [i32, i32, u64p, sz, u8p, sz, sz, u8p]),
+    "lcpc_hash_columns_d": (i32, [i32, i32, u64p, sz, sz, u8p]),
     "lcpc_pos_bytes_to_field": (i32, [u8p, sz, u64p, szp]),
     "lcpc_pos_bytes_to_field_device": (i32, [vp, sz, vp, vp]),
     "lcpc_pos_commit_bytes_device": (i32, [vp, vp, sz, C.POINTER(vp)]),

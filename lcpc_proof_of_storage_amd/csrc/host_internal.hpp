@@ -463,6 +463,9 @@ struct lcpc_encoding {
   int fid = 1;
   int kind = KIND_RS;  // R-S / fft_io (Ligero) or SDIG expander code (Brakedown)
   int code = 0;        // SdigCode id
+  // the commitment's digest D (lcpc_digest; lcpc_encoding_set_digest): configuration, set right
+  // after creation and read without synchronisation
+  int digest = 0;
   uint64_t seed = 0;
   size_t n_per_row = 0, n_cols = 0, n_col_opens = 0, n_degree_tests = 0;
   Device *dev = nullptr;
@@ -481,6 +484,7 @@ struct lcpc_encoding {
 
 struct lcpc_commit {
   int fid = 1;
+  int digest = 0;  // lcpc_digest the tree in `hashes` was built with
   Device *dev = nullptr;
   size_t n_rows = 0, n_cols = 0, n_per_row = 0, n_hashes = 0;
   bool col_major = false;  // comm stored [n_cols][n_rows] (SDIG) instead of [n_rows][n_cols]
@@ -622,6 +626,19 @@ struct lcpc_transcript {
 };
 
 namespace lcpc_host {
+inline const char *digest_name(int d) {  // lcpc_digest_name
+  static const char *const names[] = {"BLAKE3", "SHA-256", "SHA3-256", "Keccak-256"};
+  return digest_valid(d) ? names[d] : nullptr;
+}
+// The entry points that stay BLAKE3-only (the reference fixes PoSCommit = LcCommit<Blake3, ..>,
+// proof-of-storage/src/lib.rs:21; the sharded engine exchanges BLAKE3 chunk chaining values): an
+// encoding set to another digest is refused, never hashed with BLAKE3 silently.
+inline lcpc_status require_blake3(const lcpc_encoding *e, const char *what) {
+  if (!e || e->digest == 0) return LCPC_OK;
+  const char *n = digest_name(e->digest);
+  return fail(LCPC_ERR_UNSUPPORTED, std::string(what) + " is BLAKE3-only; the encoding's digest is " + (n ? n : "?"));
+}
+
 inline lcpc_status encoding_dims_ok(const lcpc_encoding *e, size_t n_per_row, size_t n_cols) {
   if (e->kind == KIND_SDIG)  // SdigEncodingS::dims_ok (lcpc-brakedown-pc/src/lib.rs:157-164)
     return (n_per_row < n_cols && n_per_row == e->n_per_row && n_cols == e->n_cols)

@@ -126,6 +126,22 @@ hipError_t merkle_tree_io(const uint8_t *ins, size_t n_ins, uint8_t *outs, hipSt
 // two) into levels 0..log2(B) of the whole tree of G B leaves ([leaves | level 1 | ...] layout)
 hipError_t assemble_subtrees(const uint8_t *subs, size_t B, size_t G, uint8_t *tree, hipStream_t s);
 
+// ------------------------------------------------------------------ other digests (digest.hip)
+// The commitment's digest D (lcpc_digest): BLAKE3 goes to the functions above, SHA-256 and the
+// Keccak-f[1600] sponge (SHA3-256, Keccak-256: one kernel, the padding byte a parameter) to
+// digest.hip's one-lane-per-column kernels.  Same arguments and layouts as the BLAKE3 functions;
+// scratch is used by BLAKE3 only (leaf_hash_scratch_bytes).  gather_paths, gather_columns and
+// assemble_subtrees are digest-agnostic.
+enum { DIGEST_BLAKE3 = 0, DIGEST_SHA256 = 1, DIGEST_SHA3_256 = 2, DIGEST_KECCAK256 = 3 };
+bool digest_valid(int digest);
+hipError_t leaf_hashes_d(int digest, int fid, const uint32_t *m, size_t n_rows, size_t n_cols, size_t stride,
+                         uint8_t *leaves, void *scratch, hipStream_t s, bool canon = false);
+hipError_t leaf_hashes_cols_d(int digest, int fid, const uint32_t *cols, size_t n_rows, size_t n_cols,
+                              uint8_t *leaves, void *scratch, hipStream_t s, bool canon = false);
+hipError_t merkle_tree_d(int digest, uint8_t *hashes, size_t np2, hipStream_t s);
+hipError_t path_checks_d(int digest, const uint8_t *leaves, const uint8_t *paths, size_t n, size_t path_len,
+                         const uint64_t *idx, const uint8_t *root, uint32_t *flags, hipStream_t s);
+
 // ------------------------------------------------------------------ prover helpers
 // out[t][c] = sum_r tensors[t][r] * coeffs[r][c]   (t < n_tensors, c < n_per_row)
 size_t collapse_scratch_bytes(int fid, size_t n_rows, size_t n_per_row, int n_tensors);

@@ -191,6 +191,10 @@ lcpc_status commit_device(const lcpc_encoding *e, const void *d_src, bool src_is
                           uint64_t *eval_out = nullptr) {
   prof::HostScope hs_total("host_commit_total");
   if (!e || !out) return fail(LCPC_ERR_INVALID_ARG, "null argument");
+  if (src_bytes || eval_left || eval_out) {
+    lcpc_status st = require_blake3(e, "a proof-of-storage commitment");
+    if (st) return st;
+  }
   const size_t np = e->n_per_row, nc = e->n_cols;
   const size_t n_rows = (len + np - 1) / np;  // LcEncoding::get_dims
   // commit's assertions (lcpc-2d/src/lib.rs:659-661) -> invalid argument
@@ -237,6 +241,7 @@ lcpc_status commit_device(const lcpc_encoding *e, const void *d_src, bool src_is
   }
   auto c = std::make_unique<lcpc_commit>();
   c->fid = fid;
+  c->digest = e->digest;
   c->dev = dev;
   c->n_rows = n_rows;
   c->n_cols = nc;
@@ -337,7 +342,15 @@ lcpc_status commit_device(const lcpc_encoding *e, const void *d_src, bool src_is
     if (st) return st;
     HIP_TRY(dsum.alloc(dev, nc * wb));
   }
-  if (c->col_major) {
+  if (c->digest != DIGEST_BLAKE3) {
+    // D = SHA-256 / SHA3-256 / Keccak-256 (digest.hip); (eval is BLAKE3-only: refused above)
+    if (c->col_major)
+      HIP_TRY(leaf_hashes_cols_d(c->digest, fid, c->comm.as<uint32_t>(), n_rows, nc, c->hashes.as<uint8_t>(), nullptr, s,
+                                 c->canon));
+    else
+      HIP_TRY(leaf_hashes_d(c->digest, fid, c->comm.as<uint32_t>(), n_rows, nc, nc, c->hashes.as<uint8_t>(), nullptr, s,
+                            c->canon));
+  } else if (c->col_major) {
     HIP_TRY(leaf_hashes_cols(fid, c->comm.as<uint32_t>(), n_rows, nc, c->hashes.as<uint8_t>(), scratch.p, s,
                              c->canon));
   } else if (fused) {
@@ -357,7 +370,7 @@ lcpc_status commit_device(const lcpc_encoding *e, const void *d_src, bool src_is
                             cs.p, s));
     }
   }
-  HIP_TRY(merkle_tree(c->hashes.as<uint8_t>(), np2, s));
+  HIP_TRY(merkle_tree_d(c->digest, c->hashes.as<uint8_t>(), np2, s));
   if (eval) {
     // over a canonical matrix the Montgomery products come out as canonical values
     if (c->canon) HIP_TRY(convert(fid, dsum.as<uint32_t>(), dsum.as<uint32_t>(), nc, true, s));
@@ -551,6 +564,14 @@ lcpc_status lcpc_encoding_set_row_kernel(lcpc_encoding *e, int kernel) {
   e->plan.row_kernel = kernel;
   return LCPC_OK;
 }
+
+const char *lcpc_digest_name(lcpc_digest d) { return digest_name((int)d); }
+lcpc_status lcpc_encoding_set_digest(lcpc_encoding *e, lcpc_digest d) {
+  if (!e || !digest_valid((int)d)) return fail(LCPC_ERR_INVALID_ARG, "digest");
+  e->digest = (int)d;
+  return LCPC_OK;
+}
+lcpc_digest lcpc_encoding_digest(const lcpc_encoding *e) { return (lcpc_digest)(e ? e->digest : 0); }
 
 lcpc_status lcpc_reserve(const lcpc_encoding *e, size_t len, size_t count) {
   if (!e || !len) return fail(LCPC_ERR_INVALID_ARG, "reserve arguments");
@@ -751,6 +772,7 @@ size_t lcpc_commit_n_rows(const lcpc_commit *c) { return c->n_rows; }
 size_t lcpc_commit_n_cols(const lcpc_commit *c) { return c->n_cols; }
 size_t lcpc_commit_n_per_row(const lcpc_commit *c) { return c->n_per_row; }
 size_t lcpc_commit_n_hashes(const lcpc_commit *c) { return c->n_hashes; }
+lcpc_digest lcpc_commit_digest(const lcpc_commit *c) { return (lcpc_digest)(c ? c->digest : 0); }
 const void *lcpc_commit_device_comm(const lcpc_commit *c) { return c->comm.p; }
 const void *lcpc_commit_device_coeffs(const lcpc_commit *c) { return c->coeffs.p; }
 
@@ -798,6 +820,12 @@ lcpc_status lcpc_commit_copy_hashes(const lcpc_commit *c, uint8_t *out) {
 lcpc_status lcpc_commit_from_parts(lcpc_field f, size_t n_rows, size_t n_cols, size_t n_per_row,
                                    const uint64_t *comm, const uint64_t *coeffs, const uint8_t *hashes,
                                    size_t n_hashes, lcpc_commit **out) {
+  return lcpc_commit_from_parts_d(LCPC_DIGEST_BLAKE3, f, n_rows, n_cols, n_per_row, comm, coeffs, hashes, n_hashes, out);
+}
+
+lcpc_status lcpc_commit_from_parts_d(lcpc_digest d, lcpc_field f, size_t n_rows, size_t n_cols, size_t n_per_row,
+                                     const uint64_t *comm, const uint64_t *coeffs, const uint8_t *hashes,
+                                     size_t n_hashes, lcpc_commit **out) {
   // LcCommit's Deserialize (WrappedLcCommit::unwrap, lcpc-2d/src/lib.rs:193-229): the fields as
   // given (row-major Montgomery comm and coeffs, the hashes in commit order, root last), loaded
   // into HBM so that prove / open_column run on them.  The reference takes any lengths and fails
@@ -805,6 +833,7 @@ lcpc_status lcpc_commit_from_parts(lcpc_field f, size_t n_rows, size_t n_cols, s
   // produces, else LCPC_ERR_INVALID_ARG.
   if (!out || (!comm && n_rows * n_cols) || (!coeffs && n_rows * n_per_row) || !hashes)
     return fail(LCPC_ERR_INVALID_ARG, "null argument");
+  if (!digest_valid((int)d)) return fail(LCPC_ERR_INVALID_ARG, "digest");
   if (!valid_field(f) || !field_gpu_supported(f)) return fail(LCPC_ERR_UNSUPPORTED, "field");
   if (!n_rows || !n_cols || n_per_row > n_cols || n_hashes != 2 * next_pow2(n_cols) - 1)
     return fail(LCPC_ERR_INVALID_ARG, "commitment parts of inconsistent sizes");
@@ -815,6 +844,7 @@ lcpc_status lcpc_commit_from_parts(lcpc_field f, size_t n_rows, size_t n_cols, s
   HIP_TRY(hipSetDevice(dev->id));
   auto c = std::make_unique<lcpc_commit>();
   c->fid = f;
+  c->digest = (int)d;
   c->dev = dev;
   c->n_rows = n_rows;
   c->n_cols = n_cols;
@@ -834,6 +864,10 @@ lcpc_status lcpc_commit_from_parts(lcpc_field f, size_t n_rows, size_t n_cols, s
 lcpc_status lcpc_check_comm(const lcpc_commit *c, const lcpc_encoding *e) {
   // check_comm (lcpc-2d/src/lib.rs:703-718); buffer sizes hold by construction
   if (!c || !e) return fail(LCPC_ERR_INVALID_ARG, "null argument");
+  // D is a type parameter of LcCommit in the reference: a mismatch cannot be written there
+  if (c->digest != e->digest)
+    return fail(LCPC_ERR_INVALID_ARG, std::string("the commitment's digest is ") + digest_name(c->digest) +
+                                          ", the encoding's " + digest_name(e->digest));
   const bool hashlen = c->n_hashes != 2 * next_pow2(c->n_cols) - 1;
   if (hashlen || encoding_dims_ok(e, c->n_per_row, c->n_cols) != LCPC_OK || c->fid != e->fid)
     return fail(LCPC_PROVER_COMMIT, "ProverError::Commit");
@@ -1150,9 +1184,10 @@ lcpc_status lcpc_verify(const uint8_t root[32], const uint64_t *outer, size_t ou
   HIP_TRY(scratch.alloc(dev, leaf_hash_scratch_bytes(fid, nr, nco)));
   HIP_TRY(column_checks(fid, dcols.as<uint32_t>(), nco, nr, dtens.as<uint32_t>(), (int)(ndt + 1),
                         denc.as<uint32_t>(), nc, didx.as<uint64_t>(), dflags.as<uint32_t>(), s));
-  HIP_TRY(leaf_hashes_cols(fid, dcols.as<uint32_t>(), nr, nco, dleaves.as<uint8_t>(), scratch.p, s));
-  HIP_TRY(path_checks(dleaves.as<uint8_t>(), dpaths.as<uint8_t>(), nco, p->path_len,
-                      didx.as<uint64_t>(), droot.as<uint8_t>(), dpflags.as<uint32_t>(), s));
+  // the verifier's encoding says which digest the root belongs to
+  HIP_TRY(leaf_hashes_cols_d(e->digest, fid, dcols.as<uint32_t>(), nr, nco, dleaves.as<uint8_t>(), scratch.p, s));
+  HIP_TRY(path_checks_d(e->digest, dleaves.as<uint8_t>(), dpaths.as<uint8_t>(), nco, p->path_len,
+                        didx.as<uint64_t>(), droot.as<uint8_t>(), dpflags.as<uint32_t>(), s));
   std::vector<uint32_t> flags(nco * (ndt + 1)), pflags(nco);
   HIP_TRY(hipMemcpyAsync(flags.data(), dflags.p, flags.size() * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(pflags.data(), dpflags.p, pflags.size() * 4, hipMemcpyDeviceToHost, s));
@@ -1218,18 +1253,23 @@ lcpc_status lcpc_collapse_columns(lcpc_field f, const uint64_t *coeffs, const ui
 }
 
 lcpc_status lcpc_merkle_tree(const uint8_t *ins, size_t n_ins, uint8_t *outs) {
+  return lcpc_merkle_tree_d(LCPC_DIGEST_BLAKE3, ins, n_ins, outs);
+}
+
+lcpc_status lcpc_merkle_tree_d(lcpc_digest d, const uint8_t *ins, size_t n_ins, uint8_t *outs) {
+  if (!digest_valid((int)d)) return fail(LCPC_ERR_INVALID_ARG, "digest");
   if (!n_ins || (n_ins & (n_ins - 1))) return fail(LCPC_ERR_INVALID_ARG, "ins.len() must be 2^k");
   lcpc_status st;
   Device *dev = current_device(&st);
   if (!dev) return st;
   Lease lease(dev);
   HIP_TRY(hipSetDevice(dev->id));
-  DBuf d;
-  HIP_TRY(d.alloc(dev, (2 * n_ins - 1) * 32));
-  HIP_TRY(hipMemcpyAsync(d.p, ins, n_ins * 32, hipMemcpyHostToDevice, lease.s));
-  HIP_TRY(merkle_tree(d.as<uint8_t>(), n_ins, lease.s));
+  DBuf t;
+  HIP_TRY(t.alloc(dev, (2 * n_ins - 1) * 32));
+  HIP_TRY(hipMemcpyAsync(t.p, ins, n_ins * 32, hipMemcpyHostToDevice, lease.s));
+  HIP_TRY(merkle_tree_d((int)d, t.as<uint8_t>(), n_ins, lease.s));
   if (n_ins > 1)
-    HIP_TRY(hipMemcpyAsync(outs, d.as<uint8_t>() + n_ins * 32, (n_ins - 1) * 32, hipMemcpyDeviceToHost,
+    HIP_TRY(hipMemcpyAsync(outs, t.as<uint8_t>() + n_ins * 32, (n_ins - 1) * 32, hipMemcpyDeviceToHost,
                            lease.s));
   HIP_TRY(hipStreamSynchronize(lease.s));
   return LCPC_OK;
@@ -1237,6 +1277,12 @@ lcpc_status lcpc_merkle_tree(const uint8_t *ins, size_t n_ins, uint8_t *outs) {
 
 lcpc_status lcpc_hash_columns(lcpc_field f, const uint64_t *comm, size_t n_rows, size_t n_cols,
                               uint8_t *out) {
+  return lcpc_hash_columns_d(LCPC_DIGEST_BLAKE3, f, comm, n_rows, n_cols, out);
+}
+
+lcpc_status lcpc_hash_columns_d(lcpc_digest d, lcpc_field f, const uint64_t *comm, size_t n_rows, size_t n_cols,
+                                uint8_t *out) {
+  if (!digest_valid((int)d)) return fail(LCPC_ERR_INVALID_ARG, "digest");
   if (!valid_field(f) || !field_gpu_supported(f)) return fail(LCPC_ERR_UNSUPPORTED, "field");
   lcpc_status st;
   Device *dev = current_device(&st);
@@ -1248,7 +1294,7 @@ lcpc_status lcpc_hash_columns(lcpc_field f, const uint64_t *comm, size_t n_rows,
   if ((st = upload(dev, dm, comm, n_rows * n_cols * wb))) return st;
   HIP_TRY(dl.alloc(dev, n_cols * 32));
   HIP_TRY(scratch.alloc(dev, leaf_hash_scratch_bytes(f, n_rows, n_cols)));
-  HIP_TRY(leaf_hashes(f, dm.as<uint32_t>(), n_rows, n_cols, n_cols, dl.as<uint8_t>(), scratch.p, lease.s));
+  HIP_TRY(leaf_hashes_d((int)d, f, dm.as<uint32_t>(), n_rows, n_cols, n_cols, dl.as<uint8_t>(), scratch.p, lease.s));
   HIP_TRY(hipMemcpyAsync(out, dl.p, n_cols * 32, hipMemcpyDeviceToHost, lease.s));
   HIP_TRY(hipStreamSynchronize(lease.s));
   return LCPC_OK;
@@ -1256,6 +1302,12 @@ lcpc_status lcpc_hash_columns(lcpc_field f, const uint64_t *comm, size_t n_rows,
 
 int lcpc_verify_column_path(lcpc_field f, const uint64_t *col, size_t n_rows, const uint8_t *path,
                             size_t path_len, size_t col_num, const uint8_t root[32]) {
+  return lcpc_verify_column_path_d(LCPC_DIGEST_BLAKE3, f, col, n_rows, path, path_len, col_num, root);
+}
+
+int lcpc_verify_column_path_d(lcpc_digest d, lcpc_field f, const uint64_t *col, size_t n_rows, const uint8_t *path,
+                              size_t path_len, size_t col_num, const uint8_t root[32]) {
+  if (!digest_valid((int)d)) return 0;
   if (!valid_field(f) || !field_gpu_supported(f)) return 0;
   lcpc_status st;
   Device *dev = current_device(&st);
@@ -1270,8 +1322,8 @@ int lcpc_verify_column_path(lcpc_field f, const uint64_t *col, size_t n_rows, co
     return 0;
   if (dl.alloc(dev, 32) || dfl.alloc(dev, 4) || scratch.alloc(dev, leaf_hash_scratch_bytes(f, n_rows, 1)))
     return 0;
-  if (leaf_hashes_cols(f, dc.as<uint32_t>(), n_rows, 1, dl.as<uint8_t>(), scratch.p, lease.s) ||
-      path_checks(dl.as<uint8_t>(), dp.as<uint8_t>(), 1, path_len, di.as<uint64_t>(), dr.as<uint8_t>(),
+  if (leaf_hashes_cols_d((int)d, f, dc.as<uint32_t>(), n_rows, 1, dl.as<uint8_t>(), scratch.p, lease.s) ||
+      path_checks_d((int)d, dl.as<uint8_t>(), dp.as<uint8_t>(), 1, path_len, di.as<uint64_t>(), dr.as<uint8_t>(),
                   dfl.as<uint32_t>(), lease.s))
     return 0;
   uint32_t flag = 0;
@@ -1683,6 +1735,7 @@ lcpc_status lcpc_pos_columns(const lcpc_encoding *e, const uint64_t *elems, size
   // CommitRequestType::ColumnsWithoutPath / Leaves (lcpc_online.rs:144-224): encode the file,
   // then return the requested columns and / or their BLAKE3 leaf digests -- no Merkle tree
   if (!e || !elems || len == 0 || (!idx && n)) return fail(LCPC_ERR_INVALID_ARG, "arguments");
+  if (lcpc_status bst = require_blake3(e, "lcpc_pos_columns")) return bst;
   for (size_t k = 0; k < n; k++)
     if (idx[k] >= e->n_cols) return fail(LCPC_PROVER_COLUMN_NUMBER, "ProverError::ColumnNumber");
   Device *dev = e->dev;
@@ -1754,6 +1807,7 @@ lcpc_status lcpc_shard_new_device(const lcpc_encoding *e, const void *d_coeffs, 
 static lcpc_status shard_new_impl(const lcpc_encoding *e, const void *coeffs, bool on_device, size_t row0,
                                   size_t n_shard_rows, size_t n_rows_total, lcpc_shard **out) {
   if (!e || !out || (!coeffs && n_shard_rows)) return fail(LCPC_ERR_INVALID_ARG, "null argument");
+  if (lcpc_status bst = require_blake3(e, "a row shard (its exchange is BLAKE3 chunk chaining values)")) return bst;
   if (e->kind != KIND_RS) return fail(LCPC_ERR_UNSUPPORTED, "row shards: Ligero / R-S encodings only");
   if (row0 + n_shard_rows > n_rows_total) return fail(LCPC_ERR_INVALID_ARG, "shard rows out of range");
   Device *dev = e->dev;

@@ -510,6 +510,7 @@ lcpc_status check_geom(int fid, int kind, size_t n_cols, int G, size_t n_rows) {
 
 lcpc_status check_shardable(const lcpc_encoding *e, lcpc_comm *comm, size_t n_rows) {
   if (!e || !comm) return fail(LCPC_ERR_INVALID_ARG, "null argument");
+  if (lcpc_status bst = require_blake3(e, "the sharded engine (its exchange is BLAKE3 chunk chaining values)")) return bst;
   lcpc_status st = check_geom(e->fid, e->kind, e->n_cols, comm->nranks, n_rows);
   if (st) return st;
   if (comm->dev != e->dev) return fail(LCPC_ERR_INVALID_ARG, "comm and encoding on different devices");
@@ -1391,6 +1392,7 @@ lcpc_status lcpc_sharded_prove(lcpc_sharded_commit *c, const uint64_t *outer, si
   prof::HostScope hs_total("host_sharded_prove_total");
   if (!c || !e || !out || (!outer && outer_len)) return fail(LCPC_ERR_INVALID_ARG, "null argument");
   *out = nullptr;
+  if (lcpc_status bst = require_blake3(e, "the sharded engine (its exchange is BLAKE3 chunk chaining values)")) return bst;
   if (e != c->e && (e->n_per_row != c->np || e->n_cols != c->nc || e->fid != c->fid))
     return fail(LCPC_PROVER_COMMIT, "ProverError::Commit");
   if (outer_len != c->n_rows) return fail(LCPC_PROVER_OUTER_TENSOR, "ProverError::OuterTensor");

@@ -28,6 +28,15 @@ from . import _native as N
 FT63, FT127, FT191, FT255, FT253_192 = 0, 1, 2, 3, 4
 FIELD_NAMES = {FT63: "Ft63", FT127: "Ft127", FT191: "Ft191", FT255: "Ft255", FT253_192: "Ft253_192"}
 
+# lcpc_digest: the reference's D: Digest of LcCommit<D, E> (lcpc-2d/src/lib.rs:174-191)
+BLAKE3, SHA256, SHA3_256, KECCAK256 = 0, 1, 2, 3
+
+
+def digest_name(digest: int) -> Optional[str]:
+    """lcpc_digest_name: "BLAKE3", "SHA-256", "SHA3-256", "Keccak-256"; None for an unknown value."""
+    s = N.load().lcpc_digest_name(digest)
+    return s.decode() if s is not None else None
+
 # status codes (include/lcpc_mi.h)
 PROVER = {1: "TooBig", 2: "Encode", 3: "Commit", 4: "ColumnNumber", 5: "OuterTensor"}
 TRANSCRIPT_CALLBACK = 35  # LCPC_ERR_TRANSCRIPT: a CallerTranscript callback failed
@@ -324,6 +333,17 @@ class LcEncoding:
         _raise(N.load().lcpc_encoding_set_row_kernel(self._h, kernel))
         return self
 
+    def set_digest(self, digest: int):
+        """lcpc_encoding_set_digest: the digest D of commitments made, proved and verified under this
+        encoding (BLAKE3, SHA256, SHA3_256, KECCAK256).  Configuration: set it right after creation.
+        The proof-of-storage and sharded entry points stay BLAKE3-only (LCPC_ERR_UNSUPPORTED)."""
+        _raise(N.load().lcpc_encoding_set_digest(self._h, digest))
+        return self
+
+    @property
+    def digest(self) -> int:
+        return N.load().lcpc_encoding_digest(self._h)
+
     def prepare_thread(self, n_rows: int):
         """Pre-allocate the calling thread's pinned staging for prove (lcpc_prepare_thread)."""
         _raise(N.load().lcpc_prepare_thread(self._h, n_rows))
@@ -617,9 +637,10 @@ class LcCommit:
                         + [_ser_digest(h[i:i + 32]) for i in range(0, len(h), 32)])
 
     @classmethod
-    def from_bincode(cls, field: int, data: bytes) -> "LcCommit":
+    def from_bincode(cls, field: int, data: bytes, digest: int = BLAKE3) -> "LcCommit":
         """serde Deserialize (WrappedLcCommit::unwrap): the fields loaded into HBM
-        (lcpc_commit_from_parts), so prove / open_column work on the result."""
+        (lcpc_commit_from_parts), so prove / open_column work on the result.  digest: the D the
+        hashes were made with (the bytes are the same for every 32-byte D and do not say)."""
         nl = limbs(field)
         r = _Reader(data)
         comm, coeffs = r.vec_f(nl), r.vec_f(nl)
@@ -630,10 +651,18 @@ class LcCommit:
             raise LcpcError(30, "serialized commitment: vector lengths disagree with its dims")
         hp, keep = _bytes_ptr(hashes)
         h = C.c_void_p()
-        _raise(N.load().lcpc_commit_from_parts(field, n_rows, n_cols, n_per_row,
-                                               _p64(np.ascontiguousarray(comm)), _p64(np.ascontiguousarray(coeffs)),
-                                               hp, len(hashes) // 32, C.byref(h)))
+        parts = (field, n_rows, n_cols, n_per_row, _p64(np.ascontiguousarray(comm)), _p64(np.ascontiguousarray(coeffs)),
+                 hp, len(hashes) // 32, C.byref(h))
+        if digest == BLAKE3:
+            _raise(N.load().lcpc_commit_from_parts(*parts))
+        else:
+            _raise(N.load().lcpc_commit_from_parts_d(digest, *parts))
         return cls(h.value, field)
+
+    @property
+    def digest(self) -> int:
+        """the digest the commitment's tree was built with (lcpc_commit_digest)"""
+        return N.load().lcpc_commit_digest(self._h)
 
     def get_n_rows(self) -> int:
         return N.load().lcpc_commit_n_rows(self._h)
@@ -912,27 +941,36 @@ def collapse_columns(field: int, coeffs, tensor, n_rows: int, n_per_row: int) ->
     return out
 
 
-def merkle_tree(ins: bytes) -> bytes:
+def merkle_tree(ins: bytes, digest: int = BLAKE3) -> bytes:
     n = len(ins) // 32
     ip, keep = _bytes_ptr(ins)
     out = (C.c_uint8 * max(32 * (n - 1), 1))()
-    _raise(N.load().lcpc_merkle_tree(ip, n, C.cast(out, N.u8p)))
+    if digest == BLAKE3:
+        _raise(N.load().lcpc_merkle_tree(ip, n, C.cast(out, N.u8p)))
+    else:
+        _raise(N.load().lcpc_merkle_tree_d(digest, ip, n, C.cast(out, N.u8p)))
     return bytes(out)[:32 * (n - 1)]
 
 
-def hash_columns(field: int, comm, n_rows: int, n_cols: int) -> bytes:
+def hash_columns(field: int, comm, n_rows: int, n_cols: int, digest: int = BLAKE3) -> bytes:
     c = _elems(comm, field)
     out = (C.c_uint8 * (32 * n_cols))()
-    _raise(N.load().lcpc_hash_columns(field, _p64(c), n_rows, n_cols, C.cast(out, N.u8p)))
+    if digest == BLAKE3:
+        _raise(N.load().lcpc_hash_columns(field, _p64(c), n_rows, n_cols, C.cast(out, N.u8p)))
+    else:
+        _raise(N.load().lcpc_hash_columns_d(digest, field, _p64(c), n_rows, n_cols, C.cast(out, N.u8p)))
     return bytes(out)
 
 
-def verify_column_path(field: int, column: LcColumn, col_num: int, root: bytes) -> bool:
+def verify_column_path(field: int, column: LcColumn, col_num: int, root: bytes, digest: int = BLAKE3) -> bool:
     c = _elems(column.col, field)
     pb = b"".join(column.path)
     pp, k1 = _bytes_ptr(pb)
     rp, k2 = _bytes_ptr(root)
-    return bool(N.load().lcpc_verify_column_path(field, _p64(c), c.shape[0], pp, len(column.path), col_num, rp))
+    args = (field, _p64(c), c.shape[0], pp, len(column.path), col_num, rp)
+    if digest == BLAKE3:
+        return bool(N.load().lcpc_verify_column_path(*args))
+    return bool(N.load().lcpc_verify_column_path_d(digest, *args))
 
 
 def verify_column_value(field: int, column: LcColumn, tensor, poly_eval) -> bool:
