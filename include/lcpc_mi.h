@@ -876,6 +876,50 @@ lcpc_status lcpc_pos_locate_porenc(const uint8_t *porenc, size_t pre, size_t enc
 lcpc_status lcpc_selftest_pool_ordering(int rounds, uint32_t spin_us, uint64_t *violations,
                                         uint64_t *control_violations, uint64_t *reused);
 
+/* The field primitives every kernel is built from (csrc/field.hpp) and the Ft127 matrix-core
+ * digit recombination (csrc/collapse_mfma.hpp), one call per GPU thread: raw words in, raw words
+ * out, NO range check on the values -- the caller owns the domain, which is the point: a test
+ * can put p - 1, 2p - 1 or an all-ones limb pattern into both operands of one product.  An element
+ * is the field's limbs as everywhere else; a, b and out are host pointers.  R = 2^(64 limbs). */
+typedef enum lcpc_selftest_op {
+  LCPC_SELFTEST_ADD = 0,           /* fe_add: a + b mod p                    (a, b < p) */
+  LCPC_SELFTEST_SUB = 1,           /* fe_sub: a - b mod p                    (a, b < p) */
+  LCPC_SELFTEST_ADD_2P = 2,        /* fe_add_2p: a + b, minus 2p if >= 2p    (a, b < 2p) */
+  LCPC_SELFTEST_SUB_2P = 3,        /* fe_sub_2p: a - b, plus 2p if negative  (a, b < 2p) */
+  LCPC_SELFTEST_REDUCE_2P = 4,     /* fe_reduce_2p: a mod p                  (a < 2p); b unused */
+  LCPC_SELFTEST_SUB_LAZY = 5,      /* fe_sub_lazy: a - b + p mod R           (a, b < p) */
+  LCPC_SELFTEST_MUL_SUB_LAZY = 6,  /* fe_mul(fe_sub_lazy(a[2i], a[2i+1]), b[i]): a holds 2n elements */
+  LCPC_SELFTEST_MUL = 7,           /* fe_mul (product scanning): a b R^-1 mod p  (a < 2p, b < p) */
+  LCPC_SELFTEST_MUL_CIOS = 8,      /* fe_mul_cios: the same                  (a, b < p) */
+  LCPC_SELFTEST_SQR = 9,           /* fe_sqr: a a R^-1 mod p; b unused */
+  LCPC_SELFTEST_MUL_LAZY = 10,     /* fe_mul_lazy: (a b + m p) / R, no final subtraction (a < 2p, b < p) */
+  LCPC_SELFTEST_DOT = 11,          /* fe_dot<k>: sum_q a[ik+q] b[ik+q] R^-1 mod p: a, b hold n k elements */
+  LCPC_SELFTEST_FROM_MONT = 12,    /* fe_from_mont (product scanning): a R^-1 mod p; b unused */
+  LCPC_SELFTEST_FROM_MONT_GENERIC = 13, /* fe_from_mont_generic: (a + m p) / R for any a < R; b unused */
+  LCPC_SELFTEST_TO_MONT = 14,      /* fe_to_mont: a R mod p; b unused */
+  LCPC_SELFTEST_REPR_WORDS = 15,   /* fe_repr_words: to_repr of a Montgomery value as u32 words; b unused */
+  LCPC_SELFTEST_CANON_REPR_WORDS = 16, /* fe_canon_repr_words: the same of a canonical value; b unused */
+  LCPC_SELFTEST_IS_CANONICAL = 17, /* fe_is_canonical: out = 1 if a < p else 0 (any a < R); b unused */
+  LCPC_SELFTEST_POW = 18,          /* fe_pow(a, e), e = the low 64 bits of b[i] */
+  LCPC_SELFTEST_BALANCED_DIGITS = 19, /* Ft127 only: the 16 int8 digits of a < p, digit j in byte j; b unused */
+  LCPC_SELFTEST_N_OPS = 20
+} lcpc_selftest_op;
+
+/* The largest k of LCPC_SELFTEST_DOT for a field (fe_dot_kmax: k p < R); 0 for an unknown field. */
+int lcpc_selftest_fe_dot_kmax(lcpc_field f);
+
+/* out[i] = op(a[i], b[i]) for i < n.  k is fe_dot's number of products (1 for every other op).
+ * LCPC_ERR_INVALID_ARG, before the device is touched: an unknown field or op, k < 1 or
+ * k > lcpc_selftest_fe_dot_kmax(f), LCPC_SELFTEST_BALANCED_DIGITS on another field than Ft127,
+ * a NULL a or out, a NULL b where the op reads b. */
+lcpc_status lcpc_selftest_field_op(lcpc_field f, int op, int k, const uint64_t *a, const uint64_t *b,
+                                   uint64_t *out, size_t n);
+
+/* out[i] (an Ft127 element) = recombine_redc of the 16 digit-position accumulators y[16 i ..]:
+ * (sum_u y_u 2^(8u)) R^-1 mod p, fully reduced, for |y_u| < 2^27.  NULL y or out:
+ * LCPC_ERR_INVALID_ARG. */
+lcpc_status lcpc_selftest_recombine(const int32_t *y, uint64_t *out, size_t n);
+
 /* ------------------------------------------------------------------ kernel timing
  * HIP-event timing of every kernel launch on the handle streams (off by default). */
 void lcpc_prof_enable(int enable);

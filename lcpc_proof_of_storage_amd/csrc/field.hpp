@@ -421,7 +421,7 @@ constexpr int fe_dot_kmax() {
 // sum_k a[k] b[k] R^-1 mod p with ONE reduction (lazy: the K double-width products are added
 // before reducing): K N^2 + N (N - 1) carry-out mads and one final subtraction, instead of K
 // full Montgomery products and K - 1 modular additions.  Requires p = 1 mod 2^32 and
-// K <= fe_dot_kmax<F>() (Ft127: 2, Ft63: 3, Ft255: 2, Ft253_192: 7).
+// K <= fe_dot_kmax<F>() (Ft63: 3, Ft127: 2, Ft191: 3, Ft255: 2, Ft253_192: 8, whose p < 2^253).
 template <class F, int K>
 __device__ __forceinline__ Fe<F> fe_dot(const Fe<F>* a, const Fe<F>* b) {
   constexpr int N = F::N;

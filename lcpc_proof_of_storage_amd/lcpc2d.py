@@ -150,6 +150,51 @@ def selftest_pool_ordering(rounds: int = 8, spin_us: int = 300) -> dict:
     return {"violations": v.value, "control_violations": cv.value, "reused": r.value}
 
 
+# lcpc_selftest_op (include/lcpc_mi.h)
+SELFTEST_OPS = {name: i for i, name in enumerate([
+    "add", "sub", "add_2p", "sub_2p", "reduce_2p", "sub_lazy", "mul_sub_lazy", "mul", "mul_cios", "sqr",
+    "mul_lazy", "dot", "from_mont", "from_mont_generic", "to_mont", "repr_words", "canon_repr_words",
+    "is_canonical", "pow", "balanced_digits"])}
+_SELFTEST_UNARY = {"reduce_2p", "sqr", "from_mont", "from_mont_generic", "to_mont", "repr_words",
+                   "canon_repr_words", "is_canonical", "balanced_digits"}
+
+
+def selftest_fe_dot_kmax(field: int) -> int:
+    """fe_dot_kmax of the field: the most products one lazy reduction may sum (0: unknown field)."""
+    return N.load().lcpc_selftest_fe_dot_kmax(field)
+
+
+def selftest_field_op(field: int, op: str, a, b=None, k: int = 1) -> np.ndarray:
+    """One field.hpp primitive per GPU thread on raw element words (lcpc_selftest_field_op): no
+    range check, the caller owns the domain.  a and b are uint64 arrays of whole elements;
+    "mul_sub_lazy" reads two elements of a per output, "dot" k of a and of b; a unary op takes no
+    b.  Returns the (n, limbs) output words."""
+    nl = limbs(field)
+    a = _elems(a, field)
+    per = 2 if op == "mul_sub_lazy" else k if op == "dot" else 1
+    if per < 1 or len(a) % per:
+        raise ValueError("a does not hold a whole number of operand tuples")
+    n = len(a) // per
+    pb = None
+    if op not in _SELFTEST_UNARY:
+        b = _elems(b, field)
+        if len(b) != n * (k if op == "dot" else 1):
+            raise ValueError("b does not match a")
+        pb = _p64(b)
+    out = np.zeros((n, nl), np.uint64)
+    _raise(N.load().lcpc_selftest_field_op(field, SELFTEST_OPS[op], k, _p64(a), pb, _p64(out), n))
+    return out
+
+
+def selftest_recombine(y) -> np.ndarray:
+    """recombine_redc of collapse_mfma.hpp per GPU thread (lcpc_selftest_recombine): y is int32
+    of shape (n, 16), the digit-position accumulators; returns the (n, 2) Ft127 words."""
+    y = np.ascontiguousarray(y, dtype=np.int32).reshape(-1, 16)
+    out = np.zeros((len(y), 2), np.uint64)
+    _raise(N.load().lcpc_selftest_recombine(y.ctypes.data_as(C.POINTER(C.c_int32)), _p64(out), len(y)))
+    return out
+
+
 def set_device(device: int):
     _raise(N.load().lcpc_set_device(device), DeviceError)
 

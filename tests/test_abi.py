@@ -177,6 +177,8 @@ def test_compute_fails_loudly_without_device(api):
         lambda: api.merkle_tree(bytes(32 * 4)),
         lambda: api.collapse_columns(1, np.zeros(16, np.uint64), np.zeros(2, np.uint64), 2, 4),
         lambda: api.hash_columns(1, np.zeros(16, np.uint64), 2, 4),
+        lambda: api.selftest_field_op(1, "mul", np.zeros(2, np.uint64), np.zeros(2, np.uint64)),
+        lambda: api.selftest_recombine(np.zeros(16, np.int32)),
     ]
     for fn in calls:
         with pytest.raises(api.DeviceError):
