@@ -35,7 +35,9 @@ extern "C" {
  * error location block (lcpc_rs_locate_*, lcpc_rs_decode_rows, lcpc_pos_locate_porenc) is additive
  * within version 3: new symbols only, nothing existing changed.  So is the digest block (lcpc_digest,
  * lcpc_encoding_set_digest, lcpc_commit_digest and the *_d functions): every existing symbol keeps
- * its signature and its BLAKE3 meaning. */
+ * its signature and its BLAKE3 meaning.  So is the update-audit block (lcpc_eval_poly*,
+ * lcpc_pos_eval_poly_bytes*, lcpc_pos_left_multiply_bytes*, lcpc_pos_update_rows,
+ * lcpc_pos_update_evaluation). */
 #define LCPC_ABI_VERSION 3
 
 typedef enum lcpc_status {
@@ -452,6 +454,61 @@ lcpc_status lcpc_verify_column_values(lcpc_field f, const uint64_t *cols, size_t
 lcpc_status lcpc_pos_columns(const lcpc_encoding *e, const uint64_t *elems, size_t len,
                              const uint64_t *idx, size_t n, uint64_t *cols_out,
                              uint8_t *leaves_out);
+
+/* ------------------------------------------------------------------ PoS update audits
+ * The evaluation request that follows an edit, an append or a reshape (messages: networking/
+ * shared.rs:90-129, 165-188; server: networking/server.rs:833-906, 963-1077; client checks:
+ * networking/client.rs:755-827, 1009-1135, 1273-1420).  Additive within version 3.  Elements are
+ * Montgomery limbs as everywhere; a file image is WriteableFt63, 7 bytes per element, and its
+ * entries are BLAKE3-only like the other PoS entries (LCPC_ERR_UNSUPPORTED for another digest). */
+/* evaluate_field_polynomial_at_point[_with_elevated_degree] (fields.rs:160-186):
+ * out = sum_{i<n} coeffs[i] x^(i + degree_offset), one element; n = 0 gives zero; x^0 = 1 also for
+ * x = 0.  One streaming pass over the coefficients, no power vector. */
+lcpc_status lcpc_eval_poly(lcpc_field f, const uint64_t *coeffs, size_t n, const uint64_t *x,
+                           uint64_t degree_offset, uint64_t *out);
+/* the same from device coefficients (8-byte aligned) */
+lcpc_status lcpc_eval_poly_device(lcpc_field f, const void *d_coeffs, size_t n, const uint64_t *x,
+                                  uint64_t degree_offset, uint64_t *out);
+/* the same over convert_byte_vec_to_field_elements_vec(bytes) (fields.rs:109-112): ceil(n_bytes / 7)
+ * coefficients read straight from the bytes, no element image.  Host bytes of any alignment go up in
+ * blocks of LCPC_POS_EVAL_STAGE_BYTES, each block evaluated as it lands, elevated by the index of its
+ * first element. */
+#define LCPC_POS_EVAL_STAGE_BYTES ((size_t)7 << 20)
+lcpc_status lcpc_pos_eval_poly_bytes(const uint8_t *bytes, size_t n_bytes, const uint64_t *x,
+                                     uint64_t degree_offset, uint64_t *out);
+/* the same from a device file image (8-byte aligned) */
+lcpc_status lcpc_pos_eval_poly_bytes_device(const void *d_bytes, size_t n_bytes, const uint64_t *x,
+                                            uint64_t degree_offset, uint64_t *out);
+/* left_multiply_unencoded_matrix_by_vector (file_handler.rs:614-638) without an element image:
+ * out[c] = sum_r left[r] M[r][c], c < pre, over the file's rows of pre elements (the last row zero
+ * padded); n_left must be the row count ceil(ceil(n_bytes / 7) / pre), else LCPC_ERR_INVALID_ARG.
+ * pre a power of two >= 8 reads the bytes directly; other widths pack first. */
+lcpc_status lcpc_pos_left_multiply_bytes(const uint8_t *bytes, size_t n_bytes, size_t pre,
+                                         const uint64_t *left, size_t n_left, uint64_t *out);
+lcpc_status lcpc_pos_left_multiply_bytes_device(const void *d_bytes, size_t n_bytes, size_t pre,
+                                                const uint64_t *left, size_t n_left, uint64_t *out);
+/* Host-only, no device (like lcpc_pos_update_chunk_range): the rows an update touches.  The
+ * reference's edit and append handlers (networking/server.rs:963-1077) each pick their "original
+ * rows" differently and disagree with their clients; this is the one rule that replaces them.
+ * An update writes `len` bytes at `offset` into a file of old_len bytes, offset <= old_len
+ * (offset == old_len is an append; offset + len > old_len extends the file).
+ * *row_lo = offset / (7 pre);  *row_hi = one past the last row of the NEW file that holds a
+ * changed byte;  [*old_lo, *old_hi) = the OLD file's bytes of those rows, clipped to old_len
+ * (empty for an append that starts a fresh row).  len == 0 or offset > old_len: INVALID_ARG. */
+lcpc_status lcpc_pos_update_rows(size_t old_len, size_t offset, size_t len, size_t pre,
+                                 size_t *row_lo, size_t *row_hi, size_t *old_lo, size_t *old_hi);
+/* One update audit's GPU half (networking/server.rs:833-906, 963-1077): both images are committed
+ * (lcpc_pos_commit_eval_bytes_device each, left = [1, x^pre, x^2pre, ...] over the commitment's rows,
+ * its own pre), and both sets of columns are opened with paths.  For a reshape the two images are
+ * the same pointer, the encodings differ, and *expected_eval (else NULL) = the file polynomial at x.
+ * result_* : n_cols elements; cols_* : n_idx x n_rows; paths_* : n_idx x log2(n_cols) x 32 B. */
+lcpc_status lcpc_pos_update_evaluation(
+    const lcpc_encoding *e_old, const void *d_old, size_t n_old,
+    const lcpc_encoding *e_new, const void *d_new, size_t n_new, const uint64_t *x,
+    const uint64_t *idx_old, size_t n_idx_old, const uint64_t *idx_new, size_t n_idx_new,
+    uint64_t *result_old, uint64_t *cols_old, uint8_t *paths_old, uint8_t root_old[32],
+    uint64_t *result_new, uint64_t *cols_new, uint8_t *paths_new, uint8_t root_new[32],
+    uint64_t *expected_eval);
 
 /* ------------------------------------------------------------------ PoS encoded files
  * (proof-of-storage/src/lcpc_online/encoded_file_{writer,reader}.rs, WriteableFt63).

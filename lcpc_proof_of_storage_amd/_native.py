@@ -163,6 +163,15 @@ SIGNATURES = {
     "lcpc_ifft_oi_rows": (i32, [i32, u64p, sz, sz]),
     "lcpc_open_columns": (i32, [vp, u64p, sz, u64p, u8p]),
     "lcpc_pos_columns": (i32, [vp, u64p, sz, u64p, sz, u64p, u8p]),
+    "lcpc_eval_poly": (i32, [i32, u64p, sz, u64p, C.c_uint64, u64p]),
+    "lcpc_eval_poly_device": (i32, [i32, vp, sz, u64p, C.c_uint64, u64p]),
+    "lcpc_pos_eval_poly_bytes": (i32, [vp, sz, u64p, C.c_uint64, u64p]),
+    "lcpc_pos_eval_poly_bytes_device": (i32, [vp, sz, u64p, C.c_uint64, u64p]),
+    "lcpc_pos_left_multiply_bytes": (i32, [vp, sz, sz, u64p, sz, u64p]),
+    "lcpc_pos_left_multiply_bytes_device": (i32, [vp, sz, sz, u64p, sz, u64p]),
+    "lcpc_pos_update_rows": (i32, [sz, sz, sz, sz, szp, szp, szp, szp]),
+    "lcpc_pos_update_evaluation": (i32, [vp, vp, sz, vp, vp, sz, u64p, u64p, sz, u64p, sz,
+                                         u64p, u64p, u8p, u8p, u64p, u64p, u8p, u8p, u64p]),
     "lcpc_hash_field_columns": (i32, [i32, u64p, sz, sz, u8p]),
     "lcpc_verify_leaf_paths": (i32, [u8p, u8p, sz, sz, u64p, u8p, u8p]),
     "lcpc_verify_column_values": (i32, [i32, u64p, sz, sz, u64p, u64p, sz, u64p, u8p]),

@@ -1765,6 +1765,227 @@ lcpc_status lcpc_pos_columns(const lcpc_encoding *e, const uint64_t *elems, size
 
 }  // extern "C"
 
+// ================================================================= update audits (pos_eval.hip)
+namespace {
+
+// sum_{i<n} c_i x^(i + d) from a device source (elements of field f, or with n_bytes a file image)
+lcpc_status eval_poly_dev(Device *dev, hipStream_t s, int f, const void *d_src, size_t n, size_t n_bytes,
+                          const uint64_t *x, uint64_t d, uint64_t *out) {
+  const int wb = field_bytes(f);
+  DBuf dx, dout, scratch;
+  lcpc_status st;
+  if ((st = upload(dev, dx, x, wb))) return st;
+  HIP_TRY(dout.alloc(dev, wb));
+  HIP_TRY(scratch.alloc(dev, poly_eval_scratch_bytes(f, n)));
+  HIP_TRY(poly_eval(f, d_src, n, n_bytes, dx.as<uint32_t>(), d, dout.as<uint32_t>(), scratch.p, s));
+  HIP_TRY(hipMemcpyAsync(out, dout.p, wb, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return LCPC_OK;
+}
+
+lcpc_status eval_poly_args(lcpc_field f, const void *coeffs, size_t n, const uint64_t *x, uint64_t *out) {
+  if (!valid_field(f) || !x || !out || (!coeffs && n)) return fail(LCPC_ERR_INVALID_ARG, "polynomial evaluation arguments");
+  if (!field_gpu_supported(f)) return fail(LCPC_ERR_UNSUPPORTED, "field has no gfx950 kernels");
+  return LCPC_OK;
+}
+
+// u^T M over a device file image: rows of pre elements, left (host) of n_left = the row count
+lcpc_status left_multiply_dev(Device *dev, hipStream_t s, const uint8_t *d_bytes, size_t n_bytes, size_t pre,
+                              const uint64_t *left, size_t n_left, uint64_t *out) {
+  const size_t len = (n_bytes + 6) / 7, n_rows = (len + pre - 1) / pre;
+  if (n_left != n_rows) return fail(LCPC_ERR_INVALID_ARG, "left vector length != the file's row count");
+  DBuf dl, dout, scratch, m;
+  lcpc_status st;
+  if ((st = upload(dev, dl, left, n_rows * 8))) return st;
+  HIP_TRY(dout.alloc(dev, pre * 8));
+  if (pos_left_mul_bytes_ok(pre)) {
+    HIP_TRY(scratch.alloc(dev, pos_left_mul_bytes_scratch_bytes(pre, n_rows)));
+    HIP_TRY(pos_left_mul_bytes(d_bytes, n_bytes, pre, n_rows, dl.as<uint32_t>(), dout.as<uint32_t>(), scratch.p, s));
+  } else {
+    // other widths: the element image (zero padded to whole rows), then the commitment's collapse
+    HIP_TRY(m.alloc(dev, n_rows * pre * 8));
+    if (n_rows * pre > len) HIP_TRY(hipMemsetAsync(m.as<uint64_t>() + len, 0, (n_rows * pre - len) * 8, s));
+    HIP_TRY(pos_pack7(d_bytes, n_bytes, m.as<uint64_t>(), s));
+    HIP_TRY(scratch.alloc(dev, collapse_scratch_bytes(LCPC_FT63, n_rows, pre, 1)));
+    HIP_TRY(collapse_rows(LCPC_FT63, m.as<uint32_t>(), n_rows, pre, dl.as<uint32_t>(), 1, dout.as<uint32_t>(), scratch.p,
+                          s));
+  }
+  HIP_TRY(hipMemcpyAsync(out, dout.p, pre * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return LCPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+lcpc_status lcpc_eval_poly(lcpc_field f, const uint64_t *coeffs, size_t n, const uint64_t *x, uint64_t degree_offset,
+                           uint64_t *out) {
+  lcpc_status st = eval_poly_args(f, coeffs, n, x, out);
+  if (st) return st;
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  DBuf dc;
+  if ((st = upload(dev, dc, coeffs, n * field_bytes(f)))) return st;
+  return eval_poly_dev(dev, lease.s, f, dc.p, n, 0, x, degree_offset, out);
+}
+
+lcpc_status lcpc_eval_poly_device(lcpc_field f, const void *d_coeffs, size_t n, const uint64_t *x,
+                                  uint64_t degree_offset, uint64_t *out) {
+  lcpc_status st = eval_poly_args(f, d_coeffs, n, x, out);
+  if (st) return st;
+  if ((uintptr_t)d_coeffs & 7) return fail(LCPC_ERR_INVALID_ARG, "device coefficients must be 8-byte aligned");
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  return eval_poly_dev(dev, lease.s, f, d_coeffs, n, 0, x, degree_offset, out);
+}
+
+lcpc_status lcpc_pos_eval_poly_bytes_device(const void *d_bytes, size_t n_bytes, const uint64_t *x,
+                                            uint64_t degree_offset, uint64_t *out) {
+  lcpc_status st = eval_poly_args(LCPC_FT63, d_bytes, n_bytes, x, out);
+  if (st) return st;
+  if ((uintptr_t)d_bytes & 7) return fail(LCPC_ERR_INVALID_ARG, "device file image must be 8-byte aligned");
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  return eval_poly_dev(dev, lease.s, LCPC_FT63, d_bytes, (n_bytes + 6) / 7, n_bytes, x, degree_offset, out);
+}
+
+lcpc_status lcpc_pos_eval_poly_bytes(const uint8_t *bytes, size_t n_bytes, const uint64_t *x, uint64_t degree_offset,
+                                     uint64_t *out) {
+  lcpc_status st = eval_poly_args(LCPC_FT63, bytes, n_bytes, x, out);
+  if (st) return st;
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  hipStream_t s = lease.s;
+  // The image goes up in staging blocks of whole tiles; block b's polynomial is evaluated as soon
+  // as it has landed, elevated by the index of its first element, and the values are summed at the
+  // end: x^degree_offset multiplies the sum (start + degree_offset could pass 2^64).
+  constexpr size_t BLOCK = LCPC_POS_EVAL_STAGE_BYTES;
+  static_assert(BLOCK % (7 * (size_t)POS_EVAL_TILE) == 0 && BLOCK % 16 == 0, "staging blocks of whole tiles");
+  const size_t nb = (n_bytes + BLOCK - 1) / BLOCK;
+  DBuf image, dx, vals, dout, scratch;
+  if ((st = upload(dev, dx, x, 8))) return st;
+  HIP_TRY(dout.alloc(dev, 8));
+  HIP_TRY(vals.alloc(dev, std::max<size_t>(nb, 1) * 8));
+  HIP_TRY(image.alloc(dev, n_bytes));
+  const size_t sb = (poly_eval_scratch_bytes(LCPC_FT63, BLOCK / 7) + 255) & ~(size_t)255;
+  HIP_TRY(scratch.alloc(dev, std::max<size_t>(nb, 1) * sb));
+  st = h2d_blocks(dev, image.as<uint8_t>(), bytes, n_bytes, BLOCK, s, [&](size_t off, size_t n) -> lcpc_status {
+    const size_t b = off / BLOCK;
+    HIP_TRY(poly_eval(LCPC_FT63, image.as<uint8_t>() + off, (n + 6) / 7, n, dx.as<uint32_t>(), (uint64_t)(off / 7),
+                      vals.as<uint32_t>() + 2 * b, scratch.as<uint8_t>() + b * sb, s));
+    return LCPC_OK;
+  });
+  if (st) return st;
+  HIP_TRY(poly_eval_sum_scale(LCPC_FT63, vals.as<uint32_t>(), nb, dx.as<uint32_t>(), degree_offset, dout.as<uint32_t>(), s));
+  HIP_TRY(hipMemcpyAsync(out, dout.p, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return LCPC_OK;
+}
+
+lcpc_status lcpc_pos_left_multiply_bytes_device(const void *d_bytes, size_t n_bytes, size_t pre, const uint64_t *left,
+                                                size_t n_left, uint64_t *out) {
+  if (!d_bytes || !n_bytes || !pre || !left || !out) return fail(LCPC_ERR_INVALID_ARG, "null or empty argument");
+  if ((uintptr_t)d_bytes & 7) return fail(LCPC_ERR_INVALID_ARG, "device file image must be 8-byte aligned");
+  lcpc_status st;
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  return left_multiply_dev(dev, lease.s, (const uint8_t *)d_bytes, n_bytes, pre, left, n_left, out);
+}
+
+lcpc_status lcpc_pos_left_multiply_bytes(const uint8_t *bytes, size_t n_bytes, size_t pre, const uint64_t *left,
+                                         size_t n_left, uint64_t *out) {
+  if (!bytes || !n_bytes || !pre || !left || !out) return fail(LCPC_ERR_INVALID_ARG, "null or empty argument");
+  lcpc_status st;
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  DBuf image;
+  HIP_TRY(image.alloc(dev, n_bytes));
+  st = h2d_blocks(dev, image.as<uint8_t>(), bytes, n_bytes, (size_t)8 << 20, lease.s,
+                  [](size_t, size_t) { return LCPC_OK; });
+  if (st) return st;
+  return left_multiply_dev(dev, lease.s, image.as<uint8_t>(), n_bytes, pre, left, n_left, out);
+}
+
+lcpc_status lcpc_pos_update_rows(size_t old_len, size_t offset, size_t len, size_t pre, size_t *row_lo, size_t *row_hi,
+                                 size_t *old_lo, size_t *old_hi) {
+  if (!len || offset > old_len || !pre || !row_lo || !row_hi || !old_lo || !old_hi)
+    return fail(LCPC_ERR_INVALID_ARG, "update: len == 0, offset > old_len, pre == 0 or a null result");
+  if (pre > SIZE_MAX / 7 || len > SIZE_MAX - offset || offset + len > SIZE_MAX - 7 * pre)
+    return fail(LCPC_ERR_INVALID_ARG, "update: range overflows");
+  const size_t row_b = 7 * pre;
+  *row_lo = offset / row_b;
+  *row_hi = (offset + len - 1) / row_b + 1;
+  *old_lo = std::min(*row_lo * row_b, old_len);
+  *old_hi = std::min(*row_hi * row_b, old_len);
+  return LCPC_OK;
+}
+
+lcpc_status lcpc_pos_update_evaluation(const lcpc_encoding *e_old, const void *d_old, size_t n_old,
+                                       const lcpc_encoding *e_new, const void *d_new, size_t n_new, const uint64_t *x,
+                                       const uint64_t *idx_old, size_t n_idx_old, const uint64_t *idx_new,
+                                       size_t n_idx_new, uint64_t *result_old, uint64_t *cols_old, uint8_t *paths_old,
+                                       uint8_t root_old[32], uint64_t *result_new, uint64_t *cols_new,
+                                       uint8_t *paths_new, uint8_t root_new[32], uint64_t *expected_eval) {
+  if (!e_old || !e_new || !d_old || !d_new || !n_old || !n_new || !x || !result_old || !result_new || !root_old ||
+      !root_new)
+    return fail(LCPC_ERR_INVALID_ARG, "null or empty argument");
+  lcpc_status st;
+  if ((st = require_blake3(e_old, "an update audit")) || (st = require_blake3(e_new, "an update audit"))) return st;
+  if (e_old->fid != LCPC_FT63 || e_new->fid != LCPC_FT63)
+    return fail(LCPC_ERR_INVALID_ARG, "update audit: WriteableFt63 encodings only");
+  struct Side {
+    const lcpc_encoding *e;
+    const void *d;
+    size_t n;
+    const uint64_t *idx;
+    size_t n_idx;
+    uint64_t *result, *cols;
+    uint8_t *paths, *root;
+  } sides[2] = {{e_old, d_old, n_old, idx_old, n_idx_old, result_old, cols_old, paths_old, root_old},
+                {e_new, d_new, n_new, idx_new, n_idx_new, result_new, cols_new, paths_new, root_new}};
+  for (const Side &sd : sides) {
+    // left = [1, x^pre, x^(2 pre), ...] over this commitment's rows: the value is the file polynomial's
+    const size_t pre = sd.e->n_per_row;
+    if (!pre) return fail(LCPC_ERR_INVALID_ARG, "encoding without dims");
+    const size_t n_rows = ((sd.n + 6) / 7 + pre - 1) / pre;
+    std::vector<uint64_t> left(n_rows);
+    {
+      Device *dev = sd.e->dev;
+      Lease lease(dev, POOL_HIGH);
+      HIP_TRY(hipSetDevice(dev->id));
+      DBuf dx, dl;
+      if ((st = upload(dev, dx, x, 8))) return st;
+      HIP_TRY(dl.alloc(dev, n_rows * 8));
+      HIP_TRY(powers(LCPC_FT63, dx.as<uint32_t>(), (uint64_t)pre, n_rows, dl.as<uint32_t>(), lease.s));
+      HIP_TRY(hipMemcpyAsync(left.data(), dl.p, n_rows * 8, hipMemcpyDeviceToHost, lease.s));
+      HIP_TRY(hipStreamSynchronize(lease.s));
+    }
+    lcpc_commit *c = nullptr;
+    if ((st = lcpc_pos_commit_eval_bytes_device(sd.e, sd.d, sd.n, left.data(), n_rows, sd.result, &c))) return st;
+    st = lcpc_open_columns(c, sd.idx, sd.n_idx, sd.cols, sd.paths);
+    std::memcpy(sd.root, c->root, 32);
+    lcpc_commit_free(c);
+    if (st) return st;
+  }
+  if (expected_eval) return lcpc_pos_eval_poly_bytes_device(d_new, n_new, x, 0, expected_eval);
+  return LCPC_OK;
+}
+
+}  // extern "C"
+
 // ================================================================= row shards (multi-GPU commit)
 // One GPU's share of a Ligero commitment whose rows are split across processes:
 // the shard encodes its rows, computes the BLAKE3 chunk chaining values of the leaf-message

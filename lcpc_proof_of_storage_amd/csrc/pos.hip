@@ -16,25 +16,18 @@
 #include "field.hpp"
 #include "kernels.hpp"
 #include "pos.hpp"
+#include "pos_bytes.hpp"
 #include "prof.hpp"
 
 namespace lcpc {
 
 namespace {
 
-// element k = bits [56k, 56k + 56) of the 448-bit little-endian run q
-__device__ __forceinline__ uint64_t pack7_elem(const uint64_t q[7], int k) {
-  const int bit = 56 * k, wi = bit >> 6, sh = bit & 63;
-  uint64_t v = q[wi] >> sh;
-  if (sh > 8 && wi + 1 < 7) v |= q[wi + 1] << (64 - sh);
-  return v & 0x00ffffffffffffffull;
-}
-
 // A block packs 2048 elements (14336 bytes): the bytes come in as coalesced 16-byte loads into
 // LDS, each thread unpacks its 56-byte run from there, and the 16 KiB of elements go out through
 // LDS again as coalesced 16-byte stores (a lane's 7 and 8 u64 accesses straight to memory are
 // 56 and 64 bytes apart across the wave).  A partial last block takes the per-thread path.
-constexpr int PACK_EL = 2048, PACK_BYTES = 7 * PACK_EL;
+// (pack7_elem, PACK_EL, PACK_BYTES: pos_bytes.hpp)
 __global__ __launch_bounds__(256) void k_pack7(const uint8_t *__restrict__ bytes, size_t n_bytes,
                                                uint64_t *__restrict__ out, size_t n_elems) {
   __shared__ __align__(16) uint64_t s_in[PACK_BYTES / 8];

@@ -19,4 +19,23 @@ hipError_t bitrev_scale(int fid, const uint32_t *in, uint32_t *out, int log_n, s
 hipError_t powers(int fid, const uint32_t *base, uint64_t step_exp, size_t n, uint32_t *dst,
                   hipStream_t s);
 
+// ---- pos_eval.hip
+// coefficients per block of the polynomial evaluation (every power of it is a reduction level)
+constexpr int POS_EVAL_TILE = 2048;
+// out[0] = sum_{i<n} c_i x^(i + d) (n = 0: zero).  n_bytes == 0: src = n elements of field fid;
+// else src = a WriteableFt63 file image of n_bytes bytes (fid 0, n = ceil(n_bytes / 7), 8-byte
+// aligned).  x, out: device, one Montgomery element each.
+size_t poly_eval_scratch_bytes(int fid, size_t n);
+hipError_t poly_eval(int fid, const void *src, size_t n, size_t n_bytes, const uint32_t *x, uint64_t d,
+                     uint32_t *out, void *scratch, hipStream_t s);
+// out[0] = (vals[0] + ... + vals[nb - 1]) * x^d
+hipError_t poly_eval_sum_scale(int fid, const uint32_t *vals, size_t nb, const uint32_t *x, uint64_t d,
+                               uint32_t *out, hipStream_t s);
+// out[c] = sum_r left[r] * M[r][c], c < pre, M the image's rows of pre elements (7 bytes each, the
+// last row zero padded); pre a power of two >= 8 (pos_left_mul_bytes_ok), bytes 8-byte aligned
+bool pos_left_mul_bytes_ok(size_t pre);
+size_t pos_left_mul_bytes_scratch_bytes(size_t pre, size_t n_rows);
+hipError_t pos_left_mul_bytes(const uint8_t *bytes, size_t n_bytes, size_t pre, size_t n_rows, const uint32_t *left,
+                              uint32_t *out, void *scratch, hipStream_t s);
+
 }  // namespace lcpc

@@ -41,7 +41,9 @@ def digest_name(digest: int) -> Optional[str]:
 PROVER = {1: "TooBig", 2: "Encode", 3: "Commit", 4: "ColumnNumber", 5: "OuterTensor"}
 TRANSCRIPT_CALLBACK = 35  # LCPC_ERR_TRANSCRIPT: a CallerTranscript callback failed
 VERIFIER = {10: "NumColOpens", 11: "ColumnPath", 12: "ColumnEval", 13: "ColumnDegree", 14: "OuterTensor",
-            15: "InnerTensor", 16: "EncodingDims", 17: "Encode"}
+            15: "InnerTensor", 16: "EncodingDims", 17: "Encode",
+            # the update audit's client-side verdicts (pos.py): raised in Python, no C status
+            40: "UpdateMismatch", 41: "RowsMismatch", 42: "ReshapeMismatch"}
 FFT = {20: "NotPowerOfTwo", 21: "TooBig", 22: "WrongSizePrecomp"}
 
 

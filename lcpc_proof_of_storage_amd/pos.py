@@ -395,25 +395,30 @@ def vector_multiply(a, b, field: int = FT63) -> np.ndarray:
 
 def evaluate_field_polynomial_at_point_with_elevated_degree(field_elements, point, degree_offset: int,
                                                             field: int = FT63) -> np.ndarray:
-    """fields.rs:172-186: sum_i c_i x^(i + degree_offset), on the GPU (the powers from
-    lcpc_pos_side_vectors, the sum a one-column collapse)."""
+    """fields.rs:172-186: sum_i c_i x^(i + degree_offset), one streaming pass on the GPU
+    (lcpc_eval_poly: no power vector is formed)."""
     nl = limbs(field)
     c = np.ascontiguousarray(field_elements, dtype=np.uint64).reshape(-1, nl)
-    n = c.shape[0]
-    if n == 0:
-        return np.zeros((1, nl), np.uint64)
-    # left = [1, x^d] (n_rows 2, n_cols d) gives x^d; right = [1, x, ..., x^(n-1)]
-    _, right = form_side_vectors_for_polynomial_evaluation_from_point(point, 1, n, field)
-    v = field_dot(c, right, field)
-    if degree_offset:
-        left, _ = form_side_vectors_for_polynomial_evaluation_from_point(point, 2, degree_offset, field)
-        v = field_dot(v, left[1], field)
-    return v
+    x = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1)[:nl].copy()
+    out = np.zeros((1, nl), np.uint64)
+    _raise(N.load().lcpc_eval_poly(field, _p64(c) if c.size else None, c.shape[0], _p64(x), degree_offset, _p64(out)))
+    return out
 
 
 def evaluate_field_polynomial_at_point(field_elements, point, field: int = FT63) -> np.ndarray:
     """fields.rs:160-170: sum_i c_i x^i (coefficients little-endian: c_0 first)."""
     return evaluate_field_polynomial_at_point_with_elevated_degree(field_elements, point, 0, field)
+
+
+def evaluate_bytes_polynomial_at_point(data, point, degree_offset: int = 0) -> np.ndarray:
+    """The same over convert_byte_vec_to_field_elements_vec(data), read straight from the bytes
+    (lcpc_pos_eval_poly_bytes; bytes-like or a uint8 array of any alignment)."""
+    a = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.asarray(data, np.uint8)
+    x = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1)[:1].copy()
+    out = np.zeros((1, 1), np.uint64)
+    _raise(N.load().lcpc_pos_eval_poly_bytes(a.ctypes.data if a.size else None, a.size, _p64(x), degree_offset,
+                                             _p64(out)))
+    return out
 
 
 def server_retreive_columns(comm: LcCommit, requested_columns: Sequence[int]) -> List[LcColumn]:
@@ -613,13 +618,259 @@ def verify_full_polynomial_evaluation_wrapper_with_single_eval_point(
 
 def left_multiply_unencoded_matrix_by_vector(data: bytes, pre_encoded_size: int, left_vector) -> np.ndarray:
     """file_handler.rs:614-638: u^T M over the file's unencoded rows (7 bytes per element, rows of
-    pre_encoded_size).  The reference returns an empty vector (its result is `with_capacity`
-    and never resized); this returns the sum it is written to accumulate."""
-    el = convert_byte_vec_to_field_elements_vec(data).reshape(-1)
-    n_rows = -(-el.size // pre_encoded_size)
+    pre_encoded_size), read straight from the bytes (lcpc_pos_left_multiply_bytes).  The reference
+    returns an empty vector (its result is `with_capacity` and never resized); this
+    returns the sum it is written to accumulate."""
+    a = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.asarray(data, np.uint8)
+    n_rows = -(-(-(-a.size // DATA_BYTE_CAPACITY)) // pre_encoded_size)
     left = np.ascontiguousarray(np.asarray(left_vector, dtype=np.uint64).reshape(-1))
     if left.size != n_rows:
         raise ValueError(f"left_vector incorrect size, expected {n_rows} and received {left.size}")
-    m = np.zeros(n_rows * pre_encoded_size, np.uint64)
-    m[:el.size] = el
-    return collapse_columns(FT63, m, left, n_rows, pre_encoded_size)
+    out = np.zeros((pre_encoded_size, 1), np.uint64)
+    _raise(N.load().lcpc_pos_left_multiply_bytes(a.ctypes.data, a.size, pre_encoded_size, _p64(left), left.size,
+                                                 _p64(out)))
+    return out
+
+
+# ---------------------------------------------------------------- update audits
+# The evaluation request after an edit, an append or a reshape (messages: networking/shared.rs:90-129,
+# 165-188; server: networking/server.rs:833-906, 963-1077; client: networking/client.rs:755-827,
+# 1009-1135, 1273-1420).  Restated where the reference is inconsistent (DESIGN.md §5d): the rows an
+# update touches follow the single rule of lcpc_pos_update_rows, the client checks the opened
+# columns against both roots and the touched rows against its own bytes, and a no-op edit passes.
+FT63_MODULUS = 5102708120182849537  # lcpc-test-fields/src/lib.rs:18-22
+EVAL_POLY_TILE = 2048               # coefficients per block of the evaluation kernel (pos.hpp)
+EVAL_STAGE_BYTES = 7 << 20          # LCPC_POS_EVAL_STAGE_BYTES
+
+
+@dataclass
+class ReshapeEvaluation:
+    """ServerMessages::ReshapeEvaluation (shared.rs:165-171)."""
+    expected_result: np.ndarray
+    original_result_vector: np.ndarray
+    original_columns: List[LcColumn]
+    new_result_vector: np.ndarray
+    new_columns: List[LcColumn]
+    original_root: bytes = b""   # not part of the message: the roots the server computed
+    new_root: bytes = b""
+
+
+@dataclass
+class UpdateEvaluation:
+    """ServerMessages::EditEvaluation / AppendEvaluation (shared.rs:172-188) as one message:
+    original_bytes = the old file's bytes of the touched rows (lcpc_pos_update_rows)."""
+    original_result_vector: np.ndarray
+    original_columns: List[LcColumn]
+    new_result_vector: np.ndarray
+    new_columns: List[LcColumn]
+    original_bytes: bytes
+    original_root: bytes = b""   # not part of the message: the roots the server computed
+    new_root: bytes = b""
+
+
+def update_rows(old_len: int, offset: int, length: int, pre: int) -> tuple:
+    """lcpc_pos_update_rows: (row_lo, row_hi, old_lo, old_hi) of writing `length` bytes at `offset`
+    into a file of old_len bytes.  Host only."""
+    r = [C.c_size_t() for _ in range(4)]
+    _raise(N.load().lcpc_pos_update_rows(old_len, offset, length, pre, *[C.byref(v) for v in r]))
+    return tuple(v.value for v in r)
+
+
+class _DeviceImage:
+    """A file image in device memory for one server call, through the HIP runtime the library links."""
+
+    def __init__(self, data):
+        N.load()
+        self._rt = C.CDLL("libamdhip64.so.7")
+        self._rt.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        self._rt.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        self._rt.hipFree.argtypes = [C.c_void_p]
+        a = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) \
+            else np.ascontiguousarray(data, np.uint8)
+        self.n = a.size
+        p = C.c_void_p()
+        if self._rt.hipMalloc(C.byref(p), self.n + 16) != 0:
+            _raise(32)
+        self.ptr = p.value
+        if self.n and self._rt.hipMemcpy(self.ptr, a.ctypes.data, self.n, 1) != 0:
+            self._rt.hipFree(self.ptr)
+            _raise(31)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self._rt.hipFree(self.ptr)
+
+
+def _columns(cols: np.ndarray, paths, n: int, path_len: int) -> List[LcColumn]:
+    pb = bytes(paths)
+    return [LcColumn(cols[k].copy(), [pb[32 * (k * path_len + i):32 * (k * path_len + i + 1)] for i in range(path_len)])
+            for k in range(n)]
+
+
+def _update_evaluation(enc_old: LigeroEncoding, d_old: int, n_old: int, enc_new: LigeroEncoding, d_new: int,
+                       n_new: int, point, cols_old, cols_new, want_expected: bool):
+    """lcpc_pos_update_evaluation: ((result, columns, root) old, the same new, expected or None)."""
+    x = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1)[:1].copy()
+    sides = []
+    for enc, n, cols in ((enc_old, n_old, cols_old), (enc_new, n_new, cols_new)):
+        idx = np.ascontiguousarray(list(cols), dtype=np.uint64)
+        n_rows = -(-(-(-n // DATA_BYTE_CAPACITY)) // enc.n_per_row)
+        pl = (enc.n_cols - 1).bit_length()
+        sides.append(dict(idx=idx, pl=pl, result=np.zeros((enc.n_cols, 1), np.uint64),
+                          cols=np.zeros((max(idx.size, 1), n_rows, 1), np.uint64),
+                          paths=(C.c_uint8 * max(32 * pl * idx.size, 1))(), root=(C.c_uint8 * 32)()))
+    expected = np.zeros((1, 1), np.uint64)
+    args = [enc_old._h, d_old, n_old, enc_new._h, d_new, n_new, _p64(x)]
+    for s in sides:
+        args += [_p64(s["idx"]) if s["idx"].size else None, s["idx"].size]
+    for s in sides:
+        args += [_p64(s["result"]), _p64(s["cols"]), C.cast(s["paths"], N.u8p), C.cast(s["root"], N.u8p)]
+    _raise(N.load().lcpc_pos_update_evaluation(*args, _p64(expected) if want_expected else None))
+    out = [(s["result"], _columns(s["cols"], s["paths"], s["idx"].size, s["pl"]), bytes(s["root"])) for s in sides]
+    return out[0], out[1], (expected if want_expected else None)
+
+
+def server_reshape_evaluation(data, old_dims, new_dims, point, cols_old, cols_new) -> ReshapeEvaluation:
+    """The reshape handler (server.rs:833-906): the one file committed under both shapes, the columns
+    of each opened, and the file polynomial's value at the point.  dims = (pre, enc)."""
+    enc_old = LigeroEncoding.new_from_dims(FT63, *old_dims)
+    enc_new = LigeroEncoding.new_from_dims(FT63, *new_dims)
+    with _DeviceImage(data) as d:
+        old, new, expected = _update_evaluation(enc_old, d.ptr, d.n, enc_new, d.ptr, d.n, point, cols_old, cols_new,
+                                                True)
+    return ReshapeEvaluation(expected, old[0], old[1], new[0], new[1], old[2], new[2])
+
+
+def server_update_evaluation(old_data, new_data, dims, point, cols, offset: Optional[int] = None,
+                             length: Optional[int] = None) -> UpdateEvaluation:
+    """The edit and append handler (server.rs:963-1077): both versions committed under dims = (pre,
+    enc), the same columns of each opened, and the old file's bytes of the rows the update touched.
+    offset / length: the update's byte range as the client sent it; left out, the range from the first
+    to the last byte in which the versions differ (an append: from the old end)."""
+    old_data, new_data = bytes(old_data), bytes(new_data)
+    if offset is None or length is None:
+        m = min(len(old_data), len(new_data))
+        ne = np.flatnonzero(np.frombuffer(old_data[:m], np.uint8) != np.frombuffer(new_data[:m], np.uint8))
+        lo = int(ne[0]) if ne.size else len(old_data)
+        hi = len(new_data) if len(new_data) > len(old_data) else (int(ne[-1]) + 1 if ne.size else 0)
+        if len(new_data) < len(old_data) or hi <= lo:
+            raise ValueError("the versions are equal (or the file shrank): give the update's offset and length")
+        offset, length = lo, hi - lo
+    _, _, old_lo, old_hi = update_rows(len(old_data), offset, length, dims[0])
+    enc = LigeroEncoding.new_from_dims(FT63, *dims)
+    with _DeviceImage(old_data) as d_old, _DeviceImage(new_data) as d_new:
+        old, new, _ = _update_evaluation(enc, d_old.ptr, d_old.n, enc, d_new.ptr, d_new.n, point, cols, cols, False)
+    return UpdateEvaluation(old[0], old[1], new[0], new[1], old_data[old_lo:old_hi], old[2], new[2])
+
+
+def _file_rows(n_bytes: int, pre: int) -> int:
+    return -(-(-(-n_bytes // DATA_BYTE_CAPACITY)) // pre)
+
+
+def _checked_file_evaluation(root: bytes, n_bytes: int, pre: int, enc: int, point, cols, result_vector,
+                             columns: Sequence[LcColumn]) -> np.ndarray:
+    """Checks 1 and 2 for one version: the opened columns hash up to root, and the decoded result
+    vector, re-encoded, agrees with them; returns the file polynomial's value at the point."""
+    cols = [int(c) for c in cols]
+    if any(b <= a for a, b in zip(cols, cols[1:])):
+        raise ValueError("requested columns must be strictly increasing")
+    n_rows = _file_rows(n_bytes, pre)
+    if len(columns) != len(cols) or any(np.asarray(c.col).size != n_rows for c in columns):
+        raise _verifier_error("ColumnEval", "opened columns do not have the file's row count")
+    res = np.ascontiguousarray(np.asarray(result_vector, dtype=np.uint64).reshape(-1, 1))
+    if res.shape[0] != enc:
+        raise _verifier_error("ColumnEval", "result vector is not one encoded row")
+    client_online_verify_column_paths(root, cols, columns)
+    # side vectors over (n_rows, pre): the left stride is pre, so the value is the file polynomial's
+    left, right = form_side_vectors_for_polynomial_evaluation_from_point(point, n_rows, pre)
+    return verifiable_full_polynomial_evaluation(left, right, decode_row(res), cols, columns, pre, enc)
+
+
+def client_verify_reshape_evaluation(old_root: bytes, new_root: bytes, file_len: int, old_dims, new_dims, point,
+                                     cols_old, cols_new, response: ReshapeEvaluation) -> np.ndarray:
+    """client.rs:755-827: both shapes' evaluations verify against their roots and agree with each
+    other and with expected_result.  Returns the evaluation; raises VerifierError (ColumnEval,
+    ReshapeMismatch)."""
+    old = _checked_file_evaluation(old_root, file_len, old_dims[0], old_dims[1], point, cols_old,
+                                   response.original_result_vector, response.original_columns)
+    new = _checked_file_evaluation(new_root, file_len, new_dims[0], new_dims[1], point, cols_new,
+                                   response.new_result_vector, response.new_columns)
+    want = np.asarray(response.expected_result, dtype=np.uint64).reshape(-1)
+    if not (np.array_equal(old.reshape(-1), new.reshape(-1)) and np.array_equal(new.reshape(-1), want)):
+        raise _verifier_error("ReshapeMismatch", "the two shapes do not evaluate to the expected result")
+    return new
+
+
+def client_verify_update_evaluation(old_root: bytes, new_root: bytes, old_len: int, offset: int, data: bytes,
+                                    pre: int, enc: int, point, cols, response: UpdateEvaluation) -> np.ndarray:
+    """client.rs:1009-1135, 1273-1420: the client wrote `data` at `offset` into its file of old_len
+    bytes (kept as old_root) and was given new_root.  Accepts new_root only if (1) the opened columns
+    hash up to the two roots, (2) both result vectors agree with them, (4) the touched rows of both
+    versions, encoded here from original_bytes and the client's own data, are what the columns hold
+    and every other row is unchanged, and (5) the evaluations differ by what those rows predict.
+    Returns the new evaluation; raises VerifierError (ColumnEval, RowsMismatch, UpdateMismatch)."""
+    data = bytes(data)
+    row_lo, row_hi, old_lo, old_hi = update_rows(old_len, offset, len(data), pre)
+    new_len = max(old_len, offset + len(data))
+    cols = [int(c) for c in cols]
+    old_val = _checked_file_evaluation(old_root, old_len, pre, enc, point, cols, response.original_result_vector,
+                                       response.original_columns)
+    new_val = _checked_file_evaluation(new_root, new_len, pre, enc, point, cols, response.new_result_vector,
+                                       response.new_columns)
+    # (4) the rows are authentic (a TODO in the reference, client.rs:1325-1327)
+    old_rows = bytes(response.original_bytes)
+    if len(old_rows) != old_hi - old_lo:
+        raise _verifier_error("RowsMismatch", "original_bytes is not the touched rows' length")
+    rel = offset - old_lo
+    spliced = bytearray(old_rows) + bytes(max(0, rel + len(data) - len(old_rows)))
+    spliced[rel:rel + len(data)] = data
+    new_rows = bytes(spliced)
+    rb = pre * DATA_BYTE_CAPACITY
+    n_rows_old, n_rows_new = _file_rows(old_len, pre), _file_rows(new_len, pre)
+    code = LigeroEncoding.new_from_dims(FT63, pre, enc)
+    for rows, n_rows, columns in ((old_rows, n_rows_old, response.original_columns),
+                                  (new_rows, n_rows_new, response.new_columns)):
+        n = -(-len(rows) // rb)
+        if n == 0 or not cols:
+            continue
+        m = np.zeros((n, enc, 1), np.uint64)
+        for i in range(n):
+            el = convert_byte_vec_to_field_elements_vec(rows[i * rb:(i + 1) * rb])
+            m[i, :el.shape[0]] = el
+        m = code.encode_rows(m)
+        for k, c in enumerate(cols):
+            col = np.asarray(columns[k].col, dtype=np.uint64).reshape(-1)
+            if not np.array_equal(m[:, c, 0], col[row_lo:row_lo + n]):
+                raise _verifier_error("RowsMismatch", "an opened column disagrees with the touched rows")
+    for k in range(len(cols)):
+        a = np.asarray(response.original_columns[k].col, dtype=np.uint64).reshape(-1)
+        b = np.asarray(response.new_columns[k].col, dtype=np.uint64).reshape(-1)
+        keep = np.ones(n_rows_old, bool)
+        keep[row_lo:row_hi] = False
+        if not np.array_equal(a[:n_rows_old][keep], b[:n_rows_old][keep]):
+            raise _verifier_error("RowsMismatch", "an untouched row changed")
+    # (5) the difference of the evaluations is the difference of the touched rows' polynomials
+    d = row_lo * pre
+    p_old = evaluate_bytes_polynomial_at_point(old_rows, point, d) if old_rows else np.zeros((1, 1), np.uint64)
+    p_new = evaluate_bytes_polynomial_at_point(new_rows, point, d)
+    lhs = (int(new_val.reshape(-1)[0]) - int(old_val.reshape(-1)[0])) % FT63_MODULUS
+    rhs = (int(p_new.reshape(-1)[0]) - int(p_old.reshape(-1)[0])) % FT63_MODULUS
+    if lhs != rhs:
+        raise _verifier_error("UpdateMismatch", "the evaluations do not differ by the update's polynomial")
+    return new_val
+
+
+def client_verify_edit_evaluation(old_root: bytes, new_root: bytes, file_len: int, offset: int, data: bytes,
+                                  pre: int, enc: int, point, cols, response: UpdateEvaluation) -> np.ndarray:
+    """The edit flow (client.rs:1273-1420): an update inside the file."""
+    if offset + len(data) > file_len:
+        raise ValueError("an edit stays inside the file")
+    return client_verify_update_evaluation(old_root, new_root, file_len, offset, data, pre, enc, point, cols, response)
+
+
+def client_verify_append_evaluation(old_root: bytes, new_root: bytes, old_len: int, data: bytes, pre: int, enc: int,
+                                    point, cols, response: UpdateEvaluation) -> np.ndarray:
+    """The append flow (client.rs:1009-1135): an update at the old end."""
+    return client_verify_update_evaluation(old_root, new_root, old_len, old_len, data, pre, enc, point, cols, response)

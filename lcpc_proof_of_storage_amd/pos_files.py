@@ -1172,6 +1172,24 @@ class FileHandler:
                 out.append(LcColumn(r.get_encoded_column_without_path(c), self.merkle_tree.get_path(c)))
         return out
 
+    def polynomial_evaluation_response(self, point, columns):
+        """The server's answer to an evaluation request from the stored files, without recommitting:
+        (result_vector, columns_with_paths), bit-identical to the commitment path's u^T Enc(M) and
+        opened columns for left = [1, x^pre, ...].  The raw file gives u^T M (lcpc_pos_left_multiply_bytes)
+        and one row encode gives Enc(u^T M) = u^T Enc(M); the columns come from the `.porenc` (canonical
+        there, Montgomery limbs here as a commitment opens them) with the `.portree`'s paths."""
+        from .lcpc2d import FT63, LcColumn, LigeroEncoding
+        from .pos import FT63_MODULUS, form_side_vectors_for_polynomial_evaluation_from_point
+        pre, enc = self.pre_encoded_size, self.encoded_size
+        left, _ = form_side_vectors_for_polynomial_evaluation_from_point(point, self.rows_written, pre)
+        row = np.zeros((enc, 1), np.uint64)
+        row[:pre] = np.asarray(self.left_multiply_unencoded_matrix_by_vector(left), dtype=np.uint64).reshape(-1, 1)
+        result = LigeroEncoding.new_from_dims(FT63, pre, enc).encode(row)
+        cols = [LcColumn(np.array([(int(v) << 64) % FT63_MODULUS for v in np.asarray(c.col).reshape(-1)],
+                                  np.uint64).reshape(-1, 1), c.path)
+                for c in self.read_full_columns(columns)]
+        return result, cols
+
     # -- re-encoding
     def _reencode_rows(self, row_lo: int, row_hi: int) -> None:
         """Rows [row_lo, row_hi) from the raw file into the .porenc (one batched GPU pass)."""
