@@ -346,6 +346,65 @@ lcpc_status lcpc_verify_ops(const uint8_t root[32], const uint64_t *outer_tensor
                             const uint64_t *inner_tensor, size_t inner_len, const lcpc_proof *p,
                             const lcpc_encoding *e, const lcpc_transcript_ops *ops, uint64_t *eval_out);
 
+/* ------------------------------------------------------------------ batched evaluation proofs
+ * NO COUNTERPART IN THE REFERENCE.  Additive within LCPC_ABI_VERSION 3.  One commitment opened at
+ * n_evals points with one set of degree tests and one set of column openings.  Transcript order:
+ * the degree tests exactly as lcpc_prove runs them; p_eval_0 .. p_eval_(n_evals - 1) in order, each
+ * coefficient under "$l//PE"; then the column challenge.  Every claim is absorbed before the
+ * columns are drawn, so each opened column checks all of them and a false claim survives with the
+ * probability it has in a single proof.  With n_evals = 1 the proof parts and the transcript's end
+ * state are those of lcpc_prove / lcpc_verify, byte for byte.
+ * The row combinations of one call go through a kernel that takes any number of tensors up to
+ * LCPC_BATCH_MAX_TENSORS, which also bounds n_evals. */
+#define LCPC_BATCH_MAX_TENSORS 4096
+typedef struct lcpc_batch_proof lcpc_batch_proof;
+/* outers: host, n_evals tensors of outer_len elements each, row-major.  n_evals == 0 or above the
+ * bound: LCPC_ERR_INVALID_ARG; a commitment of another digest than e's: LCPC_ERR_INVALID_ARG;
+ * outer_len != n_rows: LCPC_PROVER_OUTER_TENSOR; the other errors are lcpc_prove's. */
+lcpc_status lcpc_prove_batch(const lcpc_commit *c, const uint64_t *outers, size_t n_evals, size_t outer_len,
+                             const lcpc_encoding *e, lcpc_transcript *tr, lcpc_batch_proof **out);
+/* inners: n_evals tensors of inner_len elements; evals_out (may be NULL): n_evals elements,
+ * evals_out[j] = <inners_j, p_eval_j>.  Per opened column the checks fail in the reference's order:
+ * ColumnDegree, then ColumnEval (for any j; lcpc_last_error names the first failing j), then
+ * ColumnPath.  n_evals == 0 or above the bound: LCPC_ERR_INVALID_ARG; a proof that holds another
+ * number of evaluations than n_evals: LCPC_VERIFIER_OUTER_TENSOR; the other argument errors are
+ * lcpc_verify's. */
+lcpc_status lcpc_verify_batch(const uint8_t root[32], const uint64_t *outers, size_t n_evals, size_t outer_len,
+                              const uint64_t *inners, size_t inner_len, const lcpc_batch_proof *p,
+                              const lcpc_encoding *e, lcpc_transcript *tr, uint64_t *evals_out);
+/* the same over the caller's transcript for this one call (see lcpc_prove_ops) */
+lcpc_status lcpc_prove_batch_ops(const lcpc_commit *c, const uint64_t *outers, size_t n_evals, size_t outer_len,
+                                 const lcpc_encoding *e, const lcpc_transcript_ops *ops, lcpc_batch_proof **out);
+lcpc_status lcpc_verify_batch_ops(const uint8_t root[32], const uint64_t *outers, size_t n_evals, size_t outer_len,
+                                  const uint64_t *inners, size_t inner_len, const lcpc_batch_proof *p,
+                                  const lcpc_encoding *e, const lcpc_transcript_ops *ops, uint64_t *evals_out);
+void lcpc_batch_proof_free(lcpc_batch_proof *p);
+size_t lcpc_batch_proof_n_evals(const lcpc_batch_proof *p);
+size_t lcpc_batch_proof_n_cols(const lcpc_batch_proof *p);
+size_t lcpc_batch_proof_n_per_row(const lcpc_batch_proof *p);
+size_t lcpc_batch_proof_n_rows(const lcpc_batch_proof *p);
+size_t lcpc_batch_proof_n_degree_tests(const lcpc_batch_proof *p);
+size_t lcpc_batch_proof_n_col_opens(const lcpc_batch_proof *p);
+size_t lcpc_batch_proof_path_len(const lcpc_batch_proof *p);
+lcpc_field lcpc_batch_proof_field(const lcpc_batch_proof *p);
+/* j-th evaluation vector (n_per_row elements), i-th degree-test vector, k-th opened column */
+lcpc_status lcpc_batch_proof_copy_p_eval(const lcpc_batch_proof *p, size_t j, uint64_t *out);
+lcpc_status lcpc_batch_proof_copy_p_random(const lcpc_batch_proof *p, size_t i, uint64_t *out);
+lcpc_status lcpc_batch_proof_copy_column(const lcpc_batch_proof *p, size_t k, uint64_t *col, uint8_t *path);
+/* p_evals: n_evals x n_per_row elements; the other arrays as lcpc_proof_from_parts */
+lcpc_status lcpc_batch_proof_from_parts(lcpc_field f, size_t n_cols, size_t n_per_row, size_t n_rows,
+                                        size_t n_degree_tests, size_t n_col_opens, size_t path_len,
+                                        size_t n_evals, const uint64_t *p_evals, const uint64_t *p_random,
+                                        const uint64_t *cols, const uint8_t *paths, lcpc_batch_proof **out);
+/* out[t][c] = sum_r tensors[t][r] * coeffs[r][c] on host arrays for any 1 <= n_tensors <=
+ * LCPC_BATCH_MAX_TENSORS (else LCPC_ERR_INVALID_ARG): the many-tensor row-combination kernel by
+ * itself.  Every out[t] equals lcpc_collapse_columns of tensor t, bit for bit. */
+lcpc_status lcpc_collapse_columns_many(lcpc_field f, const uint64_t *coeffs, size_t n_rows, size_t n_per_row,
+                                       const uint64_t *tensors, size_t n_tensors, uint64_t *out);
+/* tensors per chunk (one pass over the coefficient matrix each) in that kernel for field f: 16, 8,
+ * 5, 4, 4 for Ft63 .. Ft253_192; Ft127's matrix-core kernel also takes 8.  0: no such field. */
+int lcpc_collapse_many_chunk(lcpc_field f);
+
 /* ------------------------------------------------------------------ free functions */
 /* collapse_columns (lcpc-2d/src/lib.rs:1126-1154) on host arrays: poly[c] += ... is computed
  * as poly = sum_r tensor[r] * coeffs[r][c] for c < n_per_row */

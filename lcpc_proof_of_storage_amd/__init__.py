@@ -9,6 +9,7 @@ from .lcpc2d import (  # noqa: F401
     BLAKE3, SHA256, SHA3_256, KECCAK256, digest_name,
     LcpcError, ProverError, VerifierError, FFTError, DeviceError,
     Transcript, CallerTranscript, LcEncoding, LigeroEncoding, RsEncoding, SdigEncoding, LcCommit, LcEvalProof, LcColumn,
+    LcBatchEvalProof, BATCH_MAX_TENSORS, collapse_columns_many, collapse_many_chunk,
     collapse_columns, merkle_tree, hash_columns, verify_column_path, verify_column_value,
     n_degree_tests, log2, limbs, num_bits, set_device, device_count, field_random,
     prof_enable, prof_reset, prof_stats, selftest_pool_ordering,

@@ -142,6 +142,25 @@ SIGNATURES = {
     "lcpc_proof_from_parts": (i32, [i32, sz, sz, sz, sz, sz, sz, u64p, u64p, u64p, u8p, C.POINTER(vp)]),
     "lcpc_verify": (i32, [u8p, u64p, sz, u64p, sz, vp, vp, vp, u64p]),
     "lcpc_collapse_columns": (i32, [i32, u64p, u64p, u64p, sz, sz]),
+    "lcpc_collapse_columns_many": (i32, [i32, u64p, sz, sz, u64p, sz, u64p]),
+    "lcpc_collapse_many_chunk": (i32, [i32]),
+    "lcpc_prove_batch": (i32, [vp, u64p, sz, sz, vp, vp, C.POINTER(vp)]),
+    "lcpc_prove_batch_ops": (i32, [vp, u64p, sz, sz, vp, C.POINTER(TranscriptOps), C.POINTER(vp)]),
+    "lcpc_verify_batch": (i32, [u8p, u64p, sz, sz, u64p, sz, vp, vp, vp, u64p]),
+    "lcpc_verify_batch_ops": (i32, [u8p, u64p, sz, sz, u64p, sz, vp, vp, C.POINTER(TranscriptOps), u64p]),
+    "lcpc_batch_proof_free": (None, [vp]),
+    "lcpc_batch_proof_n_evals": (sz, [vp]),
+    "lcpc_batch_proof_n_cols": (sz, [vp]),
+    "lcpc_batch_proof_n_per_row": (sz, [vp]),
+    "lcpc_batch_proof_n_rows": (sz, [vp]),
+    "lcpc_batch_proof_n_degree_tests": (sz, [vp]),
+    "lcpc_batch_proof_n_col_opens": (sz, [vp]),
+    "lcpc_batch_proof_path_len": (sz, [vp]),
+    "lcpc_batch_proof_field": (i32, [vp]),
+    "lcpc_batch_proof_copy_p_eval": (i32, [vp, sz, u64p]),
+    "lcpc_batch_proof_copy_p_random": (i32, [vp, sz, u64p]),
+    "lcpc_batch_proof_copy_column": (i32, [vp, sz, u64p, u8p]),
+    "lcpc_batch_proof_from_parts": (i32, [i32, sz, sz, sz, sz, sz, sz, sz, u64p, u64p, u64p, u8p, C.POINTER(vp)]),
     "lcpc_merkle_tree": (i32, [u8p, sz, u8p]),
     "lcpc_verify_column_path": (i32, [i32, u64p, sz, u8p, sz, sz, u8p]),
     "lcpc_verify_column_value": (i32, [i32, u64p, u64p, sz, u64p]),

@@ -16,6 +16,10 @@
 // Ft127) runs the contraction on the int8 matrix cores instead (collapse_mfma.hpp): there the
 // kernel streams the coefficient matrix at the HBM rate instead of being bound by 64-bit
 // multiply-adds.
+//
+// collapse_rows_many takes any number of tensors (batched evaluation proofs) in chunks:
+// TT accumulators per thread on the VALU for every field, TC tensors per MFMA chunk for Ft127 from
+// 5 tensors on.  collapse_rows and its kernels are untouched by it.
 #include "collapse_mfma.hpp"
 #include "field.hpp"
 #include "kernels.hpp"
@@ -83,6 +87,89 @@ __global__ __launch_bounds__(256) void k_collapse_fold(const uint32_t *__restric
   }
 }
 
+// ---- any number of tensors (batched evaluation proofs): chunks of TT accumulators per thread.
+// blockIdx.z = the chunk, tensors [z TT, min(n_tensors, (z + 1) TT)); the coefficient matrix is
+// read once per chunk.  TT keeps the accumulators in 32 VGPRs for every field (many_tt).  A
+// short last chunk runs all TT accumulators on clamped tensor indices (still wave-uniform) and
+// stores only the tensors that exist.
+// partial[(split n_tensors + t) n_per_row + c], as k_collapse_partial with T = n_tensors.
+template <class F>
+constexpr int many_tt() {
+  return 32 / F::N < 4 ? 4 : 32 / F::N;  // Ft63 16, Ft127 8, Ft191 5, Ft255 / Ft253_192 4
+}
+
+template <class F>
+__global__ __launch_bounds__(256) void k_collapse_many_partial(const uint32_t *__restrict__ coeffs,
+                                                               size_t n_rows, size_t n_per_row,
+                                                               const uint32_t *__restrict__ tensors,
+                                                               size_t n_tensors,
+                                                               uint32_t *__restrict__ partial,
+                                                               size_t rows_per_split) {
+  constexpr int TT = many_tt<F>();
+  const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t split = blockIdx.y;
+  const size_t t0 = (size_t)blockIdx.z * TT;
+  if (c >= n_per_row) return;
+  const size_t r0 = split * rows_per_split;
+  const size_t r1 = r0 + rows_per_split < n_rows ? r0 + rows_per_split : n_rows;
+  // wave-uniform row base of the chunk's tensor t (past the end: the last tensor again)
+  const uint32_t *tp = tensors + t0 * n_rows * F::N;
+  const size_t tl = n_tensors - t0 - 1;
+  auto tb = [&](int t) { return ((size_t)t < tl ? (size_t)t : tl) * n_rows; };
+  Fe<F> acc[TT];
+#pragma unroll
+  for (int t = 0; t < TT; t++) acc[t] = fe_zero<F>();
+  constexpr int K = fe_dot_kmax<F>() < 4 ? fe_dot_kmax<F>() : 4;
+  size_t r = r0;
+  for (; r + K <= r1; r += K) {
+    Fe<F> x[K];
+#pragma unroll
+    for (int q = 0; q < K; q++) x[q] = fe_load<F>(coeffs, (r + q) * n_per_row + c);
+#pragma unroll
+    for (int t = 0; t < TT; t++) {
+      Fe<F> w[K];
+#pragma unroll
+      for (int q = 0; q < K; q++) w[q] = fe_load<F>(tp, tb(t) + r + q);
+      acc[t] = fe_add<F>(acc[t], fe_dot<F, K>(x, w));
+    }
+  }
+  for (; r < r1; r++) {
+    const Fe<F> x = fe_load<F>(coeffs, r * n_per_row + c);
+#pragma unroll
+    for (int t = 0; t < TT; t++) acc[t] = fe_add<F>(acc[t], fe_mul<F>(x, fe_load<F>(tp, tb(t) + r)));
+  }
+#pragma unroll
+  for (int t = 0; t < TT; t++)
+    if (t0 + t < n_tensors) fe_store<F>(partial, (split * n_tensors + t0 + t) * n_per_row + c, acc[t]);
+}
+
+// out[t][c] = sum over the splits; blockIdx.y = t
+template <class F>
+__global__ __launch_bounds__(256) void k_collapse_many_fold(const uint32_t *__restrict__ partial,
+                                                            size_t n_splits, size_t n_per_row,
+                                                            size_t n_tensors, uint32_t *__restrict__ out) {
+  const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t t = blockIdx.y;
+  if (c >= n_per_row) return;
+  Fe<F> acc = fe_zero<F>();
+  for (size_t s = 0; s < n_splits; s++) acc = fe_add<F>(acc, fe_load<F>(partial, (s * n_tensors + t) * n_per_row + c));
+  fe_store<F>(out, t * n_per_row + c, acc);
+}
+
+int many_tt_of(int fid) {
+  return dispatch_field(fid, [&]<class F>() { return many_tt<F>(); });
+}
+
+// as n_splits_for, with the chunks counted into the waves in flight
+size_t many_splits_for(int fid, size_t n_rows, size_t n_per_row, size_t n_tensors) {
+  const size_t tt = (size_t)many_tt_of(fid);
+  const size_t waves = (n_per_row + 63) / 64 * ((n_tensors + tt - 1) / tt);
+  size_t splits = (8192 + waves - 1) / waves;
+  const size_t max_splits = (n_rows + 15) / 16;
+  if (splits > max_splits) splits = max_splits;
+  return splits < 1 ? 1 : splits;
+}
+
 size_t n_splits_for(size_t n_rows, size_t n_per_row) {
   // aim for >= 8192 waves of work in flight, at least 16 rows per split
   const size_t col_waves = (n_per_row + 63) / 64;
@@ -124,6 +211,25 @@ __global__ __launch_bounds__(1024) void k_dot(const uint32_t *__restrict__ a,
     if ((int)threadIdx.x < w) red[threadIdx.x] = fe_add<F>(red[threadIdx.x], red[threadIdx.x + w]);
   }
   if (threadIdx.x == 0) fe_store<F>(out, 0, red[0]);
+}
+
+// out[j] = <a_j, b_j> for vectors j = blockIdx.x of n elements each (the batched verifier's final
+// inner products in one launch)
+template <class F>
+__global__ __launch_bounds__(1024) void k_dot_many(const uint32_t *__restrict__ a,
+                                                   const uint32_t *__restrict__ b, size_t n,
+                                                   uint32_t *__restrict__ out) {
+  __shared__ Fe<F> red[1024];
+  const size_t base = (size_t)blockIdx.x * n;
+  Fe<F> acc = fe_zero<F>();
+  for (size_t i = threadIdx.x; i < n; i += 1024)
+    acc = fe_add<F>(acc, fe_mul<F>(fe_load<F>(a, base + i), fe_load<F>(b, base + i)));
+  red[threadIdx.x] = acc;
+  for (int w = 512; w > 0; w >>= 1) {
+    __syncthreads();
+    if ((int)threadIdx.x < w) red[threadIdx.x] = fe_add<F>(red[threadIdx.x], red[threadIdx.x + w]);
+  }
+  if (threadIdx.x == 0) fe_store<F>(out, blockIdx.x, red[0]);
 }
 
 template <class F>
@@ -284,6 +390,73 @@ hipError_t collapse_rows(int fid, const uint32_t *coeffs, size_t n_rows, size_t 
   });
 }
 
+int collapse_many_chunk(int fid) { return many_tt_of(fid); }
+
+// Ft127: the int8 matrix-core kernel (k_collapse_mfma_many) from MANY_MFMA_MIN_T tensors on: measured
+// 2.0-2.3 times faster than the VALU kernel at 8, 16 and 64 tensors; both kernels run
+// whole chunks of 8, so 5-7 tensors cost what 8 do.  Fewer than 5 were not measured and stay VALU.
+static constexpr size_t MANY_MFMA_MIN_T = 5;
+static bool use_mfma_many(int fid, size_t n_tensors) {
+  return !no_mfma() && fid == Ft127::ID && n_tensors >= MANY_MFMA_MIN_T;
+}
+
+size_t collapse_many_scratch_bytes(int fid, size_t n_rows, size_t n_per_row, size_t n_tensors) {
+  const size_t valu = many_splits_for(fid, n_rows, n_per_row, n_tensors) * n_tensors * n_per_row * field_bytes(fid);
+  if (!use_mfma_many(fid, n_tensors)) return valu;
+  const size_t mfma = round_up(mfma_splits_for(n_rows, n_per_row) * n_tensors * n_per_row * 16, 256) +
+                      n_tensors * n_rows * 256;
+  return mfma > valu ? mfma : valu;
+}
+
+static hipError_t collapse_mfma_many(const uint32_t *coeffs, size_t n_rows, size_t n_per_row, const uint32_t *tensors,
+                              size_t n_tensors, uint32_t *out, void *scratch, hipStream_t s) {
+  using F = Ft127;
+  constexpr size_t TC = cmfma::MANY_TC;
+  const size_t splits = mfma_splits_for(n_rows, n_per_row);
+  const size_t rps = (n_rows + splits - 1) / splits;
+  uint32_t *partial = (uint32_t *)scratch;
+  uint8_t *hdig = (uint8_t *)scratch + round_up(splits * n_tensors * n_per_row * 16, 256);
+  const size_t nd = n_tensors * n_rows * 16;
+  prof::Scope ps("collapse_many_partial", s);
+  hipLaunchKernelGGL((cmfma::k_tensor_digits<F>), dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, s, tensors,
+                     n_rows, (int)n_tensors, hdig);
+  const unsigned bx = (unsigned)((n_per_row + 4 * cmfma::COLS_PER_WAVE - 1) / (4 * cmfma::COLS_PER_WAVE));
+  hipLaunchKernelGGL((cmfma::k_collapse_mfma_many<F, (int)TC>),
+                     dim3(bx, (unsigned)splits, (unsigned)((n_tensors + TC - 1) / TC)), dim3(256), 0, s, coeffs, n_rows,
+                     n_per_row, (const uint8_t *)hdig, n_tensors, partial, rps);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  prof::Scope ps2("collapse_many_fold", s);
+  hipLaunchKernelGGL((k_collapse_many_fold<F>), dim3((unsigned)((n_per_row + 255) / 256), (unsigned)n_tensors),
+                     dim3(256), 0, s, (const uint32_t *)partial, splits, n_per_row, n_tensors, out);
+  return hipGetLastError();
+}
+
+hipError_t collapse_rows_many(int fid, const uint32_t *coeffs, size_t n_rows, size_t n_per_row,
+                              const uint32_t *tensors, size_t n_tensors, uint32_t *out, void *scratch,
+                              hipStream_t s) {
+  if (n_tensors < 1 || n_tensors > COLLAPSE_MANY_MAX_TENSORS) return hipErrorInvalidValue;
+  if (n_per_row == 0) return hipSuccess;
+  if (n_rows == 0) return hipMemsetAsync(out, 0, n_tensors * n_per_row * field_bytes(fid), s);
+  if (use_mfma_many(fid, n_tensors))
+    return collapse_mfma_many(coeffs, n_rows, n_per_row, tensors, n_tensors, out, scratch, s);
+  const size_t splits = many_splits_for(fid, n_rows, n_per_row, n_tensors);
+  const size_t rps = (n_rows + splits - 1) / splits;
+  return dispatch_field(fid, [&]<class F>() {
+    constexpr size_t TT = many_tt<F>();
+    const unsigned bx = (unsigned)((n_per_row + 255) / 256);
+    prof::Scope ps("collapse_many_partial", s);
+    hipLaunchKernelGGL((k_collapse_many_partial<F>), dim3(bx, (unsigned)splits, (unsigned)((n_tensors + TT - 1) / TT)),
+                       dim3(256), 0, s, coeffs, n_rows, n_per_row, tensors, n_tensors, (uint32_t *)scratch, rps);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    prof::Scope ps2("collapse_many_fold", s);
+    hipLaunchKernelGGL((k_collapse_many_fold<F>), dim3(bx, (unsigned)n_tensors), dim3(256), 0, s,
+                       (const uint32_t *)scratch, splits, n_per_row, n_tensors, out);
+    return hipGetLastError();
+  });
+}
+
 hipError_t column_checks(int fid, const uint32_t *cols, size_t n_open, size_t n_rows,
                          const uint32_t *tensors, int n_tensors, const uint32_t *encs,
                          size_t enc_len, const uint64_t *idx, uint32_t *flags, hipStream_t s) {
@@ -301,6 +474,15 @@ hipError_t dot(int fid, const uint32_t *a, const uint32_t *b, size_t n, uint32_t
   (void)scratch;
   return dispatch_field(fid, [&]<class F>() {
     hipLaunchKernelGGL((k_dot<F>), dim3(1), dim3(1024), 0, s, a, b, n, out);
+    return hipGetLastError();
+  });
+}
+
+hipError_t dot_many(int fid, const uint32_t *a, const uint32_t *b, size_t n, size_t n_vecs, uint32_t *out,
+                    hipStream_t s) {
+  if (!n_vecs) return hipSuccess;
+  return dispatch_field(fid, [&]<class F>() {
+    hipLaunchKernelGGL((k_dot_many<F>), dim3((unsigned)n_vecs), dim3(1024), 0, s, a, b, n, out);
     return hipGetLastError();
   });
 }

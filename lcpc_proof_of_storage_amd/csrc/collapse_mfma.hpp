@@ -214,5 +214,96 @@ __global__ __launch_bounds__(256) void k_collapse_mfma(const uint32_t *__restric
   }
 }
 
+// Any number of tensors (batched evaluation proofs): k_collapse_mfma over chunks of TC tensors,
+// blockIdx.z = the chunk, tensors [z TC, min(n_tensors, (z + 1) TC)), read from hdig exactly as
+// above.  The balanced_digits B fragment of a coefficient is computed once and fed to TC MFMAs.
+// Every tensor has its own accumulators, so |Y| is bounded per tensor as above: the split bound
+// MAX_SPLIT_ROWS = 512 and recombine_redc are unchanged.  A short last chunk runs all TC
+// accumulators on clamped tensor indices and stores only the tensors that exist.
+// partial[(split n_tensors + t) n_per_row + c].
+constexpr int MANY_TC = 8;  // 8 x TILES x 4 = 128 accumulator registers per lane
+
+template <class F, int TC>
+__global__ __launch_bounds__(256) void k_collapse_mfma_many(const uint32_t *__restrict__ coeffs, size_t n_rows,
+                                                            size_t n_per_row, const uint8_t *__restrict__ hdig,
+                                                            size_t n_tensors, uint32_t *__restrict__ partial,
+                                                            size_t rows_per_split) {
+  static_assert(F::N == 4, "Ft127 layout");
+  __shared__ int red[4][TILES][16][17];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int grp = lane >> 4, n = lane & 15;
+  const size_t col0 = ((size_t)blockIdx.x * 4 + wave) * COLS_PER_WAVE;
+  const size_t split = blockIdx.y;
+  const size_t t0 = (size_t)blockIdx.z * TC;
+  const size_t tl = n_tensors - t0 - 1;  // the chunk's last tensor (t0 < n_tensors by the grid)
+  const size_t r0 = split * rows_per_split;
+  const size_t r1 = r0 + rows_per_split < n_rows ? r0 + rows_per_split : n_rows;
+  const uint4 *cm = reinterpret_cast<const uint4 *>(coeffs);
+  const uint4 *hd = reinterpret_cast<const uint4 *>(hdig) + t0 * n_rows * 16;
+  bool colok[TILES];
+#pragma unroll
+  for (int k = 0; k < TILES; k++) colok[k] = col0 + 16 * k + n < n_per_row;
+
+  v4i acc[TC][TILES];
+#pragma unroll
+  for (int t = 0; t < TC; t++)
+#pragma unroll
+    for (int k = 0; k < TILES; k++) acc[t][k] = v4i{0, 0, 0, 0};
+
+  auto load_x = [&](size_t rg, uint4 *x) {
+    const size_t r = rg + grp;
+    const bool ok = r < r1;
+#pragma unroll
+    for (int k = 0; k < TILES; k++)
+      x[k] = ok && colok[k] ? cm[r * n_per_row + col0 + 16 * k + n] : make_uint4(0, 0, 0, 0);
+  };
+  uint4 xc[TILES], xn[TILES];
+  if (r0 < r1) load_x(r0, xc);
+  for (size_t rg = r0; rg < r1; rg += 4) {
+    const bool more = rg + 4 < r1;
+    if (more) load_x(rg + 4, xn);  // the next step's coefficients (HBM) under this step's MFMAs
+    const size_t r = rg + grp;
+    const bool ok = r < r1;
+    v4i d[TILES];
+#pragma unroll
+    for (int k = 0; k < TILES; k++) d[k] = balanced_digits(xc[k].x, xc[k].y, xc[k].z, xc[k].w);
+#pragma unroll
+    for (int t = 0; t < TC; t++) {
+      const size_t ti = (size_t)t < tl ? (size_t)t : tl;
+      const uint4 a = ok ? hd[(ti * n_rows + r) * 16 + n] : make_uint4(0, 0, 0, 0);
+      const v4i av = v4i{(int)a.x, (int)a.y, (int)a.z, (int)a.w};
+#pragma unroll
+      for (int k = 0; k < TILES; k++) acc[t][k] = __builtin_amdgcn_mfma_i32_16x16x64_i8(av, d[k], acc[t][k], 0, 0, 0);
+    }
+    if (more) {
+#pragma unroll
+      for (int k = 0; k < TILES; k++) xc[k] = xn[k];
+    }
+  }
+  // as k_collapse_mfma: one output (t, column col0 + lane) per lane through the wave's LDS slice
+  const int k = lane >> 4;
+  const size_t c = col0 + lane;
+  int(*rw)[16][17] = red[wave];
+#pragma unroll
+  for (int t = 0; t < TC; t++) {
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int q = 0; q < TILES; q++) {
+      rw[q][4 * grp + 0][n] = acc[t][q].x;
+      rw[q][4 * grp + 1][n] = acc[t][q].y;
+      rw[q][4 * grp + 2][n] = acc[t][q].z;
+      rw[q][4 * grp + 3][n] = acc[t][q].w;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    int Y[16];
+#pragma unroll
+    for (int u = 0; u < 16; u++) Y[u] = rw[k][u][n];
+    if (c < n_per_row && t0 + t < n_tensors)
+      fe_store<F>(partial, (split * n_tensors + t0 + t) * n_per_row + c, recombine_redc<F>(Y));
+  }
+}
+
 }  // namespace cmfma
 }  // namespace lcpc

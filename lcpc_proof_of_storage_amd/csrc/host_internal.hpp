@@ -592,6 +592,16 @@ struct lcpc_proof {
   pinned_vector<uint8_t> paths;
 };
 
+// A batched evaluation proof: lcpc_proof with n_evals evaluation vectors (p_evals[j][n_per_row])
+// behind one set of degree tests and one set of column openings.
+struct lcpc_batch_proof {
+  int fid = 1;
+  size_t n_cols = 0, n_per_row = 0, n_rows = 0, ndt = 0, nco = 0, path_len = 0, n_evals = 0;
+  pinned_vector<uint64_t> p_evals, p_random, cols;
+  std::vector<uint64_t> col_idx;
+  pinned_vector<uint8_t> paths;
+};
+
 // A merlin::Transcript as prove / verify see it: the library's own restatement (t), or the
 // caller's transcript behind lcpc_transcript_ops (lcpc_transcript_from_ops), every absorb and
 // squeeze forwarded.  The reference threads the caller's `&mut Transcript` through prove / verify

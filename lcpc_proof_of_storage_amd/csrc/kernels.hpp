@@ -148,6 +148,16 @@ size_t collapse_scratch_bytes(int fid, size_t n_rows, size_t n_per_row, int n_te
 hipError_t collapse_rows(int fid, const uint32_t *coeffs, size_t n_rows, size_t n_per_row,
                          const uint32_t *tensors, int n_tensors, uint32_t *out, void *scratch,
                          hipStream_t s);
+// The same for any 1 <= n_tensors <= COLLAPSE_MANY_MAX_TENSORS (batched evaluation proofs): the
+// tensors go through the VALU kernel in chunks of collapse_many_chunk(fid) accumulators per thread,
+// one read of the coefficient matrix per chunk; Ft127 from 5 tensors on takes the int8 matrix-core
+// kernel in chunks of 8 (LCPC_NO_MFMA=1: the VALU kernel).  Results are bit-identical to collapse_rows.
+constexpr size_t COLLAPSE_MANY_MAX_TENSORS = 4096;
+int collapse_many_chunk(int fid);
+size_t collapse_many_scratch_bytes(int fid, size_t n_rows, size_t n_per_row, size_t n_tensors);
+hipError_t collapse_rows_many(int fid, const uint32_t *coeffs, size_t n_rows, size_t n_per_row,
+                              const uint32_t *tensors, size_t n_tensors, uint32_t *out, void *scratch,
+                              hipStream_t s);
 // out[c] = sum_k vecs[k][c] (n_vecs vectors of len elements)
 hipError_t collapse_fold_rows(int fid, const uint32_t *vecs, size_t n_vecs, size_t len, uint32_t *out,
                               hipStream_t s);
@@ -172,6 +182,9 @@ hipError_t path_checks(const uint8_t *leaves, const uint8_t *paths, size_t n, si
 // out = sum_i a[i] * b[i]
 hipError_t dot(int fid, const uint32_t *a, const uint32_t *b, size_t n, uint32_t *out,
                void *scratch, hipStream_t s);
+// out[j] = sum_i a[j][i] * b[j][i] for j < n_vecs (vectors of n elements): one workgroup per j
+hipError_t dot_many(int fid, const uint32_t *a, const uint32_t *b, size_t n, size_t n_vecs, uint32_t *out,
+                    hipStream_t s);
 // elementwise Montgomery <-> canonical conversion (device); with bad non-null, canonical
 // inputs that are not < p set *bad = 1
 hipError_t convert(int fid, const uint32_t *in, uint32_t *out, size_t n, bool to_mont,

@@ -778,6 +778,18 @@ class LcCommit:
                                                                  C.byref(h)))
         return LcEvalProof(h.value)
 
+    def prove_batch(self, outer_tensors, enc: LcEncoding, tr) -> "LcBatchEvalProof":
+        """One proof for m evaluation points: outer_tensors is a sequence of m outer tensors (or an
+        (m, n_rows, limbs) array).  The degree tests run as in prove, then p_eval_0 .. p_eval_(m-1)
+        are absorbed in order, then the columns are drawn.  tr as for prove."""
+        o = _stack_tensors(outer_tensors, self.field)
+        h = C.c_void_p()
+        tr = _transcript(tr)
+        fn = N.load().lcpc_prove_batch
+        _call_with_transcript(tr, lambda th: fn(self._h, _p64(o.reshape(-1)), o.shape[0], o.shape[1], enc._h, th,
+                                                C.byref(h)))
+        return LcBatchEvalProof(h.value)
+
 
 class LcEvalProof:
     """LcEvalProof<Blake3, E> (lcpc-2d/src/lib.rs:516-557)."""
@@ -977,6 +989,181 @@ class LcEvalProof:
         _call_with_transcript(tr, lambda th: N.load().lcpc_verify(rp, _p64(o), o.shape[0], _p64(i), i.shape[0],
                                                                   self._h, enc._h, th, _p64(out)))
         return out
+
+
+BATCH_MAX_TENSORS = 4096  # LCPC_BATCH_MAX_TENSORS
+
+
+def _stack_tensors(tensors, field: int) -> np.ndarray:
+    """m tensors of equal length as one (m, len, limbs) array"""
+    nl = limbs(field)
+    if isinstance(tensors, np.ndarray) and tensors.ndim == 3:
+        return np.ascontiguousarray(tensors, dtype=np.uint64)
+    rows = [_elems(t, field) for t in tensors]
+    if not rows:
+        return np.zeros((0, 0, nl), np.uint64)
+    if any(r.shape != rows[0].shape for r in rows):
+        raise LcpcError(30, "the tensors of a batch must have one length")
+    return np.ascontiguousarray(np.stack(rows))
+
+
+class LcBatchEvalProof:
+    """One commitment opened at m points: the degree tests and the column openings of an
+    LcEvalProof, and m evaluation vectors p_eval_0 .. p_eval_(m-1).  The reference has no batched
+    form; with m = 1 every part equals LcEvalProof's."""
+
+    def __init__(self, handle):
+        self._h = handle
+        L = N.load()
+        self.field = L.lcpc_batch_proof_field(handle)
+        self.n_evals = L.lcpc_batch_proof_n_evals(handle)
+        self.n_cols = L.lcpc_batch_proof_n_cols(handle)
+        self.n_per_row = L.lcpc_batch_proof_n_per_row(handle)
+        self.n_rows = L.lcpc_batch_proof_n_rows(handle)
+        self.n_degree_tests = L.lcpc_batch_proof_n_degree_tests(handle)
+        self.n_col_opens = L.lcpc_batch_proof_n_col_opens(handle)
+        self.path_len = L.lcpc_batch_proof_path_len(handle)
+
+    def __del__(self):
+        try:
+            N.load().lcpc_batch_proof_free(self._h)
+        except Exception:
+            pass
+
+    def get_n_cols(self) -> int:
+        return self.n_cols
+
+    def get_n_per_row(self) -> int:
+        return self.n_per_row
+
+    @property
+    def p_eval_vec(self) -> List[np.ndarray]:
+        res = []
+        for j in range(self.n_evals):
+            out = np.zeros((self.n_per_row, limbs(self.field)), np.uint64)
+            _raise(N.load().lcpc_batch_proof_copy_p_eval(self._h, j, _p64(out)))
+            res.append(out)
+        return res
+
+    @property
+    def p_random_vec(self) -> List[np.ndarray]:
+        res = []
+        for i in range(self.n_degree_tests):
+            out = np.zeros((self.n_per_row, limbs(self.field)), np.uint64)
+            _raise(N.load().lcpc_batch_proof_copy_p_random(self._h, i, _p64(out)))
+            res.append(out)
+        return res
+
+    @property
+    def columns(self) -> List[LcColumn]:
+        res = []
+        nl = limbs(self.field)
+        for k in range(self.n_col_opens):
+            col = np.zeros((self.n_rows, nl), np.uint64)
+            path = (C.c_uint8 * max(32 * self.path_len, 1))()
+            _raise(N.load().lcpc_batch_proof_copy_column(self._h, k, _p64(col), C.cast(path, N.u8p)))
+            pb = bytes(path)
+            res.append(LcColumn(col, [pb[32 * i:32 * i + 32] for i in range(self.path_len)]))
+        return res
+
+    @classmethod
+    def from_parts(cls, field: int, n_cols: int, p_eval_vec, p_random_vec, columns: List[LcColumn]):
+        nl = limbs(field)
+        if not 1 <= len(p_eval_vec) <= BATCH_MAX_TENSORS:
+            raise LcpcError(30, "a batch proof holds between 1 and BATCH_MAX_TENSORS evaluation vectors")
+        pes = [_elems(x, field) for x in p_eval_vec]
+        if any(x.shape != pes[0].shape for x in pes):
+            raise VerifierError(12, "malformed proof: p_eval vectors of different lengths")
+        LcEvalProof._check_shapes(field, pes[0], p_random_vec, [_elems(c.col, field).shape[0] for c in columns],
+                                  [len(c.path) for c in columns], [len(d) for c in columns for d in c.path])
+        pe = np.ascontiguousarray(np.concatenate(pes)) if pes[0].shape[0] else np.zeros((1, nl), np.uint64)
+        pr = np.ascontiguousarray(np.concatenate([_elems(x, field) for x in p_random_vec]) if p_random_vec
+                                  else np.zeros((1, nl), np.uint64))
+        n_rows = _elems(columns[0].col, field).shape[0] if columns else 0
+        path_len = len(columns[0].path) if columns else 0
+        cols = np.ascontiguousarray(np.concatenate([_elems(c.col, field) for c in columns]) if columns
+                                    else np.zeros((1, nl), np.uint64))
+        paths = b"".join(b"".join(c.path) for c in columns)
+        pp, keep = _bytes_ptr(paths)
+        h = C.c_void_p()
+        _raise(N.load().lcpc_batch_proof_from_parts(field, n_cols, pes[0].shape[0], n_rows, len(p_random_vec),
+                                                    len(columns), path_len, len(pes), _p64(pe), _p64(pr), _p64(cols),
+                                                    pp, C.byref(h)))
+        return cls(h.value)
+
+    # ---- serialization: LcEvalProof's bincode layout with p_eval widened to a vector of vectors
+    # (INTEGRATION.md): n_cols u64; p_eval as u64 m, then m Vec<F>; p_random as u64 count, then
+    # that many Vec<F>; columns as u64 count, then per column Vec<F> and a Vec of 32-byte digests.
+    def to_bytes(self) -> bytes:
+        nl = limbs(self.field)
+        parts = [_q(self.n_cols), _q(self.n_evals)]
+        parts += [_ser_vec_f(x, nl) for x in self.p_eval_vec]
+        parts.append(_q(self.n_degree_tests))
+        parts += [_ser_vec_f(x, nl) for x in self.p_random_vec]
+        cols = self.columns
+        parts.append(_q(len(cols)))
+        parts += [c.to_bincode(self.field) for c in cols]
+        return b"".join(parts)
+
+    @classmethod
+    def from_bytes(cls, field: int, data: bytes) -> "LcBatchEvalProof":
+        """Inverse of to_bytes; truncated input, counts past the input's size and trailing bytes
+        raise LcpcError (LCPC_ERR_INVALID_ARG)."""
+        nl = limbs(field)
+        r = _Reader(data)
+
+        def count() -> int:
+            n = r.u64()
+            if n > len(data):  # every counted item takes at least a byte: no huge allocation
+                raise LcpcError(30, "truncated bincode input")
+            return n
+
+        n_cols = r.u64()
+        p_evals = [r.vec_f(nl) for _ in range(count())]
+        p_random = [r.vec_f(nl) for _ in range(count())]
+        columns = []
+        for _ in range(count()):
+            col = r.vec_f(nl)
+            columns.append(LcColumn(col, [r.digest() for _ in range(count())]))
+        r.end()
+        return cls.from_parts(field, n_cols, p_evals, p_random, columns)
+
+    to_bincode, from_bincode = to_bytes, from_bytes
+
+    def verify(self, root: bytes, outer_tensors, inner_tensors, enc: LcEncoding, tr) -> List[np.ndarray]:
+        """The m evaluations <inner_j, p_eval_j>, or VerifierError; tr as for LcCommit.prove."""
+        o = _stack_tensors(outer_tensors, self.field)
+        i = _stack_tensors(inner_tensors, self.field)
+        if o.shape[0] != i.shape[0]:
+            raise LcpcError(30, "as many inner tensors as outer tensors")
+        m = o.shape[0]
+        rp, keep = _bytes_ptr(root)
+        out = np.zeros((max(m, 1), limbs(self.field)), np.uint64)
+        tr = _transcript(tr)
+        fn = N.load().lcpc_verify_batch
+        _call_with_transcript(tr, lambda th: fn(rp, _p64(o.reshape(-1)), m, o.shape[1], _p64(i.reshape(-1)),
+                                                i.shape[1], self._h, enc._h, th, _p64(out)))
+        return [out[j].copy() for j in range(m)]
+
+
+def collapse_columns_many(field: int, coeffs, tensors, n_rows: int, n_per_row: int) -> np.ndarray:
+    """out[t] = collapse_columns(coeffs, tensors[t]) for every tensor in one call (the many-tensor
+    kernel); tensors: (n_tensors, n_rows, limbs).  Returns (n_tensors, n_per_row, limbs)."""
+    nl = limbs(field)
+    c = _elems(coeffs, field)
+    t = _stack_tensors(tensors, field)
+    n_tensors = t.shape[0]
+    if n_tensors and t.shape[1] != n_rows:
+        raise LcpcError(30, "every tensor has n_rows elements")
+    out = np.zeros((max(n_tensors, 1), n_per_row, nl), np.uint64)
+    _raise(N.load().lcpc_collapse_columns_many(field, _p64(c.reshape(-1)), n_rows, n_per_row, _p64(t.reshape(-1)),
+                                               n_tensors, _p64(out.reshape(-1))))
+    return out[:n_tensors]
+
+
+def collapse_many_chunk(field: int) -> int:
+    """tensors per thread and pass over the coefficient matrix in the many-tensor kernel"""
+    return N.load().lcpc_collapse_many_chunk(field)
 
 
 # ---------------------------------------------------------------- free functions
