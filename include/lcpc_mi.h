@@ -1036,6 +1036,28 @@ lcpc_status lcpc_selftest_field_op(lcpc_field f, int op, int k, const uint64_t *
  * LCPC_ERR_INVALID_ARG. */
 lcpc_status lcpc_selftest_recombine(const int32_t *y, uint64_t *out, size_t n);
 
+/* The row transform under every encode, commit and decode, called directly: n_rows rows of
+ * 2^log_n points on a plan made for the call.  Row r reads the n_valid leading elements at
+ * src + r src_stride (the rest of the row counts as zero) and writes 2^log_n elements at
+ * dst + r dst_stride, fffft::fft_io's output (Montgomery words; canonical words with canon = 1).
+ * inverse = 1 takes the inverse plan's root, omega^-1 -- the inner transform of ifft_oi, without
+ * its reordering and its 2^-log_n.  copy (optional, may be NULL): row r's n_valid inputs are also
+ * written to copy + r copy_stride, as the commit paths keep their coefficient matrix.  Strides are
+ * in elements; src, dst and copy are host buffers of n_rows whole strides.  All three are uploaded
+ * whole before the transform, and dst and copy downloaded whole after it, so every element the
+ * kernels do not write -- the gap after each row, copy beyond n_valid -- returns as the caller set
+ * it, and whatever src holds beyond n_valid is on the device for the kernels to (not) read.
+ * n_valid <= 2^(log_n - 1) runs the
+ * half-zero variant of the first pass, as rate-1/2 rows do.
+ * LCPC_ERR_INVALID_ARG, before the device is touched: an unknown field, a NULL src or dst,
+ * log_n < 0, canon together with inverse, n_valid > 2^log_n, src_stride or copy_stride < n_valid,
+ * dst_stride < 2^log_n.  LCPC_ERR_UNSUPPORTED, before the device is touched and before the
+ * lengths are looked at: log_n above the field's range (24 for Ft63 and Ft127, 22 for Ft191,
+ * Ft255 and Ft253_192). */
+lcpc_status lcpc_selftest_ntt_rows(lcpc_field f, int log_n, int inverse, const uint64_t *src,
+                                   size_t src_stride, size_t n_valid, uint64_t *dst, size_t dst_stride,
+                                   size_t n_rows, uint64_t *copy, size_t copy_stride, int canon);
+
 /* ------------------------------------------------------------------ kernel timing
  * HIP-event timing of every kernel launch on the handle streams (off by default). */
 void lcpc_prof_enable(int enable);

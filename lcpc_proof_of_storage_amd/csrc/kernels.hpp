@@ -42,6 +42,9 @@ struct NttPlan {
 };
 // the [t][c] table above for a pass-A split l1 from a flat table tw (n = 2^log_n elements)
 hipError_t ntt_tw2_table(int fid, const uint32_t *tw, int log_n, int l1, uint32_t *out, hipStream_t s);
+// the longest row a plan can be made for is 2^ntt_max_log_n(fid); beyond it ntt_plan_init returns
+// hipErrorInvalidValue before it allocates anything
+int ntt_max_log_n(int fid);
 hipError_t ntt_plan_init(NttPlan &p, int fid, int log_n, bool inverse, hipStream_t s);
 void ntt_plan_free(NttPlan &p);
 // rows r in [0, n_rows): in = src + r * src_stride (elements), n_valid leading elements

@@ -8,6 +8,9 @@
 // fast store runs first) the late writer leaves X behind.  This replaces nothing in the
 // reference (whose buffers are host Vecs, lcpc-2d/src/lib.rs:659-690); it is the device-side
 // evidence for the pool that the commit / prove / shard paths share.
+//
+// lcpc_selftest_ntt_rows (at the end): the NTT dispatch called directly, for the row lengths and
+// pass variants that no commit-sized test can isolate.
 #include "host_internal.hpp"
 
 #include <vector>
@@ -104,4 +107,60 @@ extern "C" lcpc_status lcpc_selftest_pool_ordering(int rounds, uint32_t spin_us,
   dev->release_stream(b, POOL_PROVER);
   for (void *q : held) dev->blocks.put(q, rb, nullptr, 0);
   return rc;
+}
+
+// ntt_rows (ntt.hip) with every argument the commit paths fix chosen by the caller: any row
+// length of the four-step dispatch, HALFZ or not, the canonical-output and fused-copy variants of
+// pass A, and strides, on one plan that lives for the call.  The device buffers keep the host
+// strides and are uploaded whole first, so what the kernels leave in the gap after each row (and
+// in copy beyond n_valid) comes back as the caller set it.
+extern "C" lcpc_status lcpc_selftest_ntt_rows(lcpc_field f, int log_n, int inverse, const uint64_t *src,
+                                              size_t src_stride, size_t n_valid, uint64_t *dst, size_t dst_stride,
+                                              size_t n_rows, uint64_t *copy, size_t copy_stride, int canon) {
+  if (!valid_field(f)) return fail(LCPC_ERR_INVALID_ARG, "field");
+  if (!src || !dst) return fail(LCPC_ERR_INVALID_ARG, "null src or dst");
+  if (log_n < 0) return fail(LCPC_ERR_INVALID_ARG, "log_n");
+  if (canon && inverse) return fail(LCPC_ERR_INVALID_ARG, "canonical output: forward plans only");
+  if (!field_gpu_supported(f) || log_n > ntt_max_log_n(f))
+    return fail(LCPC_ERR_UNSUPPORTED, "length beyond the NTT range");
+  const size_t n = (size_t)1 << log_n;
+  if (n_valid > n) return fail(LCPC_ERR_INVALID_ARG, "n_valid > 2^log_n");
+  if (src_stride < n_valid || dst_stride < n || (copy && copy_stride < n_valid))
+    return fail(LCPC_ERR_INVALID_ARG, "stride below its row length");
+  if (n_rows == 0) return LCPC_OK;
+  lcpc_status st;
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  const size_t wb = field_bytes(f);
+  NttPlan plan;
+  hipError_t he = ntt_plan_init(plan, f, log_n, inverse != 0, lease.s);
+  if (he != hipSuccess) {
+    ntt_plan_free(plan);
+    if (he == hipErrorInvalidValue) return fail(LCPC_ERR_UNSUPPORTED, "length beyond the NTT range");
+    HIP_TRY(he);
+  }
+  struct PlanGuard {
+    NttPlan &p;
+    hipStream_t s;
+    ~PlanGuard() {
+      (void)hipStreamSynchronize(s);
+      ntt_plan_free(p);
+    }
+  } guard{plan, lease.s};
+  // whole strides, the last row's included: what lies beyond a row's length is part of the check
+  const size_t src_b = n_rows * src_stride * wb, dst_b = n_rows * dst_stride * wb;
+  const size_t copy_b = copy ? n_rows * copy_stride * wb : 0;
+  DBuf ds, dd, dc;
+  HIP_TRY(ds.alloc(dev, std::max(src_b, wb)));  // (src_stride = n_valid = 0: nothing to upload or to read)
+  HIP_TRY(h2d(ds.p, src, src_b, lease.s));
+  if ((st = upload(dev, dd, dst, dst_b))) return st;
+  if (copy_b && (st = upload(dev, dc, copy, copy_b))) return st;
+  HIP_TRY(ntt_rows(plan, ds.as<uint32_t>(), src_stride, n_valid, dd.as<uint32_t>(), dst_stride, n_rows, lease.s,
+                   copy_b ? dc.as<uint32_t>() : nullptr, copy_stride, canon != 0));
+  HIP_TRY(hipMemcpyAsync(dst, dd.p, dst_b, hipMemcpyDeviceToHost, lease.s));
+  if (copy_b) HIP_TRY(hipMemcpyAsync(copy, dc.p, copy_b, hipMemcpyDeviceToHost, lease.s));
+  HIP_TRY(hipStreamSynchronize(lease.s));
+  return LCPC_OK;
 }

@@ -197,6 +197,31 @@ def selftest_recombine(y) -> np.ndarray:
     return out
 
 
+def selftest_ntt_rows(field: int, log_n: int, src: np.ndarray, n_valid: int, dst: np.ndarray, *,
+                      n_rows: int = 1, src_stride: Optional[int] = None, dst_stride: Optional[int] = None,
+                      copy: Optional[np.ndarray] = None, copy_stride: Optional[int] = None,
+                      canon: bool = False, inverse: bool = False) -> np.ndarray:
+    """The row transform called directly (lcpc_selftest_ntt_rows): n_rows rows of 2^log_n points,
+    row r from the n_valid leading elements at src + r src_stride into dst + r dst_stride
+    (Montgomery words, canonical ones with canon), the inputs also into copy + r copy_stride
+    when copy is given.  Strides are in elements and default to the row lengths.  src, dst and
+    copy are C-contiguous uint64 arrays of n_rows whole strides; dst and copy are written in
+    place, and what the kernels do not write keeps the caller's words.  Returns dst."""
+    for a in (src, dst, copy):
+        if a is not None and (a.dtype != np.uint64 or not a.flags["C_CONTIGUOUS"]):
+            raise TypeError("selftest_ntt_rows needs C-contiguous uint64 arrays (dst, copy: written in place)")
+    ss = n_valid if src_stride is None else src_stride
+    ds = (1 << log_n) if dst_stride is None else dst_stride
+    cs = n_valid if copy_stride is None else copy_stride
+    nl = limbs(field)
+    for a, stride, what in ((src, ss, "src"), (dst, ds, "dst"), (copy, cs, "copy")):
+        if a is not None and a.size < n_rows * stride * nl:
+            raise ValueError(f"{what} holds fewer than n_rows * stride elements")
+    _raise(N.load().lcpc_selftest_ntt_rows(field, log_n, 1 if inverse else 0, _p64(src), ss, n_valid, _p64(dst), ds,
+                                           n_rows, None if copy is None else _p64(copy), cs, 1 if canon else 0))
+    return dst
+
+
 def set_device(device: int):
     _raise(N.load().lcpc_set_device(device), DeviceError)
 

@@ -41,13 +41,17 @@ typedef struct {
   void *ctx;
   size_t lo, hi;
 } pf_arg;
+/* set while a thread runs a range of a split loop: a parallel-for called from there (the NTT's
+ * stages under the row-parallel encode) runs inline, so the threads never multiply */
+static _Thread_local int t_in_range = 0;
 static void *pf_tramp(void *p) {
   pf_arg *a = (pf_arg *)p;
+  t_in_range = 1;
   a->fn(a->ctx, a->lo, a->hi);
   return NULL;
 }
 void of_parallel_for(size_t n, size_t min_chunk, of_range_fn fn, void *ctx) {
-  int nt = g_threads;
+  int nt = t_in_range ? 1 : g_threads;
   if (min_chunk < 1) min_chunk = 1;
   if ((size_t)nt > n / min_chunk) nt = (int)(n / min_chunk);
   if (nt <= 1) {
@@ -65,6 +69,7 @@ void of_parallel_for(size_t n, size_t min_chunk, of_range_fn fn, void *ctx) {
     args[t].hi = n * (size_t)(t + 1) / (size_t)nt;
     started[t] = t > 0 && pthread_create(&th[t], NULL, pf_tramp, &args[t]) == 0;
   }
+  t_in_range = 1;
   fn(ctx, args[0].lo, args[0].hi); /* the calling thread takes the first range */
   for (int t = 1; t < nt; t++) {
     if (started[t])
@@ -72,6 +77,7 @@ void of_parallel_for(size_t n, size_t min_chunk, of_range_fn fn, void *ctx) {
     else
       fn(ctx, args[t].lo, args[t].hi); /* could not spawn: run inline */
   }
+  t_in_range = 0; /* (only a thread that was not in a range gets here with nt > 1) */
 }
 
 /* ---------------- parameters ---------------- */

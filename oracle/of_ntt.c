@@ -22,6 +22,12 @@
  * the encoded rows are R-S evaluations, ported by tests/test_oracle_invariants.py), which hold
  * under either.  They are the switches of include/lcpc_fft_convention.h, shared with the
  * product's NTT plans; the defaults are the restatement above.
+ *
+ * The len/2 butterflies of one stage touch disjoint pairs, so each stage runs through
+ * of_parallel_for (of_set_threads), flattened over the butterfly index k = c * gap + i; the
+ * stages themselves stay in order, joined between.  All arithmetic is exact, so the thread
+ * count can not change any output bit (tests/test_oracle_ntt_threads.py).  A call made from
+ * inside another of_parallel_for (the row-parallel encode of commit) runs its stages serially.
  */
 #include <stdlib.h>
 #include <string.h>
@@ -77,33 +83,63 @@ static uint64_t *roots_table(const of_field *f, int lg, const uint64_t *w) {
   return r;
 }
 
+/* One radix-2 stage: butterfly k = c * gap + i pairs x[2 c gap + i] with x[2 c gap + i + gap]
+ * under the root roots[nchunks * i]; no two butterflies of a stage share an element. */
+typedef struct {
+  const of_field *f;
+  uint64_t *x;
+  const uint64_t *roots;
+  size_t gap, nchunks;
+} stage_ctx;
+#define STAGE_MIN_CHUNK 2048 /* butterflies per thread below which a stage is not split further */
+
+static void dif_stage(void *p, size_t lo, size_t hi) {
+  const stage_ctx *s = (const stage_ctx *)p;
+  const of_field *f = s->f;
+  const size_t nl = (size_t)f->nl, gap = s->gap;
+  uint64_t a[OF_MAXL], b[OF_MAXL], d[OF_MAXL];
+  for (size_t k = lo; k < hi; k++) {
+    const size_t i = k & (gap - 1), c2g = (k - i) * 2; /* gap = 2^m: c2g = 2 c gap */
+    uint64_t *lo_e = s->x + (c2g + i) * nl, *hi_e = lo_e + gap * nl;
+    memcpy(a, lo_e, sizeof(uint64_t) * nl);
+    memcpy(b, hi_e, sizeof(uint64_t) * nl);
+    of_mont_add(f, a, b, lo_e);
+    of_mont_sub(f, a, b, d);
+    of_mont_mul(f, d, s->roots + s->nchunks * i * nl, hi_e);
+  }
+}
+
+static void dit_stage(void *p, size_t lo, size_t hi) {
+  const stage_ctx *s = (const stage_ctx *)p;
+  const of_field *f = s->f;
+  const size_t nl = (size_t)f->nl, gap = s->gap;
+  uint64_t a[OF_MAXL], b[OF_MAXL];
+  for (size_t k = lo; k < hi; k++) {
+    const size_t i = k & (gap - 1), c2g = (k - i) * 2; /* gap = 2^m: c2g = 2 c gap */
+    uint64_t *lo_e = s->x + (c2g + i) * nl, *hi_e = lo_e + gap * nl;
+    memcpy(a, lo_e, sizeof(uint64_t) * nl);
+    of_mont_mul(f, hi_e, s->roots + s->nchunks * i * nl, b);
+    of_mont_add(f, a, b, lo_e);
+    of_mont_sub(f, a, b, hi_e);
+  }
+}
+
 int of_fft_io(int fid, uint64_t *x, size_t len) {
   const of_field *f = of_get_field(fid);
   int lg;
   if (!log2_exact(len, &lg)) return 1;
   if ((uint32_t)lg > f->s) return 2;
   if (len == 1) return 0;
-  const int nl = f->nl;
   uint64_t w[OF_MAXL];
   of_ntt_omega(fid, lg, w);
   uint64_t *roots = roots_table(f, lg, w);
-  uint64_t a[OF_MAXL], b[OF_MAXL], d[OF_MAXL];
   for (size_t gap = len / 2; gap > 0; gap /= 2) {
-    size_t nchunks = len / (2 * gap);
-    for (size_t c = 0; c < nchunks; c++) {
-      uint64_t *base = x + c * 2 * gap * nl;
-      for (size_t i = 0; i < gap; i++) {
-        memcpy(a, base + i * nl, sizeof(uint64_t) * nl);
-        memcpy(b, base + (i + gap) * nl, sizeof(uint64_t) * nl);
-        of_mont_add(f, a, b, base + i * nl);
-        of_mont_sub(f, a, b, d);
-        of_mont_mul(f, d, roots + nchunks * i * nl, base + (i + gap) * nl);
-      }
-    }
+    stage_ctx sc = {f, x, roots, gap, len / (2 * gap)};
+    of_parallel_for(len / 2, STAGE_MIN_CHUNK, dif_stage, &sc);
   }
   free(roots);
 #if !LCPC_FFT_OUTPUT_BITREV
-  bitrev_permute(x, lg, nl);
+  bitrev_permute(x, lg, f->nl);
 #endif
   return 0;
 }
@@ -119,21 +155,12 @@ int of_ifft_oi(int fid, uint64_t *x, size_t len) {
   of_ntt_omega(fid, lg, w);
   of_inv(fid, w, wi);
   uint64_t *roots = roots_table(f, lg, wi);
-  uint64_t a[OF_MAXL], b[OF_MAXL];
 #if !LCPC_FFT_OUTPUT_BITREV
   bitrev_permute(x, lg, nl);  /* natural-order evaluations in: the DIT below reads bit-reversed */
 #endif
   for (size_t gap = 1; gap < len; gap *= 2) {
-    size_t nchunks = len / (2 * gap);
-    for (size_t c = 0; c < nchunks; c++) {
-      uint64_t *base = x + c * 2 * gap * nl;
-      for (size_t i = 0; i < gap; i++) {
-        memcpy(a, base + i * nl, sizeof(uint64_t) * nl);
-        of_mont_mul(f, base + (i + gap) * nl, roots + nchunks * i * nl, b);
-        of_mont_add(f, a, b, base + i * nl);
-        of_mont_sub(f, a, b, base + (i + gap) * nl);
-      }
-    }
+    stage_ctx sc = {f, x, roots, gap, len / (2 * gap)};
+    of_parallel_for(len / 2, STAGE_MIN_CHUNK, dit_stage, &sc);
   }
   /* multiply by len^-1 */
   uint64_t n_m[OF_MAXL] = {0, 0, 0, 0}, n_c[OF_MAXL] = {(uint64_t)len, 0, 0, 0}, ninv[OF_MAXL];

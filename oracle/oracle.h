@@ -136,7 +136,10 @@ typedef struct of_proof {
   uint64_t *col_idx;      /* indices the prover opened (informational) */
 } of_proof;
 
+/* threads of the parallel loops (rows of a commitment, columns of a hash, the butterflies of one
+ * NTT stage); n < 1 counts as 1.  No output bit depends on it. */
 void of_set_threads(int n);
+int of_get_threads(void);
 of_commit *of_commit_new(const of_enc *e, const uint64_t *coeffs, size_t len);
 void of_commit_free(of_commit *c);
 of_proof *of_prove(const of_commit *c, const of_enc *e, const uint64_t *outer, of_transcript *tr,

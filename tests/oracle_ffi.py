@@ -132,6 +132,7 @@ def _setup(L):
         "of_enc_encode": (C.c_int, [C.POINTER(OfEnc), u64p]),
         "of_enc_encode_rows": (C.c_int, [C.POINTER(OfEnc), u64p, C.c_size_t, C.c_size_t, u64p]),
         "of_set_threads": (None, [C.c_int]),
+        "of_get_threads": (C.c_int, []),
         "of_commit_new": (C.POINTER(OfCommit), [C.POINTER(OfEnc), u64p, C.c_size_t]),
         "of_commit_free": (None, [C.POINTER(OfCommit)]),
         "of_prove": (C.POINTER(OfProof), [C.POINTER(OfCommit), C.POINTER(OfEnc), u64p, C.c_void_p,

@@ -179,7 +179,44 @@ def test_compute_fails_loudly_without_device(api):
         lambda: api.hash_columns(1, np.zeros(16, np.uint64), 2, 4),
         lambda: api.selftest_field_op(1, "mul", np.zeros(2, np.uint64), np.zeros(2, np.uint64)),
         lambda: api.selftest_recombine(np.zeros(16, np.int32)),
+        lambda: api.selftest_ntt_rows(1, 3, np.zeros(16, np.uint64), 8, np.zeros(16, np.uint64)),
     ]
     for fn in calls:
         with pytest.raises(api.DeviceError):
             fn()
+
+
+NTT_MAX_LOG_N = {0: 24, 1: 24, 2: 22, 3: 22, 4: 22}  # include/lcpc_mi.h, lcpc_selftest_ntt_rows
+
+
+@pytest.mark.parametrize("fid", range(5))
+def test_selftest_ntt_rows_refuses_before_the_device(native, api, fid):
+    """lcpc_selftest_ntt_rows validates its arguments before it asks for a device, so the refusals
+    carry their own status with or without one (a call that got past them would raise the
+    no-device DeviceError here, or succeed on a GPU machine: either way not these codes)."""
+    call = native.load().lcpc_selftest_ntt_rows
+    nl = api.limbs(fid)
+    n = 16
+    src, dst, cp = (np.zeros(3 * n * nl, np.uint64) for _ in range(3))
+    p = api._p64
+    INVALID, UNSUPPORTED = 30, 34
+    ok = dict(f=fid, log_n=4, inverse=0, src=p(src), ss=n, nv=n, dst=p(dst), ds=n, rows=2, copy=p(cp), cs=n, canon=0)
+
+    def status(**kw):
+        a = {**ok, **kw}
+        return call(a["f"], a["log_n"], a["inverse"], a["src"], a["ss"], a["nv"], a["dst"], a["ds"], a["rows"],
+                    a["copy"], a["cs"], a["canon"])
+
+    assert status(f=5) == INVALID and status(f=-1) == INVALID
+    assert status(src=None) == INVALID and status(dst=None) == INVALID
+    assert status(log_n=-1) == INVALID
+    assert status(nv=n + 1, ss=n + 1, cs=n + 1) == INVALID  # n_valid > 2^log_n
+    assert status(ss=n - 1) == INVALID and status(ds=n - 1) == INVALID and status(cs=n - 1) == INVALID
+    assert status(canon=1, inverse=1) == INVALID
+    top = NTT_MAX_LOG_N[fid]
+    assert status(log_n=top + 1) == UNSUPPORTED and status(log_n=62) == UNSUPPORTED
+    assert status(log_n=top + 1, inverse=1) == UNSUPPORTED
+    # in range, the same call reaches the device (status 0 with one, a device error without)
+    assert status() not in (INVALID, UNSUPPORTED)
+    assert status(copy=None, cs=0) not in (INVALID, UNSUPPORTED)
+    assert status(rows=0) == 0
