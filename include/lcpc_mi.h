@@ -37,7 +37,8 @@ extern "C" {
  * lcpc_encoding_set_digest, lcpc_commit_digest and the *_d functions): every existing symbol keeps
  * its signature and its BLAKE3 meaning.  So is the update-audit block (lcpc_eval_poly*,
  * lcpc_pos_eval_poly_bytes*, lcpc_pos_left_multiply_bytes*, lcpc_pos_update_rows,
- * lcpc_pos_update_evaluation). */
+ * lcpc_pos_update_evaluation).  So are the diagnostics added since (lcpc_selftest_field_op,
+ * lcpc_selftest_recombine, lcpc_selftest_ntt_rows, lcpc_selftest_spmm, lcpc_selftest_reed_solomon). */
 #define LCPC_ABI_VERSION 3
 
 typedef enum lcpc_status {
@@ -1057,6 +1058,37 @@ lcpc_status lcpc_selftest_recombine(const int32_t *y, uint64_t *out, size_t n);
 lcpc_status lcpc_selftest_ntt_rows(lcpc_field f, int log_n, int inverse, const uint64_t *src,
                                    size_t src_stride, size_t n_valid, uint64_t *dst, size_t dst_stride,
                                    size_t n_rows, uint64_t *copy, size_t copy_stride, int canon);
+
+/* One sparse level of the Brakedown encode, y = M x, on a matrix of the caller's: for every output
+ * j < m_rows and every row b in [b0, b0 + nb), y[j][b] = sum_k val[k] x[idx[k]][b] R^-1 mod p over
+ * k in [ptr[j], ptr[j + 1]) (Montgomery products, as the encode computes them).  The matrix is CSR
+ * by output: ptr has m_rows + 1 entries, every idx is below m_cols, val holds the field's limbs per
+ * nonzero -- raw words with NO range check, as lcpc_selftest_field_op: the caller owns the domain.
+ * x = [m_cols][R] and y = [m_rows][R] are element-major (element j of row b at j R + b), host
+ * buffers.  The matrix goes to the device by the upload every encoding's levels take, the Ft127
+ * matrix-core form (nonzeros padded to groups of 4) included, and the launch is the encode's own
+ * dispatch.  y is uploaded whole before it and downloaded whole after it: rows outside
+ * [b0, b0 + nb) return as the caller set them.
+ * path 0: the kernel an encoding would run -- the int8 matrix cores for Ft127 unless LCPC_NO_MFMA
+ * is set or some output has more than 512 nonzeros (then the VALU kernel for the whole matrix),
+ * the VALU kernel for every other field.  path 1: the VALU kernel.  *used_mfma = 1 if the
+ * matrix-core kernel ran, else 0.
+ * LCPC_ERR_INVALID_ARG, before the device is touched: an unknown field, a NULL pointer, a path
+ * other than 0 or 1, R or m_rows above 2^32 - 1, b0 + nb > R, ptr[0] != 0, a ptr that decreases,
+ * an idx >= m_cols.  nb = 0 or m_rows = 0: LCPC_OK, nothing written (*used_mfma = 0). */
+lcpc_status lcpc_selftest_spmm(lcpc_field f, size_t m_rows, size_t m_cols, const uint32_t *ptr,
+                               const uint32_t *idx, const uint64_t *val, const uint64_t *x, uint64_t *y,
+                               size_t R, size_t b0, size_t nb, int path, int *used_mfma);
+
+/* The Reed-Solomon step at the bottom of the Brakedown recursion (encode::reed_solomon), launched
+ * as the encode launches it: out[k][b] = sum_(j < m) in[j][b] (k + 1)^j mod p for k < n_out and
+ * the rows b in [b0, b0 + nb).  in = [m][R] and out = [n_out][R], element-major host buffers of
+ * Montgomery words (in < p; no range check).  out is uploaded whole first: rows outside the range
+ * return as the caller set them.  m = 0 writes zeros.
+ * LCPC_ERR_INVALID_ARG, before the device is touched: an unknown field, a NULL in or out, R, m or
+ * n_out above 2^32 - 1, b0 + nb > R.  nb = 0 or n_out = 0: LCPC_OK, nothing written. */
+lcpc_status lcpc_selftest_reed_solomon(lcpc_field f, const uint64_t *in, size_t m, uint64_t *out,
+                                       size_t n_out, size_t R, size_t b0, size_t nb);
 
 /* ------------------------------------------------------------------ kernel timing
  * HIP-event timing of every kernel launch on the handle streams (off by default). */

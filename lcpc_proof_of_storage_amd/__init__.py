@@ -14,4 +14,5 @@ from .lcpc2d import (  # noqa: F401
     n_degree_tests, log2, limbs, num_bits, set_device, device_count, field_random,
     prof_enable, prof_reset, prof_stats, selftest_pool_ordering,
     SELFTEST_OPS, selftest_fe_dot_kmax, selftest_field_op, selftest_recombine, selftest_ntt_rows,
+    selftest_spmm, selftest_reed_solomon,
 )

@@ -95,7 +95,8 @@ __device__ __forceinline__ Fe<F> redc_plus(const uint32_t x[4], uint32_t top) {
 }
 
 // The field element of a digit-position accumulator column: sum_u Y[u] 2^(8u) R^-1 mod p, for
-// |Y[u]| < 2^27 (at most 512 x 16 products of balanced digits per accumulator).
+// |Y[u]| < 2^27 (at most 512 x 16 products of balanced digits per accumulator; the sparse levels
+// of sdig.hip reach 2^26.32 at their 512-nonzero cap on operands searched for it, the tests' worst).
 template <class F>
 __device__ __forceinline__ Fe<F> recombine_redc(const int (&Y)[16]) {
   // Y = sum_u Y_u 2^(8u) as S_w = sum_j Y_(4w+j) 2^(8j) (int64), then signed carries

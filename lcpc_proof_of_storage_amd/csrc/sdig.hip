@@ -67,7 +67,10 @@ __global__ __launch_bounds__(256) void k_spmm(const uint32_t *__restrict__ ptr,
 // Lane (n = lane & 15, g = lane >> 4): A fragment = h of padded nonzero 4q + g at digit
 // position n; B fragment of tile t = the digits of x[idx][b0 + 16 t + n].  The output's
 // neighbour list (pidx) is staged in LDS first.  |Y| < 2^27 needs at most 512 nonzeros per
-// output (checked when the plan is built).
+// output (checked when the plan is built): 512 x 16 products of at most 2^14, and 2^27 itself
+// would take a residue whose digits are all -128, which is negative.  The largest a searched-for
+// (value, input) pair reaches at 512 nonzeros is 83,860,992 = 2^26.32, 0.62 of the bound
+// (tests/test_gpu_sdig_levels.py; random data stays near 2^17).
 //
 // The A fragment: lane (n, g) computes H = gval[4q + g] 2^(8n) mod p (a = n; the Montgomery
 // product with the constant 2^(8n) R mod p) and its balanced digits, i.e. bytes u = 0..15 of
@@ -321,6 +324,16 @@ hipError_t spmm(const SdigPlan &p, const CsrDev &M, const uint32_t *x, uint32_t 
   return hipGetLastError();
 }
 
+// out[k][b] = sum_j in[j][b] (k + 1)^j for k < n_out, on rows [b0, b0 + nb)
+template <class F>
+hipError_t reed_solomon(const uint32_t *in, size_t m, uint32_t *out, size_t n_out, size_t R, size_t b0, size_t nb,
+                        hipStream_t s) {
+  if (!(n_out * nb)) return hipSuccess;
+  hipLaunchKernelGGL((k_reed_solomon<F>), dim3((unsigned)((n_out * nb + 255) / 256)), dim3(256), 0, s, in, m, out,
+                     n_out, (uint32_t)R, (uint32_t)b0, (uint32_t)nb);
+  return hipGetLastError();
+}
+
 template <class F>
 hipError_t encode_rows_slice(const SdigPlan &p, uint32_t *cw, size_t R, size_t b0, size_t nb, uint32_t *tmp,
                              hipStream_t s) {
@@ -340,11 +353,7 @@ hipError_t encode_rows_slice(const SdigPlan &p, uint32_t *cw, size_t R, size_t b
   const size_t in_end = in_start + ML.cols;
   if ((e = spmm<F>(p, ML, cw + in_start * R * N, tmp, R, b0, nb, s)) != hipSuccess) return e;
   const size_t n_rs = p.post[L - 1].cols;
-  if (n_rs * nb) {
-    hipLaunchKernelGGL((k_reed_solomon<F>), dim3((unsigned)((n_rs * nb + 255) / 256)), dim3(256), 0,
-                       s, tmp, ML.rows, cw + in_end * R * N, n_rs, (uint32_t)R, (uint32_t)b0, (uint32_t)nb);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
+  if ((e = reed_solomon<F>(tmp, ML.rows, cw + in_end * R * N, n_rs, R, b0, nb, s)) != hipSuccess) return e;
   // postcodes in reverse (:76-90): input [in_start, out_start), output at out_start
   size_t in_pos = in_end + ML.rows, out_pos = in_end + n_rs;
   for (int i = L - 1; i >= 0; i--) {
@@ -371,8 +380,11 @@ hipError_t encode_cm(const SdigPlan &p, uint32_t *cw, size_t R, uint32_t *tmp, h
 hipError_t sdig_plan_mfma(SdigPlan &plan, const std::vector<CsrHost> &pre, const std::vector<CsrHost> &post,
                           hipStream_t s);
 
-hipError_t sdig_plan_upload(SdigPlan &plan, int fid, const std::vector<CsrHost> &pre,
-                            const std::vector<CsrHost> &post, hipStream_t s) {
+// Every matrix of pre and post onto the device: the CSR form of each in one allocation, then the
+// matrix-core forms (sdig_plan_mfma).  Shared by sdig_plan_upload and sdig_selftest_spmm, whose
+// one matrix takes the same layout and the same group padding as a plan's levels.
+static hipError_t plan_upload_matrices(SdigPlan &plan, int fid, const std::vector<CsrHost> &pre,
+                                       const std::vector<CsrHost> &post, hipStream_t s) {
   const int N = field_words(fid);
   auto bytes_of = [&](const CsrHost &h) {
     const size_t a = ((h.rows + 1) * 4 + 255) & ~(size_t)255;
@@ -386,9 +398,6 @@ hipError_t sdig_plan_upload(SdigPlan &plan, int fid, const std::vector<CsrHost> 
   hipError_t e = hipMalloc(&plan.d_buf, total ? total : 256);
   if (e != hipSuccess) return e;
   plan.fid = fid;
-  plan.n_per_row = pre[0].cols;
-  plan.n_cols = sdig_codeword_length(pre, post);
-  plan.tmp_elems = pre.back().rows;
   uint8_t *cur = (uint8_t *)plan.d_buf;
   auto put = [&](const CsrHost &h, CsrDev &d) -> hipError_t {
     d.rows = h.rows;
@@ -416,6 +425,28 @@ hipError_t sdig_plan_upload(SdigPlan &plan, int fid, const std::vector<CsrHost> 
     if ((e = put(post[i], plan.post[i])) != hipSuccess) return e;
   if ((e = sdig_plan_mfma(plan, pre, post, s)) != hipSuccess) return e;
   return hipStreamSynchronize(s);  // host vectors may be freed after return
+}
+
+hipError_t sdig_plan_upload(SdigPlan &plan, int fid, const std::vector<CsrHost> &pre,
+                            const std::vector<CsrHost> &post, hipStream_t s) {
+  plan.n_per_row = pre[0].cols;
+  plan.n_cols = sdig_codeword_length(pre, post);
+  plan.tmp_elems = pre.back().rows;
+  return plan_upload_matrices(plan, fid, pre, post, s);
+}
+
+hipError_t sdig_selftest_spmm(int fid, const CsrHost &M, const uint32_t *x, uint32_t *y, size_t R, size_t b0,
+                              size_t nb, bool force_valu, bool *used_mfma, hipStream_t s) {
+  SdigPlan plan;
+  hipError_t e = plan_upload_matrices(plan, fid, {M}, {}, s);
+  if (e == hipSuccess) {
+    if (force_valu) plan.mfma = false;
+    *used_mfma = plan.mfma;
+    e = dispatch_field(fid, [&]<class F>() { return spmm<F>(plan, plan.pre[0], x, y, R, b0, nb, s); });
+  }
+  const hipError_t e2 = hipStreamSynchronize(s);  // the plan's buffers are freed below
+  sdig_plan_free(plan);
+  return e != hipSuccess ? e : e2;
 }
 
 // The matrix-core forms of every level (Ft127; LCPC_NO_MFMA=1 keeps the VALU kernel for A/B
@@ -476,6 +507,11 @@ hipError_t sdig_plan_mfma(SdigPlan &plan, const std::vector<CsrHost> &pre, const
   if (e == hipSuccess) e = hipStreamSynchronize(s);  // the host forms are freed on return
   if (e == hipSuccess) plan.mfma = true;
   return e;
+}
+
+hipError_t sdig_selftest_reed_solomon(int fid, const uint32_t *in, size_t m, uint32_t *out, size_t n_out, size_t R,
+                                      size_t b0, size_t nb, hipStream_t s) {
+  return dispatch_field(fid, [&]<class F>() { return reed_solomon<F>(in, m, out, n_out, R, b0, nb, s); });
 }
 
 void sdig_plan_free(SdigPlan &plan) {

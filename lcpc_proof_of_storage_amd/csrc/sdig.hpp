@@ -76,6 +76,18 @@ void sdig_plan_free(SdigPlan &plan);
 // row): writes the rest of every codeword.  tmp holds tmp_elems * R elements.
 hipError_t sdig_encode_cm(const SdigPlan &plan, uint32_t *cw, size_t R, uint32_t *tmp,
                           hipStream_t s);
+// One sparse level on a caller's matrix (lcpc_selftest_spmm): M goes to the device as a plan's
+// levels do (the same upload, the same matrix-core form), then y[j][b] = sum_k val_k x[idx_k][b]
+// for b in [b0, b0 + nb) by the dispatch the encode uses; x = [M.cols][R], y = [M.rows][R], device
+// pointers.  force_valu takes the VALU kernel where the plan would take the matrix cores;
+// *used_mfma = the matrix-core kernel ran.  Returns after the stream has drained.
+hipError_t sdig_selftest_spmm(int fid, const CsrHost &M, const uint32_t *x, uint32_t *y, size_t R, size_t b0,
+                              size_t nb, bool force_valu, bool *used_mfma, hipStream_t s);
+// The base-case Reed-Solomon step of the encode by its own launcher (lcpc_selftest_reed_solomon):
+// out[k][b] = sum_j in[j][b] (k + 1)^j, j < m, k < n_out, rows [b0, b0 + nb); in = [m][R],
+// out = [n_out][R], device pointers.
+hipError_t sdig_selftest_reed_solomon(int fid, const uint32_t *in, size_t m, uint32_t *out, size_t n_out, size_t R,
+                                      size_t b0, size_t nb, hipStream_t s);
 
 // dst[c][r] = src[r][c] (element units, row strides src_stride / dst_stride) for r < rows,
 // c < cols; source columns c >= n_valid, and flat source offsets r * src_stride + c >= n_flat,

@@ -10,7 +10,9 @@
 // evidence for the pool that the commit / prove / shard paths share.
 //
 // lcpc_selftest_ntt_rows (at the end): the NTT dispatch called directly, for the row lengths and
-// pass variants that no commit-sized test can isolate.
+// pass variants that no commit-sized test can isolate.  lcpc_selftest_spmm (after it): one
+// Brakedown level on a caller's matrix, for the kernels and bounds matgen's matrices never reach,
+// and lcpc_selftest_reed_solomon, the Reed-Solomon step under the last level.
 #include "host_internal.hpp"
 
 #include <vector>
@@ -161,6 +163,75 @@ extern "C" lcpc_status lcpc_selftest_ntt_rows(lcpc_field f, int log_n, int inver
                    copy_b ? dc.as<uint32_t>() : nullptr, copy_stride, canon != 0));
   HIP_TRY(hipMemcpyAsync(dst, dd.p, dst_b, hipMemcpyDeviceToHost, lease.s));
   if (copy_b) HIP_TRY(hipMemcpyAsync(copy, dc.p, copy_b, hipMemcpyDeviceToHost, lease.s));
+  HIP_TRY(hipStreamSynchronize(lease.s));
+  return LCPC_OK;
+}
+
+// One Brakedown level y = M x (sdig.hip) on a matrix the caller wrote: nonzero counts, indices
+// and values that matgen never draws (an empty output, 512 nonzeros, 513, every value p - 1), any
+// R and any row range.  The matrix takes the plan's own upload and group padding and the launch
+// is the encode's spmm; y is uploaded whole first, so rows outside the range return untouched.
+extern "C" lcpc_status lcpc_selftest_spmm(lcpc_field f, size_t m_rows, size_t m_cols, const uint32_t *ptr,
+                                          const uint32_t *idx, const uint64_t *val, const uint64_t *x, uint64_t *y,
+                                          size_t R, size_t b0, size_t nb, int path, int *used_mfma) {
+  if (!valid_field(f)) return fail(LCPC_ERR_INVALID_ARG, "field");
+  if (!ptr || !idx || !val || !x || !y || !used_mfma) return fail(LCPC_ERR_INVALID_ARG, "null argument");
+  if (path != 0 && path != 1) return fail(LCPC_ERR_INVALID_ARG, "path");
+  if (R > UINT32_MAX || m_rows > UINT32_MAX) return fail(LCPC_ERR_INVALID_ARG, "R or m_rows above 2^32 - 1");
+  if (b0 > R || nb > R - b0) return fail(LCPC_ERR_INVALID_ARG, "b0 + nb > R");
+  if (ptr[0] != 0) return fail(LCPC_ERR_INVALID_ARG, "ptr[0] != 0");
+  for (size_t j = 0; j < m_rows; j++)
+    if (ptr[j + 1] < ptr[j]) return fail(LCPC_ERR_INVALID_ARG, "ptr decreases");
+  const size_t nnz = ptr[m_rows];
+  for (size_t k = 0; k < nnz; k++)
+    if (idx[k] >= m_cols) return fail(LCPC_ERR_INVALID_ARG, "idx >= m_cols");
+  *used_mfma = 0;
+  if (nb == 0 || m_rows == 0) return LCPC_OK;
+  lcpc_status st;
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  const size_t wb = field_bytes(f);
+  CsrHost M;
+  M.rows = m_rows;
+  M.cols = m_cols;
+  M.ptr.assign(ptr, ptr + m_rows + 1);
+  M.idx.assign(idx, idx + nnz);
+  M.val.assign(val, val + nnz * (wb / 8));
+  DBuf dx, dy;
+  if ((st = upload(dev, dx, x, m_cols * R * wb))) return st;
+  if ((st = upload(dev, dy, y, m_rows * R * wb))) return st;
+  bool mfma = false;
+  HIP_TRY(sdig_selftest_spmm(f, M, dx.as<uint32_t>(), dy.as<uint32_t>(), R, b0, nb, path == 1, &mfma, lease.s));
+  *used_mfma = mfma ? 1 : 0;
+  HIP_TRY(hipMemcpyAsync(y, dy.p, m_rows * R * wb, hipMemcpyDeviceToHost, lease.s));
+  HIP_TRY(hipStreamSynchronize(lease.s));
+  return LCPC_OK;
+}
+
+// The Reed-Solomon step at the bottom of the Brakedown recursion (k_reed_solomon, sdig.hip) on the
+// caller's input: the encode feeds it the last precode's outputs only, never p - 1 in every
+// element.  The launch is the encode's; out is uploaded whole first, as y above.
+extern "C" lcpc_status lcpc_selftest_reed_solomon(lcpc_field f, const uint64_t *in, size_t m, uint64_t *out,
+                                                  size_t n_out, size_t R, size_t b0, size_t nb) {
+  if (!valid_field(f)) return fail(LCPC_ERR_INVALID_ARG, "field");
+  if (!in || !out) return fail(LCPC_ERR_INVALID_ARG, "null in or out");
+  if (R > UINT32_MAX || n_out > UINT32_MAX || m > UINT32_MAX)
+    return fail(LCPC_ERR_INVALID_ARG, "R, m or n_out above 2^32 - 1");
+  if (b0 > R || nb > R - b0) return fail(LCPC_ERR_INVALID_ARG, "b0 + nb > R");
+  if (nb == 0 || n_out == 0) return LCPC_OK;
+  lcpc_status st;
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  const size_t wb = field_bytes(f);
+  DBuf din, dout;
+  if ((st = upload(dev, din, in, m * R * wb))) return st;
+  if ((st = upload(dev, dout, out, n_out * R * wb))) return st;
+  HIP_TRY(sdig_selftest_reed_solomon(f, din.as<uint32_t>(), m, dout.as<uint32_t>(), n_out, R, b0, nb, lease.s));
+  HIP_TRY(hipMemcpyAsync(out, dout.p, n_out * R * wb, hipMemcpyDeviceToHost, lease.s));
   HIP_TRY(hipStreamSynchronize(lease.s));
   return LCPC_OK;
 }

@@ -222,6 +222,59 @@ def selftest_ntt_rows(field: int, log_n: int, src: np.ndarray, n_valid: int, dst
     return dst
 
 
+def selftest_spmm(field: int, ptr, idx, val, x: np.ndarray, y: np.ndarray, *, b0: int = 0,
+                  nb: Optional[int] = None, path: int = 0):
+    """One sparse level of the Brakedown encode on the caller's CSR matrix (lcpc_selftest_spmm):
+    y[j][b] = sum_k val[k] x[idx[k]][b] R^-1 mod p over the nonzeros [ptr[j], ptr[j + 1]) of output
+    j, for the rows b in [b0, b0 + nb) (default: from b0 to R).  val holds raw element words (no
+    range check); x has shape (m_cols, R, limbs) and y (m_rows, R, limbs), C-contiguous uint64, and
+    y is written in place: what lies outside the row range keeps the caller's words.  path 0 is
+    the kernel an encoding would run, path 1 the VALU kernel.  Returns (y, used_mfma)."""
+    nl = limbs(field)
+    for a in (x, y):
+        if a.dtype != np.uint64 or not a.flags["C_CONTIGUOUS"] or a.ndim != 3 or a.shape[2] != nl:
+            raise TypeError("selftest_spmm needs C-contiguous uint64 arrays of shape (n, R, limbs) (y: written in place)")
+    (m_cols, R, _), m_rows = x.shape, y.shape[0]
+    if y.shape[1] != R:
+        raise ValueError("x and y differ in R")
+    ptr = np.ascontiguousarray(ptr, dtype=np.uint32)
+    if len(ptr) != m_rows + 1:
+        raise ValueError("ptr must hold m_rows + 1 entries")
+    nnz = int(ptr[-1])
+    if len(idx) != nnz or len(val) != nnz:
+        raise ValueError("idx and val must hold ptr[-1] nonzeros")
+
+    def spare(a):  # an empty array still needs an address to pass
+        return a if a.size else np.zeros(nl, a.dtype)
+    idx = spare(np.ascontiguousarray(idx, dtype=np.uint32))
+    val = spare(np.ascontiguousarray(val, dtype=np.uint64))
+    used = C.c_int(0)
+    _raise(N.load().lcpc_selftest_spmm(field, m_rows, m_cols, ptr.ctypes.data_as(N.u32p), idx.ctypes.data_as(N.u32p),
+                                       _p64(val), _p64(spare(x)), _p64(spare(y)), R, b0, R - b0 if nb is None else nb,
+                                       path, C.byref(used)))
+    return y, used.value
+
+
+def selftest_reed_solomon(field: int, inp: np.ndarray, out: np.ndarray, *, b0: int = 0,
+                          nb: Optional[int] = None) -> np.ndarray:
+    """The Reed-Solomon step of the Brakedown encode (lcpc_selftest_reed_solomon):
+    out[k][b] = sum_j inp[j][b] (k + 1)^j for the rows b in [b0, b0 + nb) (default: from b0 to R).
+    inp has shape (m, R, limbs), out (n_out, R, limbs), C-contiguous uint64; out is written in
+    place and keeps the caller's words outside the row range.  Returns out."""
+    nl = limbs(field)
+    for a in (inp, out):
+        if a.dtype != np.uint64 or not a.flags["C_CONTIGUOUS"] or a.ndim != 3 or a.shape[2] != nl:
+            raise TypeError("selftest_reed_solomon needs C-contiguous uint64 arrays of shape (n, R, limbs)")
+    R = out.shape[1]
+    if inp.shape[1] != R:
+        raise ValueError("inp and out differ in R")
+    pi = _p64(inp if inp.size else np.zeros(nl, np.uint64))
+    po = _p64(out if out.size else np.zeros(nl, np.uint64))
+    _raise(N.load().lcpc_selftest_reed_solomon(field, pi, inp.shape[0], po, out.shape[0], R, b0,
+                                               R - b0 if nb is None else nb))
+    return out
+
+
 def set_device(device: int):
     _raise(N.load().lcpc_set_device(device), DeviceError)
 

@@ -180,6 +180,9 @@ def test_compute_fails_loudly_without_device(api):
         lambda: api.selftest_field_op(1, "mul", np.zeros(2, np.uint64), np.zeros(2, np.uint64)),
         lambda: api.selftest_recombine(np.zeros(16, np.int32)),
         lambda: api.selftest_ntt_rows(1, 3, np.zeros(16, np.uint64), 8, np.zeros(16, np.uint64)),
+        lambda: api.selftest_spmm(1, [0, 1], [0], np.zeros((1, 2), np.uint64), np.zeros((1, 4, 2), np.uint64),
+                                  np.zeros((1, 4, 2), np.uint64)),
+        lambda: api.selftest_reed_solomon(1, np.zeros((3, 4, 2), np.uint64), np.zeros((5, 4, 2), np.uint64)),
     ]
     for fn in calls:
         with pytest.raises(api.DeviceError):
@@ -220,3 +223,67 @@ def test_selftest_ntt_rows_refuses_before_the_device(native, api, fid):
     assert status() not in (INVALID, UNSUPPORTED)
     assert status(copy=None, cs=0) not in (INVALID, UNSUPPORTED)
     assert status(rows=0) == 0
+
+
+@pytest.mark.parametrize("fid", range(5))
+def test_selftest_spmm_refuses_before_the_device(native, api, fid):
+    """lcpc_selftest_spmm validates the matrix and the row range before it asks for a device (as
+    lcpc_selftest_ntt_rows above): the refusals carry LCPC_ERR_INVALID_ARG with or without one."""
+    import ctypes as C
+    call = native.load().lcpc_selftest_spmm
+    nl = api.limbs(fid)
+    m_rows, m_cols, R = 3, 4, 5
+    ptr = np.array([0, 2, 2, 5], np.uint32)
+    idx = np.array([0, 3, 1, 1, 2], np.uint32)
+    val, x, y = (np.zeros(n * nl, np.uint64) for n in (5, m_cols * R, m_rows * R))
+    used = C.c_int(-1)
+    p32 = lambda a: a.ctypes.data_as(native.u32p)  # noqa: E731
+    p = api._p64
+    INVALID = 30
+    ok = dict(f=fid, m_rows=m_rows, m_cols=m_cols, ptr=p32(ptr), idx=p32(idx), val=p(val), x=p(x), y=p(y), R=R, b0=0,
+              nb=R, path=0, used=C.byref(used))
+
+    def status(**kw):
+        a = {**ok, **kw}
+        return call(a["f"], a["m_rows"], a["m_cols"], a["ptr"], a["idx"], a["val"], a["x"], a["y"], a["R"], a["b0"],
+                    a["nb"], a["path"], a["used"])
+
+    assert status(f=5) == INVALID and status(f=-1) == INVALID
+    for name in ("ptr", "idx", "val", "x", "y", "used"):
+        assert status(**{name: None}) == INVALID, name
+    assert status(path=2) == INVALID and status(path=-1) == INVALID
+    assert status(ptr=p32(np.array([0, 3, 2, 5], np.uint32))) == INVALID  # not monotone
+    assert status(ptr=p32(np.array([1, 2, 2, 5], np.uint32))) == INVALID  # ptr[0] != 0
+    assert status(idx=p32(np.array([0, 3, 1, 4, 2], np.uint32))) == INVALID  # idx >= m_cols
+    assert status(m_cols=3) == INVALID
+    assert status(b0=1, nb=R) == INVALID and status(b0=R + 1, nb=0) == INVALID and status(b0=0, nb=R + 1) == INVALID
+    assert status(b0=2**64 - 1, nb=2) == INVALID  # b0 + nb wraps
+    assert status(R=2**32, nb=1) == INVALID and status(m_rows=2**32) == INVALID
+    # nothing to do: LCPC_OK without a device, y untouched
+    y[:] = 7
+    assert status(nb=0) == 0 and status(b0=R, nb=0) == 0 and status(m_rows=0) == 0
+    assert used.value == 0 and np.all(y == 7)
+    # in range, the same call reaches the device (status 0 with one, a device error without)
+    assert status() != INVALID and status(b0=1, nb=R - 1, path=1) != INVALID
+
+
+@pytest.mark.parametrize("fid", range(5))
+def test_selftest_reed_solomon_refuses_before_the_device(native, api, fid):
+    call = native.load().lcpc_selftest_reed_solomon
+    nl = api.limbs(fid)
+    m, n_out, R = 3, 4, 5
+    inp, out = np.zeros(m * R * nl, np.uint64), np.full(n_out * R * nl, 7, np.uint64)
+    p = api._p64
+    INVALID = 30
+    ok = dict(f=fid, inp=p(inp), m=m, out=p(out), n_out=n_out, R=R, b0=0, nb=R)
+
+    def status(**kw):
+        a = {**ok, **kw}
+        return call(a["f"], a["inp"], a["m"], a["out"], a["n_out"], a["R"], a["b0"], a["nb"])
+
+    assert status(f=5) == INVALID and status(f=-1) == INVALID
+    assert status(inp=None) == INVALID and status(out=None) == INVALID
+    assert status(b0=1) == INVALID and status(nb=R + 1) == INVALID and status(b0=2**64 - 1, nb=2) == INVALID
+    assert status(R=2**32, nb=1) == INVALID and status(n_out=2**32) == INVALID and status(m=2**32) == INVALID
+    assert status(nb=0) == 0 and status(n_out=0) == 0 and np.all(out == 7)
+    assert status() != INVALID and status(m=0) != INVALID

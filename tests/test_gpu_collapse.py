@@ -68,9 +68,12 @@ def test_collapse_device_form_matches_host_form(gpu, oracle, n_t):
 # sign s and -128 elsewhere, so that every product h[a][u] d_a of the column has the same sign and
 # Y_u grows by about 2^17 per row, the most any coefficient can give.
 ADV_SHAPES = [(64, 70), (600, 70), (37, 100)]
-ADV_TARGETS = [(u, s) for u in (0, 7, 14, 15) for s in (1, -1)]
-ADV_PER_ROW = (1 << 26) // 512  # the floor asserted below: half of the 2^27 bound per 512 rows
-ADV_CANDIDATES = 20000
+# The search for T and the construction of x live in mfma_adv.py, shared with the sparse levels of
+# sdig.hip (test_gpu_sdig_levels.py), which use the same digit scheme.
+from mfma_adv import ADV_PER_ROW, ADV_TARGETS  # noqa: E402
+from mfma_adv import adversarial_coefficient as _adversarial_coefficient  # noqa: E402
+from mfma_adv import adversarial_tensor_words as _adversarial_tensor_words  # noqa: E402
+from mfma_adv import residue_digits as _residue_digits  # noqa: E402
 
 
 def _mfma_rows_per_split(n_rows, n_per_row):
@@ -79,50 +82,6 @@ def _mfma_rows_per_split(n_rows, n_per_row):
     splits = min((512 + blocks_x - 1) // blocks_x, (n_rows + 15) // 16)
     splits = max(splits, (n_rows + 511) // 512, 1)
     return (n_rows + splits - 1) // splits
-
-
-def _residue_digits(fr, T):
-    import field_ref as FR
-    return [FR.balanced_digits((T << (8 * a)) % fr.p) for a in range(16)]  # h[a][u]
-
-
-_ADV_WORDS = {}
-
-
-def _adversarial_tensor_words(fr, n_t):
-    """One T per tensor from a fixed-seed search (done once): the candidates whose smallest
-    sum_a |h[a][u]| over the targeted digit positions is largest."""
-    if not _ADV_WORDS:
-        _ADV_WORDS[0] = _search_tensor_words(fr, 3)
-    return _ADV_WORDS[0][:n_t]
-
-
-def _search_tensor_words(fr, n_t):
-    import random
-    rng = random.Random(0xADC0)
-    cands = [rng.randrange(fr.p) for _ in range(ADV_CANDIDATES)]
-    off = int.from_bytes(b"\x80" * 16, "little")
-    us = sorted({u for u, _ in ADV_TARGETS})
-
-    def score(T):
-        tot = [0] * 16
-        for a in range(16):
-            for u, byte in enumerate((((T << (8 * a)) % fr.p) + off).to_bytes(16, "little")):
-                tot[u] += abs(byte - 128)
-        return min(tot[u] for u in us)
-    return sorted(cands, key=score, reverse=True)[:n_t]
-
-
-def _adversarial_coefficient(fr, h, u, s):
-    """x in [0, p) whose digits d_a (a < 15) are 127 where h[a][u] has sign s, else -128."""
-    d = [127 if h[a][u] * s > 0 else -128 for a in range(15)]
-    low = sum(v << (8 * a) for a, v in enumerate(d))
-    d15_min = 0 if low >= 0 else 1
-    d15_max = min((fr.p - 1 - low) >> 120, 127)
-    d15 = d15_max if h[15][u] * s > 0 else d15_min
-    x = low + (d15 << 120)
-    assert 0 <= x < fr.p
-    return x
 
 
 @pytest.mark.parametrize("n_rows,n_per_row", ADV_SHAPES)
