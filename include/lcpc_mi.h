@@ -38,7 +38,7 @@ extern "C" {
  * its signature and its BLAKE3 meaning.  So is the update-audit block (lcpc_eval_poly*,
  * lcpc_pos_eval_poly_bytes*, lcpc_pos_left_multiply_bytes*, lcpc_pos_update_rows,
  * lcpc_pos_update_evaluation).  So are the diagnostics added since (lcpc_selftest_field_op,
- * lcpc_selftest_recombine, lcpc_selftest_ntt_rows, lcpc_selftest_spmm, lcpc_selftest_reed_solomon). */
+ * lcpc_selftest_recombine, lcpc_selftest_twiddle_words, lcpc_selftest_ntt_rows, lcpc_selftest_spmm, lcpc_selftest_reed_solomon). */
 #define LCPC_ABI_VERSION 3
 
 typedef enum lcpc_status {
@@ -1019,7 +1019,10 @@ typedef enum lcpc_selftest_op {
   LCPC_SELFTEST_IS_CANONICAL = 17, /* fe_is_canonical: out = 1 if a < p else 0 (any a < R); b unused */
   LCPC_SELFTEST_POW = 18,          /* fe_pow(a, e), e = the low 64 bits of b[i] */
   LCPC_SELFTEST_BALANCED_DIGITS = 19, /* Ft127 only: the 16 int8 digits of a < p, digit j in byte j; b unused */
-  LCPC_SELFTEST_N_OPS = 20
+  LCPC_SELFTEST_MUL_TW = 20,       /* Ft127 only: fe_mul_tw(a[i], W), W = the 2 limbs elements b[2 limbs i ..], the
+                                      word-expanded constant of w (lcpc_selftest_twiddle_words): a w + m p
+                                      over 2^64, in [0, 2p)               (a < 2p, every W_j < p) */
+  LCPC_SELFTEST_N_OPS = 21
 } lcpc_selftest_op;
 
 /* The largest k of LCPC_SELFTEST_DOT for a field (fe_dot_kmax: k p < R); 0 for an unknown field. */
@@ -1027,7 +1030,7 @@ int lcpc_selftest_fe_dot_kmax(lcpc_field f);
 
 /* out[i] = op(a[i], b[i]) for i < n.  k is fe_dot's number of products (1 for every other op).
  * LCPC_ERR_INVALID_ARG, before the device is touched: an unknown field or op, k < 1 or
- * k > lcpc_selftest_fe_dot_kmax(f), LCPC_SELFTEST_BALANCED_DIGITS on another field than Ft127,
+ * k > lcpc_selftest_fe_dot_kmax(f), LCPC_SELFTEST_BALANCED_DIGITS or _MUL_TW on another field than Ft127,
  * a NULL a or out, a NULL b where the op reads b. */
 lcpc_status lcpc_selftest_field_op(lcpc_field f, int op, int k, const uint64_t *a, const uint64_t *b,
                                    uint64_t *out, size_t n);
@@ -1036,6 +1039,12 @@ lcpc_status lcpc_selftest_field_op(lcpc_field f, int op, int k, const uint64_t *
  * (sum_u y_u 2^(8u)) R^-1 mod p, fully reduced, for |y_u| < 2^27.  NULL y or out:
  * LCPC_ERR_INVALID_ARG. */
 lcpc_status lcpc_selftest_recombine(const int32_t *y, uint64_t *out, size_t n);
+
+/* The word-expanded table entries the Ft127 encode passes multiply by (csrc/field.hpp, fe_mul_tw):
+ * for each of the n Montgomery values tw[i] = w R mod p (< p), out holds 2 limbs elements,
+ * out[2 limbs i + j] = w 2^(32 (j + 2)) mod p, fully reduced, made by the kernel that fills a
+ * plan's table.  LCPC_ERR_INVALID_ARG: another field than Ft127, a NULL tw or out. */
+lcpc_status lcpc_selftest_twiddle_words(lcpc_field f, const uint64_t *tw, uint64_t *out, size_t n);
 
 /* The row transform under every encode, commit and decode, called directly: n_rows rows of
  * 2^log_n points on a plan made for the call.  Row r reads the n_valid leading elements at

@@ -278,6 +278,7 @@ SIGNATURES = {
     "lcpc_selftest_fe_dot_kmax": (i32, [i32]),
     "lcpc_selftest_field_op": (i32, [i32, i32, i32, u64p, u64p, u64p, sz]),
     "lcpc_selftest_recombine": (i32, [C.POINTER(C.c_int32), u64p, sz]),
+    "lcpc_selftest_twiddle_words": (i32, [i32, u64p, u64p, sz]),
     "lcpc_selftest_ntt_rows": (i32, [i32, i32, i32, u64p, sz, sz, u64p, sz, sz, u64p, sz, i32]),
     "lcpc_selftest_spmm": (i32, [i32, sz, sz, u32p, u32p, u64p, u64p, u64p, sz, sz, sz, i32, C.POINTER(C.c_int)]),
     "lcpc_selftest_reed_solomon": (i32, [i32, u64p, sz, u64p, sz, sz, sz, sz]),

@@ -411,6 +411,139 @@ __device__ __forceinline__ Fe<F> fe_mul_lazy(const Fe<F>& a, const Fe<F>& b) {
   return fe_mul_fips<F, true>(a, b);
 }
 
+// ---- product by a word-expanded constant: two Montgomery word-steps instead of N.
+// For a table constant w, keep the N canonical values W_i = w 2^(32 (i + 2)) mod p (W_(N-2) is
+// w R, the Montgomery form).  With x = sum_i x_i 2^(32 i),
+//     T = sum_i x_i W_i  =  x w 2^64  (mod p),     T < N 2^32 p,
+// so two word-steps (m = -T_0, T += m p, T >>= 32; p = 1 mod 2^32) leave
+//     y = (T + m_0 p + m_1 p 2^32) / 2^64  =  x w  (mod p),     y < p (N 2^-32 + 1) < 2p:
+// the class and the range of fe_mul_lazy(x, w R), from N^2 + 2 (N - 1) mads instead of
+// N^2 + N (N - 1) (Ft127: 22 for 28) and 2 column steps for N.  Any x < R is in the domain.
+// For N = 2 two steps are the whole Montgomery reduction, and one step gives y < 3p.
+//
+// Carry-free mads of column k (bit i < N: x_i W_i[k]; bit N + r: m_r p_(k-r)), chosen as
+// fips_free_mask does.  W_i < p, so W_i[N-1] <= p_(N-1); column 0 starts from 0, the others from
+// an addend below 2^37.  Ft127: column 0's first product, m_0 p_1, m_1 p_1, two of the
+// x_i W_i[3] and m_1 p_3 -- 6 of the 22 mads.
+template <class F>
+__host__ __device__ constexpr uint32_t tw_free_mask(int k) {
+  constexpr int N = F::N;
+  using u128 = unsigned __int128;
+  const u128 lim = ((u128)1 << 64) - 1;
+  const u128 w = 0xffffffffu;
+  u128 bound[N + 2] = {};
+  bool cand[N + 2] = {};
+  for (int i = 0; i < N; i++) {
+    if (k < N) {
+      cand[i] = true;
+      bound[i] = w * (k == N - 1 ? (u128)F::P[N - 1] : w);
+    }
+  }
+  for (int r = 0; r < 2; r++) {
+    const int j = k - r;
+    if (j >= 1 && j < N) {
+      cand[N + r] = true;
+      bound[N + r] = w * (u128)F::P[j];
+    }
+  }
+  u128 sum = k ? (u128)1 << 37 : 0;
+  uint32_t mask = 0;
+  for (;;) {
+    int best = -1;
+    for (int s = 0; s < N + 2; s++)
+      if (cand[s] && !((mask >> s) & 1u) && (best < 0 || bound[s] < bound[best])) best = s;
+    if (best < 0 || sum + bound[best] > lim) break;
+    sum += bound[best];
+    mask |= 1u << best;
+  }
+  return mask;
+}
+
+// x w in [0, 2p) for any x < R and the word-expanded constant W of w (above), W_i < p
+template <class F>
+__device__ __forceinline__ Fe<F> fe_mul_tw(const Fe<F>& x, const Fe<F> (&W)[F::N]) {
+  constexpr int N = F::N;
+  static_assert(F::NP == 0xffffffffu && F::P[0] == 1u, "p = 1 mod 2^32");
+  static_assert(N > 2, "N = 2: two word-steps are fe_mul_lazy itself, one leaves y < 3p");
+  static_assert(F::P[N - 1] < 0x7fffff00u, "tw_free_mask's addend bound and y < 2p < R need p < R / 2");
+  uint32_t m[2], out[N];
+  uint64_t acc = 0;
+  uint32_t r2 = 0;
+  auto column = [&]<int k>() {
+    constexpr uint32_t fm = tw_free_mask<F>(k);
+    uint64_t unused;
+    bool first = k == 0;  // column 0 starts from nothing: a plain product, no zero addend to set up
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+      if (k >= N || !((fm >> i) & 1u)) continue;
+      acc = first ? (uint64_t)x.v[i] * W[i].v[k < N ? k : 0] : mad_co_vv(x.v[i], W[i].v[k < N ? k : 0], acc, unused);
+      first = false;
+    }
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+      const int j = k - r;
+      if (j >= 1 && j < N && ((fm >> (N + r)) & 1u)) acc = mad_co_vs(m[r], F::P[j < N ? j : 0], acc, unused);
+    }
+    uint64_t cprev = 0, ccur;
+    bool have = false;
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+      if (k >= N || ((fm >> i) & 1u)) continue;
+      acc = mad_co_vv(x.v[i], W[i].v[k < N ? k : 0], acc, ccur);
+      if (have) r2 = add_carry(r2, cprev);
+      cprev = ccur;
+      have = true;
+    }
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+      const int j = k - r;
+      if (j < 1 || j >= N || ((fm >> (N + r)) & 1u)) continue;
+      acc = mad_co_vs(m[r], F::P[j < N ? j : 0], acc, ccur);
+      if (have) r2 = add_carry(r2, cprev);
+      cprev = ccur;
+      have = true;
+    }
+    if (have) r2 = add_carry(r2, cprev);
+    if constexpr (k < 2) {
+      uint32_t nlo, nhi;
+      fips_col_step((uint32_t)acc, (uint32_t)(acc >> 32), r2, m[k], nlo, nhi);
+      acc = ((uint64_t)nhi << 32) | nlo;
+    } else if constexpr (k < N) {
+      out[k - 2] = (uint32_t)acc;
+      acc = (acc >> 32) | ((uint64_t)r2 << 32);
+    } else {  // column N holds m_1 p_(N-1) alone; y < 2p < R, so nothing lies above its two words
+      out[N - 2] = (uint32_t)acc;
+      out[N - 1] = (uint32_t)(acc >> 32);
+    }
+    r2 = 0;
+  };
+  [&]<int... Ks>(std::integer_sequence<int, Ks...>) {
+    (column.template operator()<Ks>(), ...);
+  }(std::make_integer_sequence<int, N + 1>{});
+  Fe<F> r;
+#pragma unroll
+  for (int i = 0; i < N; i++) r.v[i] = out[i];
+  return r;
+}
+
+// The word-expanded constant of a Montgomery value wm = w R < p: W_i = wm c_i R^-1 with
+// c_i = 2^(32 (i + 2)) mod p -- a single word below R, and R 2^(32 (i + 2 - N)) = R2 * that word
+// from there on.  Every W_i is fully reduced; W_(N-2) == wm.
+template <class F>
+__device__ __forceinline__ void fe_tw_expand(const Fe<F>& wm, Fe<F> (&W)[F::N]) {
+  constexpr int N = F::N;
+  Fe<F> r2;
+#pragma unroll
+  for (int i = 0; i < N; i++) r2.v[i] = F::R2[i];
+#pragma unroll
+  for (int i = 0; i < N; i++) {
+    Fe<F> c = fe_zero<F>();
+    c.v[(i + 2) % N] = 1u;
+    if (i + 2 >= N) c = fe_mul<F>(r2, c);
+    W[i] = fe_mul<F>(wm, c);
+  }
+}
+
 // Largest K with K * p < R = 2^(32N) (a safe bound from the top word): a sum of K products,
 // each < p^2, stays below p R, so one Montgomery reduction of the sum lands in [0, 2p).
 template <class F>

@@ -35,11 +35,29 @@ struct NttPlan {
   // the flat table they were c * bitrev(t) apart, one cache line per lane); log_n > 12 only
   uint32_t *d_tw2 = nullptr;
   uint32_t *d_tw2_canon = nullptr;  // forward plans: canonical words
+  // Ft127, log_n > 12 (LCPC_NTT_TW4, ntt_v2.hpp): the word-expanded sub-FFT twiddles of the passes
+  // that multiply by them (field.hpp, fe_mul_tw), N elements per entry, entry e = W(w^(e << l2)),
+  // e < 2^(l1-1) (pass A's 2^l1-point DIF), then at ntt_tw4_b() entry e = W(w^(e << l1)),
+  // e < 2^(l2-1) (pass B's).  Only what a block stages in LDS is kept, so the table is 64
+  // (2^(l1-1) + 2^(l2-1)) bytes whatever the row length.  A pass longer than 2^NTT_TW4_MAX_L points
+  // keeps the one-element twiddles (its part is empty).  Inverse plans get the table too: they
+  // run the same kernels.
+  uint32_t *d_tw4 = nullptr;
   // which kernel encodes the PoS-dims rows (2^15-point Ft63, rate 1/2): LCPC_ROW_KERNEL_AUTO (the
   // measured choice: the one-pass kernel for file images, the four-step pair for element rows),
   // _FOURSTEP or _ONEPASS (lcpc_encoding_set_row_kernel)
   int row_kernel = 0;
 };
+// the longest sub-FFT whose block stages word-expanded twiddles: 2^(L-1) entries of 64 bytes beside
+// the tile (16 KiB at L = 9; at L = 12 the table alone would be 128 KiB of a CU's 160)
+constexpr int NTT_TW4_MAX_L = 9;
+inline size_t ntt_tw4_entries(int l) { return l <= NTT_TW4_MAX_L ? (size_t)1 << (l - 1) : 0; }
+inline const uint32_t *ntt_tw4_b(const NttPlan &p) {  // pass B's part of d_tw4 (Ft127: 16 words per entry)
+  return p.d_tw4 + ntt_tw4_entries(p.l1) * 16;
+}
+// out[e][i] = the word-expanded constant's element i of the Montgomery value tw[e * stride],
+// e < count (Ft127 only; hipErrorInvalidValue otherwise)
+hipError_t ntt_tw4_table(int fid, const uint32_t *tw, size_t stride, size_t count, uint32_t *out, hipStream_t s);
 // the [t][c] table above for a pass-A split l1 from a flat table tw (n = 2^log_n elements)
 hipError_t ntt_tw2_table(int fid, const uint32_t *tw, int log_n, int l1, uint32_t *out, hipStream_t s);
 // the longest row a plan can be made for is 2^ntt_max_log_n(fid); beyond it ntt_plan_init returns

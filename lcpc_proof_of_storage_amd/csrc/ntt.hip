@@ -14,6 +14,8 @@ DECL(ft191)
 DECL(ft255)
 DECL(ft253)
 #undef DECL
+hipError_t ntt_tw4_table_ft127(const uint32_t *, size_t, size_t, uint32_t *, hipStream_t);
+bool ntt_tw4_enabled();  // ntt_ft127.hip: the build's LCPC_NTT_TW4
 
 namespace {
 // out[(t << l2) + c] = tw[c * bitrev_l1(t)]: an element copy of `words` u32 words
@@ -33,6 +35,11 @@ hipError_t ntt_tw2_table(int fid, const uint32_t *tw, int log_n, int l1, uint32_
   hipLaunchKernelGGL(k_tw2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, tw, out, l1, log_n - l1,
                      field_words(fid));
   return hipGetLastError();
+}
+
+hipError_t ntt_tw4_table(int fid, const uint32_t *tw, size_t stride, size_t count, uint32_t *out, hipStream_t s) {
+  if (fid != 1) return hipErrorInvalidValue;
+  return count ? ntt_tw4_table_ft127(tw, stride, count, out, s) : hipSuccess;
 }
 
 int field_words(int fid) {
@@ -71,6 +78,16 @@ hipError_t ntt_plan_init(NttPlan &p, int fid, int log_n, bool inverse, hipStream
     if ((e = hipMalloc(&p.d_tw2, n * field_bytes(fid))) != hipSuccess) return e;
     if ((e = ntt_tw2_table(fid, p.d_tw, log_n, p.l1, p.d_tw2, s)) != hipSuccess) return e;
   }
+  if (fid == 1 && log_n > 12 && ntt_tw4_enabled()) {
+    // the word-expanded sub-FFT twiddles (kernels.hpp, NttPlan::d_tw4): pass A's block stages
+    // tw[e << l2], pass B's tw[e << l1]
+    const size_t na = ntt_tw4_entries(p.l1), nb = ntt_tw4_entries(p.l2);
+    if (na + nb) {
+      if ((e = hipMalloc(&p.d_tw4, (na + nb) * 4 * field_bytes(fid))) != hipSuccess) return e;
+      if ((e = ntt_tw4_table(fid, p.d_tw, (size_t)1 << p.l2, na, p.d_tw4, s)) != hipSuccess) return e;
+      if ((e = ntt_tw4_table(fid, p.d_tw, (size_t)1 << p.l1, nb, p.d_tw4 + na * 16, s)) != hipSuccess) return e;
+    }
+  }
   if (inverse) return hipSuccess;
   // canonical words of w^e = Montgomery words of w^e R^-1 (canon_out encodes)
   e = hipMalloc(&p.d_tw_canon, n * field_bytes(fid));
@@ -88,10 +105,12 @@ void ntt_plan_free(NttPlan &p) {
   if (p.d_tw_canon) (void)hipFree(p.d_tw_canon);
   if (p.d_tw2) (void)hipFree(p.d_tw2);
   if (p.d_tw2_canon) (void)hipFree(p.d_tw2_canon);
+  if (p.d_tw4) (void)hipFree(p.d_tw4);
   p.d_tw = nullptr;
   p.d_tw_canon = nullptr;
   p.d_tw2 = nullptr;
   p.d_tw2_canon = nullptr;
+  p.d_tw4 = nullptr;
 }
 
 hipError_t ntt_rows(const NttPlan &p, const uint32_t *src, size_t src_stride, size_t n_valid,

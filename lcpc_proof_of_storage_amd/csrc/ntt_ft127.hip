@@ -12,4 +12,10 @@ hipError_t ntt_tw_table_ft127(uint32_t *tw, int log_n, bool inverse, hipStream_t
                      s, tw, log_n, inverse ? 1 : 0);
   return hipGetLastError();
 }
+hipError_t ntt_tw4_table_ft127(const uint32_t *tw, size_t stride, size_t count, uint32_t *out, hipStream_t s) {
+  hipLaunchKernelGGL((ntt_detail::k_tw4_table<Ft127>), dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, tw,
+                     stride, count, out);
+  return hipGetLastError();
+}
+bool ntt_tw4_enabled() { return LCPC_NTT_TW4 != 0; }
 }  // namespace lcpc

@@ -27,6 +27,7 @@
 #include "prof.hpp"
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace lcpc {
 namespace ntt_detail {
@@ -43,6 +44,18 @@ __global__ void k_tw_table(uint32_t *__restrict__ tw, int log_n, int inverse) {
   for (int i = 0; i < F::N; i++) w.v[i] = inverse ? F::ROOT_INV[i] : F::ROOT[i];
   for (int i = 0; i < F::S - log_n; i++) w = fe_sqr<F>(w);
   fe_store<F>(tw, e, fe_pow<F>(w, e));
+}
+
+// out[e][i] = element i of the word-expanded constant of tw[e * stride] (field.hpp, fe_tw_expand)
+template <class F>
+__global__ __launch_bounds__(256) void k_tw4_table(const uint32_t *__restrict__ tw, size_t stride, size_t count,
+                                                   uint32_t *__restrict__ out) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= count) return;
+  Fe<F> W[F::N];
+  fe_tw_expand<F>(fe_load<F>(tw, e * stride), W);
+#pragma unroll
+  for (int i = 0; i < F::N; i++) fe_store<F>(out, e * F::N + i, W[i]);
 }
 
 __device__ __forceinline__ int bitrev(int x, int bits) {
@@ -171,16 +184,28 @@ hipError_t ntt_rows_t(const NttPlan &p, const uint32_t *src, size_t ss, size_t n
       return ntt_row1::launch<F>(p, src, ss, nv, dst, ds, n_rows, s, cp, cs, canon);
   }
   constexpr int HI = F::N >= 8 ? 11 : 12;  // LDS budget of 32-byte fields
+  // The sub-FFT twiddle product (ntt_v2.hpp): Ft127 passes of at most 2^NTT_TW4_MAX_L points
+  // multiply by the word-expanded twiddles of d_tw4, everything else by the flat table's elements.
+  if (LCPC_NTT_TW4 && F::ID == 1 && ntt_tw4_entries(p.l1) + ntt_tw4_entries(p.l2) && !p.d_tw4)
+    return hipErrorInvalidValue;
   auto pass_a = [&]<int L, int CW, int T = L + CW - R>() {
+    constexpr bool TW4 = LCPC_NTT_TW4 && LCPC_NTT_TW4_A && F::ID == 1 && L <= NTT_TW4_MAX_L;
+    using TW = std::conditional_t<TW4, ntt_v2::TwWords<F>, ntt_v2::TwLib<F>>;
+    const uint32_t *tw = TW4 ? p.d_tw4 : p.d_tw;
     // the inter-pass twiddles in [t][c] layout (canonical words for canon_out)
     const uint32_t *t2 = canon ? p.d_tw2_canon : p.d_tw2;
     if (halfz && canon)
-      return ntt_v2::launch_a<F, L, CW, T, true, true>(src, ss, nv, dst, ds, p.d_tw, p.log_n, n_rows, s, cp, cs, t2);
+      return ntt_v2::launch_a<F, L, CW, T, true, true, TW>(src, ss, nv, dst, ds, tw, p.log_n, n_rows, s, cp, cs, t2);
     if (halfz)
-      return ntt_v2::launch_a<F, L, CW, T, true>(src, ss, nv, dst, ds, p.d_tw, p.log_n, n_rows, s, cp, cs, t2);
+      return ntt_v2::launch_a<F, L, CW, T, true, false, TW>(src, ss, nv, dst, ds, tw, p.log_n, n_rows, s, cp, cs, t2);
     if (canon)
-      return ntt_v2::launch_a<F, L, CW, T, false, true>(src, ss, nv, dst, ds, p.d_tw, p.log_n, n_rows, s, cp, cs, t2);
-    return ntt_v2::launch_a<F, L, CW, T, false>(src, ss, nv, dst, ds, p.d_tw, p.log_n, n_rows, s, cp, cs, t2);
+      return ntt_v2::launch_a<F, L, CW, T, false, true, TW>(src, ss, nv, dst, ds, tw, p.log_n, n_rows, s, cp, cs, t2);
+    return ntt_v2::launch_a<F, L, CW, T, false, false, TW>(src, ss, nv, dst, ds, tw, p.log_n, n_rows, s, cp, cs, t2);
+  };
+  auto pass_b = [&]<int L, int CW, int T = L + CW - R>() {
+    constexpr bool TW4 = LCPC_NTT_TW4 && F::ID == 1 && L <= NTT_TW4_MAX_L;
+    using TW = std::conditional_t<TW4, ntt_v2::TwWords<F>, ntt_v2::TwLib<F>>;
+    return ntt_v2::launch_b<F, L, CW, T, TW>(dst, ds, TW4 ? ntt_tw4_b(p) : p.d_tw, p.log_n, n_rows, s);
   };
   hipError_t e;
   if constexpr (F::ID == 1) {
@@ -191,7 +216,7 @@ hipError_t ntt_rows_t(const NttPlan &p, const uint32_t *src, size_t ss, size_t n
     // (tools/microbench/nttbench.hip mode 2, profiles/r05_nttbench_cfg2.txt)
     if (p.log_n == 14 && p.l1 == 7) {
       if ((e = pass_a.template operator()<7, 5, 10>()) != hipSuccess) return e;
-      return ntt_v2::launch_b<F, 7, 5, 10>(dst, ds, p.d_tw, p.log_n, n_rows, s);
+      return pass_b.template operator()<7, 5, 10>();
     }
   }
   if constexpr (F::ID == 0) {
@@ -205,11 +230,7 @@ hipError_t ntt_rows_t(const NttPlan &p, const uint32_t *src, size_t ss, size_t n
     e = dispatch_logs<F, 6, HI>(p.l1, [&]<int L>() { return pass_a.template operator()<L, log_cw<L, E>()>(); });
   }
   if (e != hipSuccess) return e;
-  return dispatch_logs<F, 7, HI>(p.l2, [&]<int L>() {
-    constexpr int CW = log_cw<L, E>();
-    constexpr int T = L + CW - R;
-    return ntt_v2::launch_b<F, L, CW, T>(dst, ds, p.d_tw, p.log_n, n_rows, s);
-  });
+  return dispatch_logs<F, 7, HI>(p.l2, [&]<int L>() { return pass_b.template operator()<L, log_cw<L, E>()>(); });
 }
 
 }  // namespace ntt_detail

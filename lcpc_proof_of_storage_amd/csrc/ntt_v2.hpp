@@ -22,6 +22,24 @@
 #define LCPC_NTT_LAZY 1
 #endif
 
+// LCPC_NTT_TW4 (default 1; needs LCPC_NTT_LAZY): the Ft127 passes of at most 2^NTT_TW4_MAX_L points
+// multiply by word-expanded twiddles (field.hpp, fe_mul_tw: two Montgomery word-steps per product
+// instead of four) staged in LDS from NttPlan::d_tw4.  0: every field takes the library product
+// (tools/ab_lib.py runs one build against the other).
+#ifndef LCPC_NTT_TW4
+#define LCPC_NTT_TW4 1
+#endif
+#if !LCPC_NTT_LAZY
+#undef LCPC_NTT_TW4
+#define LCPC_NTT_TW4 0
+#endif
+// LCPC_NTT_TW4_A (default 1): 0 keeps pass A on the library product while pass B takes the
+// expanded twiddles (an A/B switch: pass A answers the shorter instruction stream far less than
+// pass B does).
+#ifndef LCPC_NTT_TW4_A
+#define LCPC_NTT_TW4_A 1
+#endif
+
 namespace lcpc {
 namespace ntt_v2 {
 
@@ -33,6 +51,41 @@ template <class F>
 __device__ __forceinline__ Fe<F> NTT_MUL(const Fe<F> &a, const Fe<F> &b) { return fe_mul<F>(a, b); }
 #endif
 
+// The twiddle product of the sub-FFT stages as a policy: what a block stages in LDS at `lds` for
+// the HALF = 2^(LOG_S-1) twiddles of its 2^LOG_S-point DIF, and the product by entry e.
+// TwLib: one Montgomery element per twiddle, from the flat table twn[e << shift]; the library product.
+template <class F>
+struct TwLib {
+  static constexpr int ELEMS = 1;  // LDS elements per twiddle
+  template <int HALF>
+  static __device__ __forceinline__ void stage(Fe<F> *lds, const uint32_t *__restrict__ twn, int shift, int tid,
+                                               int nt) {
+    for (int e = tid; e < HALF; e += nt) lds[e] = fe_load<F>(twn, (size_t)e << shift);
+  }
+  template <int HALF>
+  static __device__ __forceinline__ Fe<F> mul(const Fe<F> *lds, const Fe<F> &x, int e) {
+    return NTT_MUL<F>(x, lds[e]);
+  }
+};
+// TwWords: the word-expanded constant (N elements per twiddle) from the pass's compact table
+// twn[e][i], staged as N planes [i][e] so that each of a product's N reads has the lane pattern
+// of TwLib's one; fe_mul_tw.  The result is the class fe_mul_lazy returns, in [0, 2p).
+template <class F>
+struct TwWords {
+  static constexpr int ELEMS = F::N;
+  template <int HALF>
+  static __device__ __forceinline__ void stage(Fe<F> *lds, const uint32_t *__restrict__ twn, int, int tid, int nt) {
+    for (int k = tid; k < HALF * F::N; k += nt) lds[(k % F::N) * HALF + k / F::N] = fe_load<F>(twn, k);
+  }
+  template <int HALF>
+  static __device__ __forceinline__ Fe<F> mul(const Fe<F> *lds, const Fe<F> &x, int e) {
+    Fe<F> W[F::N];
+#pragma unroll
+    for (int i = 0; i < F::N; i++) W[i] = lds[i * HALF + e];
+    return fe_mul_tw<F>(x, W);
+  }
+};
+
 __device__ __forceinline__ int brev(int x, int bits) {
   return bits ? (int)(__builtin_bitreverse32((uint32_t)x) >> (32 - bits)) : 0;
 }
@@ -40,7 +93,7 @@ __device__ __forceinline__ int brev(int x, int bits) {
 // Stages S0 .. S0+RR-1 of the 2^LOG_S-point DIF on the K = 2^RR register elements
 // x[j] = v[b + j*GL] (GL = 2^(LOG_S-S0-RR), b = b_lo + multiple of GL*K, b_lo < GL).
 // HALFZ: x[j] == 0 for j >= K/2 on entry (only meaningful for S0 == 0).
-template <class F, int LOG_S, int S0, int RR, bool HALFZ>
+template <class F, int LOG_S, int S0, int RR, bool HALFZ, class TW>
 __device__ __forceinline__ void dif_regs(Fe<F> *x, int b_lo, const Fe<F> *tw) {
   constexpr int LOG_GL = LOG_S - S0 - RR;
   constexpr int GL = 1 << LOG_GL;
@@ -56,21 +109,17 @@ __device__ __forceinline__ void dif_regs(Fe<F> *x, int b_lo, const Fe<F> *tw) {
       const bool triv = (LOG_GL == 0 && jm == 0);
       if (HALFZ && qq == 0) {
         const Fe<F> a = x[j];
-#if LCPC_NTT_LAZY
-        x[j + h] = triv ? a : fe_mul_lazy<F>(a, tw[(b_lo + jm * GL) << s]);
-#else
-        x[j + h] = triv ? a : fe_mul<F>(a, tw[(b_lo + jm * GL) << s]);
-#endif
+        x[j + h] = triv ? a : TW::template mul<(1 << LOG_S) / 2>(tw, a, (b_lo + jm * GL) << s);
       } else {
         const Fe<F> a = x[j], c = x[j + h];
 #if LCPC_NTT_LAZY
         // residues in [0, 2p) throughout; the final store reduces (k_pass_b)
         x[j] = fe_add_2p<F>(a, c);
         const Fe<F> d = fe_sub_2p<F>(a, c);
-        x[j + h] = triv ? d : fe_mul_lazy<F>(d, tw[(b_lo + jm * GL) << s]);
+        x[j + h] = triv ? d : TW::template mul<(1 << LOG_S) / 2>(tw, d, (b_lo + jm * GL) << s);
 #else
         x[j] = fe_add<F>(a, c);
-        x[j + h] = triv ? fe_sub<F>(a, c) : fe_mul<F>(fe_sub_lazy<F>(a, c), tw[(b_lo + jm * GL) << s]);
+        x[j + h] = triv ? fe_sub<F>(a, c) : TW::template mul<(1 << LOG_S) / 2>(tw, fe_sub_lazy<F>(a, c), (b_lo + jm * GL) << s);
 #endif
       }
     }
@@ -84,7 +133,7 @@ constexpr int rr_of() {
 }
 
 // middle rounds: LDS -> registers -> LDS, lanes = adjacent vectors (v fastest)
-template <class F, int LOG_S, int LOG_CW, int LOG_T, int R, int S0, int LAST_S0>
+template <class F, int LOG_S, int LOG_CW, int LOG_T, int R, int S0, int LAST_S0, class TW>
 __device__ __forceinline__ void mid_rounds(Fe<F> *tile, const Fe<F> *tw, int tid) {
   if constexpr (S0 < LAST_S0) {
     constexpr int RR = rr_of<LOG_S, R, S0>();
@@ -99,12 +148,12 @@ __device__ __forceinline__ void mid_rounds(Fe<F> *tile, const Fe<F> *tw, int tid
       Fe<F> x[K];
 #pragma unroll
       for (int j = 0; j < K; j++) x[j] = tile[(b + j * GL) * LD + v];
-      dif_regs<F, LOG_S, S0, RR, false>(x, b_lo, tw);
+      dif_regs<F, LOG_S, S0, RR, false, TW>(x, b_lo, tw);
 #pragma unroll
       for (int j = 0; j < K; j++) tile[(b + j * GL) * LD + v] = x[j];
     }
     __syncthreads();
-    mid_rounds<F, LOG_S, LOG_CW, LOG_T, R, S0 + RR, LAST_S0>(tile, tw, tid);
+    mid_rounds<F, LOG_S, LOG_CW, LOG_T, R, S0 + RR, LAST_S0, TW>(tile, tw, tid);
   }
 }
 
@@ -119,8 +168,9 @@ constexpr int last_s0() {  // first stage of the last round
 // element including e = 0, so the whole transform comes out scaled by R^-1 -- i.e. in canonical
 // form (see ntt_rows' canon_out).  tw2: the inter-pass twiddles w^(c bitrev(t)) laid out [t][c]
 // (NttPlan::d_tw2 / d_tw2_canon), so the lanes of a store (adjacent columns c) load adjacent
-// twiddles.
-template <class F, int LOG_S, int LOG_CW, int LOG_T, bool HALFZ, bool CANON>
+// twiddles; it keeps the library product under either policy (1/8 of the products).
+// twn: what the policy TW stages (TwLib: the flat table; TwWords: pass A's part of d_tw4).
+template <class F, int LOG_S, int LOG_CW, int LOG_T, bool HALFZ, bool CANON, class TW>
 __global__ __launch_bounds__(1 << LOG_T) void k_pass_a(const uint32_t *__restrict__ src,
                                                        size_t src_stride, size_t n_valid,
                                                        uint32_t *__restrict__ dst,
@@ -134,15 +184,15 @@ __global__ __launch_bounds__(1 << LOG_T) void k_pass_a(const uint32_t *__restric
   static_assert(R >= 1 && R <= LOG_S, "tile / thread shape");
   constexpr int LS0 = last_s0<LOG_S, R>();
   constexpr bool ONE_ROUND = LS0 == 0;
-  __shared__ __align__(16) uint32_t smem[((ONE_ROUND ? 0 : S * LD) + S / 2) * F::N];
+  __shared__ __align__(16) uint32_t smem[((ONE_ROUND ? 0 : S * LD) + S / 2 * TW::ELEMS) * F::N];
   Fe<F> *tw = reinterpret_cast<Fe<F> *>(smem);
-  Fe<F> *tile = tw + S / 2;
+  Fe<F> *tile = tw + S / 2 * TW::ELEMS;
   const int tid = threadIdx.x;
   const int log_m = log_n - LOG_S;
   const int groups = 1 << (log_m - LOG_CW);
   const size_t row = blockIdx.x / groups;
   const size_t c0 = (size_t)(blockIdx.x % groups) << LOG_CW;
-  for (int e = tid; e < S / 2; e += T) tw[e] = fe_load<F>(twn, (size_t)e << log_m);
+  TW::template stage<S / 2>(tw, twn, log_m, tid, T);
 
   const uint32_t *in = src + row * src_stride * F::N;
   uint32_t *out = dst + row * dst_stride * F::N;
@@ -169,7 +219,7 @@ __global__ __launch_bounds__(1 << LOG_T) void k_pass_a(const uint32_t *__restric
       }
     }
     __syncthreads();  // twiddle table
-    dif_regs<F, LOG_S, 0, RR, HALFZ>(x, q, tw);
+    dif_regs<F, LOG_S, 0, RR, HALFZ, TW>(x, q, tw);
     if constexpr (ONE_ROUND) {
 #pragma unroll
       for (int j = 0; j < K; j++) {
@@ -187,7 +237,7 @@ __global__ __launch_bounds__(1 << LOG_T) void k_pass_a(const uint32_t *__restric
   }
   if constexpr (!ONE_ROUND) {
     __syncthreads();
-    mid_rounds<F, LOG_S, LOG_CW, LOG_T, R, rr_of<LOG_S, R, 0>(), LS0>(tile, tw, tid);
+    mid_rounds<F, LOG_S, LOG_CW, LOG_T, R, rr_of<LOG_S, R, 0>(), LS0, TW>(tile, tw, tid);
     // ---- last round: LDS -> registers -> twiddle -> HBM
     constexpr int RR = LOG_S - LS0;
     constexpr int K = 1 << RR;
@@ -198,7 +248,7 @@ __global__ __launch_bounds__(1 << LOG_T) void k_pass_a(const uint32_t *__restric
       Fe<F> x[K];
 #pragma unroll
       for (int j = 0; j < K; j++) x[j] = tile[(b + j) * LD + v];
-      dif_regs<F, LOG_S, LS0, RR, false>(x, 0, tw);
+      dif_regs<F, LOG_S, LS0, RR, false, TW>(x, 0, tw);
       const size_t c = c0 + v;
 #pragma unroll
       for (int j = 0; j < K; j++) {
@@ -212,22 +262,22 @@ __global__ __launch_bounds__(1 << LOG_T) void k_pass_a(const uint32_t *__restric
   }
 }
 
-template <class F, int LOG_S, int LOG_CW, int LOG_T>
+template <class F, int LOG_S, int LOG_CW, int LOG_T, class TW>
 __global__ __launch_bounds__(1 << LOG_T) void k_pass_b(uint32_t *__restrict__ data, size_t stride,
                                                        const uint32_t *__restrict__ twn,
                                                        int log_n) {
   constexpr int S = 1 << LOG_S, CW = 1 << LOG_CW, LD = CW > 1 ? CW + 1 : 1, T = 1 << LOG_T;
   constexpr int R = LOG_S + LOG_CW - LOG_T;
   static_assert(R >= 1 && R <= LOG_S, "tile / thread shape");
-  __shared__ __align__(16) uint32_t smem[(S * LD + S / 2) * F::N];
+  __shared__ __align__(16) uint32_t smem[(S * LD + S / 2 * TW::ELEMS) * F::N];
   Fe<F> *tw = reinterpret_cast<Fe<F> *>(smem);
-  Fe<F> *tile = tw + S / 2;
+  Fe<F> *tile = tw + S / 2 * TW::ELEMS;
   const int tid = threadIdx.x;
   const int log_blocks = log_n - LOG_S;
   const int groups = 1 << (log_blocks - LOG_CW);
   const size_t row = blockIdx.x / groups;
   const size_t b0 = (size_t)(blockIdx.x % groups) << LOG_CW;
-  for (int e = tid; e < S / 2; e += T) tw[e] = fe_load<F>(twn, (size_t)e << log_blocks);
+  TW::template stage<S / 2>(tw, twn, log_blocks, tid, T);
   uint32_t *io = data + (row * stride + b0 * S) * F::N;
   // ---- round 0 from HBM: lanes = adjacent positions of one block
   {
@@ -238,12 +288,12 @@ __global__ __launch_bounds__(1 << LOG_T) void k_pass_b(uint32_t *__restrict__ da
 #pragma unroll
     for (int j = 0; j < K; j++) x[j] = fe_load<F>(io, (size_t)v * S + q + j * GL);
     __syncthreads();
-    dif_regs<F, LOG_S, 0, RR, false>(x, q, tw);
+    dif_regs<F, LOG_S, 0, RR, false, TW>(x, q, tw);
 #pragma unroll
     for (int j = 0; j < K; j++) tile[(q + j * GL) * LD + v] = x[j];
   }
   __syncthreads();
-  mid_rounds<F, LOG_S, LOG_CW, LOG_T, R, rr_of<LOG_S, R, 0>(), LOG_S>(tile, tw, tid);
+  mid_rounds<F, LOG_S, LOG_CW, LOG_T, R, rr_of<LOG_S, R, 0>(), LOG_S, TW>(tile, tw, tid);
   for (int idx = tid; idx < S * CW; idx += T) {
     const int v = idx >> LOG_S, t = idx & (S - 1);
 #if LCPC_NTT_LAZY
@@ -254,23 +304,23 @@ __global__ __launch_bounds__(1 << LOG_T) void k_pass_b(uint32_t *__restrict__ da
   }
 }
 
-template <class F, int LOG_S, int LOG_CW, int LOG_T, bool HALFZ, bool CANON = false>
+template <class F, int LOG_S, int LOG_CW, int LOG_T, bool HALFZ, bool CANON, class TW>
 hipError_t launch_a(const uint32_t *src, size_t ss, size_t nv, uint32_t *dst, size_t ds,
                     const uint32_t *tw, int log_n, size_t n_rows, hipStream_t s, uint32_t *cp,
                     size_t cs, const uint32_t *tw2) {
   const size_t groups = (size_t)1 << (log_n - LOG_S - LOG_CW);
   prof::Scope ps("ntt_pass_a", s);
-  hipLaunchKernelGGL((k_pass_a<F, LOG_S, LOG_CW, LOG_T, HALFZ, CANON>), dim3((unsigned)(n_rows * groups)),
+  hipLaunchKernelGGL((k_pass_a<F, LOG_S, LOG_CW, LOG_T, HALFZ, CANON, TW>), dim3((unsigned)(n_rows * groups)),
                      dim3(1 << LOG_T), 0, s, src, ss, nv, dst, ds, tw, tw2, log_n, cp, cs);
   return hipGetLastError();
 }
 
-template <class F, int LOG_S, int LOG_CW, int LOG_T>
+template <class F, int LOG_S, int LOG_CW, int LOG_T, class TW>
 hipError_t launch_b(uint32_t *dst, size_t ds, const uint32_t *tw, int log_n, size_t n_rows,
                     hipStream_t s) {
   const size_t groups = (size_t)1 << (log_n - LOG_S - LOG_CW);
   prof::Scope ps("ntt_pass_b", s);
-  hipLaunchKernelGGL((k_pass_b<F, LOG_S, LOG_CW, LOG_T>), dim3((unsigned)(n_rows * groups)),
+  hipLaunchKernelGGL((k_pass_b<F, LOG_S, LOG_CW, LOG_T, TW>), dim3((unsigned)(n_rows * groups)),
                      dim3(1 << LOG_T), 0, s, dst, ds, tw, log_n);
   return hipGetLastError();
 }

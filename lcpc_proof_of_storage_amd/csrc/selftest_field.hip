@@ -21,7 +21,9 @@ int dot_kmax(int fid) {
 
 // elements of a / of b that one output reads
 int a_per_out(int op, int k) { return op == LCPC_SELFTEST_MUL_SUB_LAZY ? 2 : op == LCPC_SELFTEST_DOT ? k : 1; }
-int b_per_out(int op, int k) { return op == LCPC_SELFTEST_DOT ? k : 1; }
+int b_per_out(int fid, int op, int k) {
+  return op == LCPC_SELFTEST_DOT ? k : op == LCPC_SELFTEST_MUL_TW ? field_words(fid) : 1;
+}
 bool unary(int op) {
   switch (op) {
     case LCPC_SELFTEST_REDUCE_2P:
@@ -88,6 +90,13 @@ __global__ __launch_bounds__(256) void k_field_op(const uint32_t *__restrict__ a
   } else if constexpr (OP == LCPC_SELFTEST_POW) {
     const Fe<F> e = fe_load<F>(b, i);
     r = fe_pow<F>(fe_load<F>(a, i), (uint64_t)e.v[0] | ((uint64_t)e.v[1] << 32));
+  } else if constexpr (OP == LCPC_SELFTEST_MUL_TW) {
+    if constexpr (F::ID == 1) {
+      Fe<F> W[F::N];
+#pragma unroll
+      for (int q = 0; q < F::N; q++) W[q] = fe_load<F>(b, i * F::N + q);
+      r = fe_mul_tw<F>(fe_load<F>(a, i), W);
+    }
   } else if constexpr (OP == LCPC_SELFTEST_BALANCED_DIGITS) {
     if constexpr (F::N == 4) {
       const Fe<F> x = fe_load<F>(a, i);
@@ -155,6 +164,7 @@ extern "C" lcpc_status lcpc_selftest_field_op(lcpc_field f, int op, int k, const
   if (!valid_field(f)) return fail(LCPC_ERR_INVALID_ARG, "field");
   if (op < 0 || op >= LCPC_SELFTEST_N_OPS) return fail(LCPC_ERR_INVALID_ARG, "op");
   if (op == LCPC_SELFTEST_BALANCED_DIGITS && f != LCPC_FT127) return fail(LCPC_ERR_INVALID_ARG, "balanced_digits: Ft127");
+  if (op == LCPC_SELFTEST_MUL_TW && f != LCPC_FT127) return fail(LCPC_ERR_INVALID_ARG, "mul_tw: Ft127");
   if (k < 1 || k > dot_kmax(f)) return fail(LCPC_ERR_INVALID_ARG, "k outside [1, fe_dot_kmax]");
   if (!a || !out || (!b && !unary(op))) return fail(LCPC_ERR_INVALID_ARG, "null operand or output");
   lcpc_status st;
@@ -166,7 +176,7 @@ extern "C" lcpc_status lcpc_selftest_field_op(lcpc_field f, int op, int k, const
   const size_t wb = field_bytes(f);
   DBuf da, db, dout;
   if ((st = upload(dev, da, a, n * a_per_out(op, k) * wb))) return st;
-  if (!unary(op) && (st = upload(dev, db, b, n * b_per_out(op, k) * wb))) return st;
+  if (!unary(op) && (st = upload(dev, db, b, n * b_per_out(f, op, k) * wb))) return st;
   HIP_TRY(dout.alloc(dev, n * wb));
   HIP_TRY(dispatch_field(f, [&]<class F>() {
     return launch_op<F, 0>(op, k, da.as<uint32_t>(), db.as<uint32_t>(), dout.as<uint32_t>(), n, lease.s);
@@ -191,6 +201,25 @@ extern "C" lcpc_status lcpc_selftest_recombine(const int32_t *y, uint64_t *out, 
                      dout.as<uint32_t>(), n);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, dout.p, n * 16, hipMemcpyDeviceToHost, lease.s));
+  HIP_TRY(hipStreamSynchronize(lease.s));
+  return LCPC_OK;
+}
+
+extern "C" lcpc_status lcpc_selftest_twiddle_words(lcpc_field f, const uint64_t *tw, uint64_t *out, size_t n) {
+  if (f != LCPC_FT127) return fail(LCPC_ERR_INVALID_ARG, "twiddle_words: Ft127");
+  if (!tw || !out) return fail(LCPC_ERR_INVALID_ARG, "null twiddles or output");
+  lcpc_status st;
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  if (!n) return LCPC_OK;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  const size_t wb = field_bytes(f), nw = (size_t)field_words(f);
+  DBuf dtw, dout;
+  if ((st = upload(dev, dtw, tw, n * wb))) return st;
+  HIP_TRY(dout.alloc(dev, n * nw * wb));
+  HIP_TRY(lcpc::ntt_tw4_table(f, dtw.as<uint32_t>(), 1, n, dout.as<uint32_t>(), lease.s));
+  HIP_TRY(hipMemcpyAsync(out, dout.p, n * nw * wb, hipMemcpyDeviceToHost, lease.s));
   HIP_TRY(hipStreamSynchronize(lease.s));
   return LCPC_OK;
 }

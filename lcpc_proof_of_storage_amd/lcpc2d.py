@@ -156,7 +156,7 @@ def selftest_pool_ordering(rounds: int = 8, spin_us: int = 300) -> dict:
 SELFTEST_OPS = {name: i for i, name in enumerate([
     "add", "sub", "add_2p", "sub_2p", "reduce_2p", "sub_lazy", "mul_sub_lazy", "mul", "mul_cios", "sqr",
     "mul_lazy", "dot", "from_mont", "from_mont_generic", "to_mont", "repr_words", "canon_repr_words",
-    "is_canonical", "pow", "balanced_digits"])}
+    "is_canonical", "pow", "balanced_digits", "mul_tw"])}
 _SELFTEST_UNARY = {"reduce_2p", "sqr", "from_mont", "from_mont_generic", "to_mont", "repr_words",
                    "canon_repr_words", "is_canonical", "balanced_digits"}
 
@@ -169,8 +169,9 @@ def selftest_fe_dot_kmax(field: int) -> int:
 def selftest_field_op(field: int, op: str, a, b=None, k: int = 1) -> np.ndarray:
     """One field.hpp primitive per GPU thread on raw element words (lcpc_selftest_field_op): no
     range check, the caller owns the domain.  a and b are uint64 arrays of whole elements;
-    "mul_sub_lazy" reads two elements of a per output, "dot" k of a and of b; a unary op takes no
-    b.  Returns the (n, limbs) output words."""
+    "mul_sub_lazy" reads two elements of a per output, "dot" k of a and of b, "mul_tw" (Ft127) one
+    of a and the 2 limbs elements of a word-expanded constant of b (selftest_twiddle_words); a
+    unary op takes no b.  Returns the (n, limbs) output words."""
     nl = limbs(field)
     a = _elems(a, field)
     per = 2 if op == "mul_sub_lazy" else k if op == "dot" else 1
@@ -180,7 +181,7 @@ def selftest_field_op(field: int, op: str, a, b=None, k: int = 1) -> np.ndarray:
     pb = None
     if op not in _SELFTEST_UNARY:
         b = _elems(b, field)
-        if len(b) != n * (k if op == "dot" else 1):
+        if len(b) != n * (k if op == "dot" else 2 * nl if op == "mul_tw" else 1):
             raise ValueError("b does not match a")
         pb = _p64(b)
     out = np.zeros((n, nl), np.uint64)
@@ -194,6 +195,16 @@ def selftest_recombine(y) -> np.ndarray:
     y = np.ascontiguousarray(y, dtype=np.int32).reshape(-1, 16)
     out = np.zeros((len(y), 2), np.uint64)
     _raise(N.load().lcpc_selftest_recombine(y.ctypes.data_as(C.POINTER(C.c_int32)), _p64(out), len(y)))
+    return out
+
+
+def selftest_twiddle_words(field: int, tw) -> np.ndarray:
+    """The word-expanded table entries of the Montgomery values tw (lcpc_selftest_twiddle_words,
+    Ft127): for n values the (n, 2 limbs, limbs) words of w 2^(32 (j + 2)) mod p, j < 2 limbs."""
+    nl = limbs(field)
+    tw = _elems(tw, field)
+    out = np.zeros((len(tw), 2 * nl, nl), np.uint64)
+    _raise(N.load().lcpc_selftest_twiddle_words(field, _p64(tw), _p64(out), len(tw)))
     return out
 
 

@@ -1,5 +1,7 @@
 # A/B helper: run bench.py against another build of liblcpc_mi.so (argv[1]), e.g. one built from an
 # older commit in a git worktree; the remaining arguments are bench.py's.
+# The other build must export every symbol this tree's binding loads: for a switch such as
+# -DLCPC_NTT_TW4=0 build this tree twice; for an older commit run its own bench.py in its worktree.
 import os
 import runpy
 import sys

@@ -13,7 +13,11 @@ Inputs (all measured on MI355X, committed under profiles/):
 
 Model: time = (waves / 1024 SIMDs) x sum_class(static count x cost) x (dynamic / static VALU).
 
-    python tools/encode_cycle_model.py ISSUE_COST.json PMC_DIR TRACE_STATS.csv [OUT.txt [OUT.json]]
+    python tools/encode_cycle_model.py ISSUE_COST.json PMC_DIR TRACE_STATS.csv [OUT.txt [OUT.json [ATTRIBUTION.txt]]]
+
+ATTRIBUTION.txt: another instruction stream's counts (tools/isa_attribution.py's output), e.g.
+profiles/tw4_encode_isa_attribution.txt for the passes on word-expanded twiddles; the default is
+round 6's.  OUT.txt may be - for the terminal.
 
 OUT.json (profiles/issue_floor_encode.json) is what bench.py quotes in roofline_valu.issue_floor.
 """
@@ -88,10 +92,10 @@ def durations(stats_csv):
 
 def main():
     cost = issue_costs(sys.argv[1])
-    att = attribution()
+    att = attribution(sys.argv[6]) if len(sys.argv) > 6 else attribution()
     ctr = pmc(sys.argv[2])
     dur = durations(sys.argv[3])
-    out = open(sys.argv[4], "w") if len(sys.argv) > 4 else sys.stdout
+    out = open(sys.argv[4], "w") if len(sys.argv) > 4 and sys.argv[4] != "-" else sys.stdout
     print("# cfg3 encode (Ft127, 512 x 65536, 65536 waves per pass) against its VALU issue floor", file=out)
     print("# issue cost per wave-instruction per SIMD at 4 waves/SIMD (ns, wall time: tools/microbench/issue_cost.hip)",
           file=out)
@@ -122,7 +126,7 @@ def main():
     tot_meas = sum(dur.values())
     print(f"encode: model {tot_model:.3f} ms, measured {tot_meas:.3f} ms: the passes run at "
           f"{tot_model / tot_meas:.0%} of their VALU issue floor", file=out)
-    if len(sys.argv) > 5:
+    if len(sys.argv) > 5 and sys.argv[5] != "-":
         json.dump({"config_len": 1 << 24, "field": "Ft127", "code": "ligero",
                    "model_ms": {k: round(v, 4) for k, v in res.items()},
                    "measured_ms": {k: round(v, 4) for k, v in dur.items()},

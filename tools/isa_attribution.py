@@ -28,8 +28,11 @@ import isa_count as IC  # noqa: E402
 # butterflies per thread of the cfg3 shapes (ntt_v2.hpp; R = 3, 256 threads, 8 elements per
 # round): pass B <8,3,8> rounds of 3, 3, 2 stages -> 12 + 12 + 8; pass A <8,3,8,HALFZ> the same
 # minus stage 0's 4, which are (a, a w) with no add / sub.  Twiddle products per thread are
-# counted from the code itself: 28 v_mad_u64_u32 per Montgomery product (16 a_i b_j + 12 m_i p_j)
-SHAPES = {"k_pass_b": {"butterflies": 32}, "k_pass_a": {"butterflies": 28}}
+# counted from the code itself: 28 v_mad_u64_u32 per Montgomery product (16 a_i b_j + 12 m_i p_j),
+# 22 per word-expanded product (16 x_i W_i[k] + 6 m_r p_j; ntt_v2.hpp's TwWords policy, which leaves
+# pass A's inter-pass twiddle -- 4 products in the static stream -- on the library product)
+SHAPES = {"k_pass_b": {"butterflies": 32, "lib_products_tw4": 0},
+          "k_pass_a": {"butterflies": 28, "lib_products_tw4": 4}}
 
 
 def compile_s(src, out):
@@ -65,7 +68,7 @@ def main():
                 prims[cur].append(t.split()[0])
         print("# Ft127 field primitives, gfx950 VALU instructions (stand-alone kernels; the load /", file=out)
         print("# store address setup, 1 instruction, is included)", file=out)
-        for k in ("k_mul_lazy", "k_add2p", "k_sub2p", "k_bfly"):
+        for k in ("k_mul_lazy", "k_mul_tw", "k_add2p", "k_sub2p", "k_bfly", "k_bfly_tw"):
             c = valu_classes(prims[k])
             print(f"{k:12s} VALU {sum(c.values()):4d}  " + ", ".join(f"{n} {v}" for n, v in
                                                                       sorted(c.items(), key=lambda kv: -kv[1])),
@@ -73,16 +76,23 @@ def main():
         ks = IC.kernels(ns)
         dem = dict(zip(ks, IC.demangle(list(ks))))
         print("\n# cfg3 passes, static VALU instructions per thread (one tile item per thread)", file=out)
-        for want, key in (("k_pass_a<lcpc::Ft127, 8, 3, 8, true, true>", "k_pass_a"),
-                          ("k_pass_b<lcpc::Ft127, 8, 3, 8>", "k_pass_b")):
+        for want, key in (("k_pass_a<lcpc::Ft127, 8, 3, 8, true, true", "k_pass_a"),
+                          ("k_pass_b<lcpc::Ft127, 8, 3, 8", "k_pass_b")):
             mk = next(k for k in ks if want in dem[k])
             c = valu_classes(ks[mk])
             tot = sum(c.values())
             sh = dict(SHAPES[key])
             mads = c.get("mad_u64_u32", 0)
-            sh["products"] = mads // 28
-            print(f"{want}: VALU {tot}, s_nop {IC.classify(ks[mk]).get('s_nop', 0)}", file=out)
-            print(f"   {sh['products']} twiddle products, {sh['butterflies']} butterflies per thread: "
+            if "TwWords" in dem[mk]:
+                lib = sh["lib_products_tw4"]
+                sh["products"] = lib + (mads - 28 * lib) // 22
+                what = f"twiddle products ({lib} library, {sh['products'] - lib} word-expanded)"
+            else:
+                sh["products"] = mads // 28
+                what = "twiddle products"
+            name = dem[mk].split('(')[0]
+            print(f"{name[name.find('k_pass'):]}: VALU {tot}, s_nop {IC.classify(ks[mk]).get('s_nop', 0)}", file=out)
+            print(f"   {sh['products']} {what}, {sh['butterflies']} butterflies per thread: "
                   f"{tot / sh['products']:.1f} VALU per product, {tot / sh['butterflies']:.1f} per butterfly, "
                   f"{mads / sh['products']:.1f} mads per product", file=out)
             for n, v in sorted(c.items(), key=lambda kv: -kv[1]):

@@ -74,9 +74,30 @@ void bench(const char *fname, int log_n, size_t rows, bool with_copy = false) {
     }
     return t2;
   };
+  // Ft127: the word-expanded sub-FFT twiddles of a 2^l-point pass (NttPlan::d_tw4's two parts)
+  std::map<int, uint32_t *> tw4s;
+  auto tw4_for = [&](int l) -> uint32_t * {
+    uint32_t *&t4 = tw4s[l];
+    if constexpr (F::ID == 1) {
+      if (!t4) {
+        const size_t cnt = (size_t)1 << (l - 1);
+        CK(hipMalloc(&t4, cnt * W * W * 4));
+        hipLaunchKernelGGL((ntt_detail::k_tw4_table<F>), dim3((cnt + 255) / 256), dim3(256), 0, 0, tw,
+                           (size_t)1 << (log_n - l), cnt, t4);
+        CK(hipDeviceSynchronize());
+      }
+    }
+    return t4;
+  };
   NttPlan plan;
   plan.fid = F::ID; plan.log_n = log_n; plan.l1 = log_n / 2; plan.l2 = log_n - plan.l1; plan.d_tw = tw;
   plan.d_tw2 = tw2_for(plan.l1);
+  if constexpr (F::ID == 1 && LCPC_NTT_TW4) {  // the plan's layout: pass A's part, then pass B's
+    const size_t na = ntt_tw4_entries(plan.l1), nb = ntt_tw4_entries(plan.l2);
+    CK(hipMalloc(&plan.d_tw4, (na + nb) * W * W * 4));
+    CK(hipMemcpy(plan.d_tw4, tw4_for(plan.l1), na * W * W * 4, hipMemcpyDeviceToDevice));
+    CK(hipMemcpy(plan.d_tw4 + na * W * W, tw4_for(plan.l2), nb * W * W * 4, hipMemcpyDeviceToDevice));
+  }
   CK(ntt_detail::ntt_rows_t<F>(plan, coeffs, np, np, ref, n, rows, s, nullptr, 0, false));
   CK(hipStreamSynchronize(s));
 
@@ -84,13 +105,23 @@ void bench(const char *fname, int log_n, size_t rows, bool with_copy = false) {
   vs.push_back({"product (ntt_rows_t)", [&](const uint32_t *c, uint32_t *o, hipStream_t st) {
                   CK(ntt_detail::ntt_rows_t<F>(plan, c, np, np, o, n, rows, st, nullptr, 0, false));
                 }});
+  // every shape with the library product; Ft127 also with the word-expanded twiddles ("tw4")
 #define V2(LA, CWA, TA, LB, CWB, TB)                                                           \
   vs.push_back({"v2 A(S=2^" #LA ",CW=2^" #CWA ",T=2^" #TA ") B(S=2^" #LB ",CW=2^" #CWB ",T=2^" #TB ")", \
                 [&](const uint32_t *c, uint32_t *o, hipStream_t st) {                          \
-                  CK((ntt_v2::launch_a<F, LA, CWA, TA, true>(c, np, np, o, n, tw, log_n, rows, st, cpy, np,  \
-                                                             tw2_for(LA))));                    \
-                  CK((ntt_v2::launch_b<F, LB, CWB, TB>(o, n, tw, log_n, rows, st)));           \
-                }});
+                  CK((ntt_v2::launch_a<F, LA, CWA, TA, true, false, ntt_v2::TwLib<F>>(                \
+                      c, np, np, o, n, tw, log_n, rows, st, cpy, np, tw2_for(LA))));            \
+                  CK((ntt_v2::launch_b<F, LB, CWB, TB, ntt_v2::TwLib<F>>(o, n, tw, log_n, rows, st))); \
+                }});                                                                           \
+  if constexpr (F::ID == 1) {                                                                  \
+    if (LA <= NTT_TW4_MAX_L && LB <= NTT_TW4_MAX_L)                                            \
+      vs.push_back({"tw4 A(S=2^" #LA ",CW=2^" #CWA ",T=2^" #TA ") B(S=2^" #LB ",CW=2^" #CWB ",T=2^" #TB ")", \
+                    [&](const uint32_t *c, uint32_t *o, hipStream_t st) {                      \
+                      CK((ntt_v2::launch_a<F, LA, CWA, TA, true, false, ntt_v2::TwWords<F>>(          \
+                          c, np, np, o, n, tw4_for(LA), log_n, rows, st, cpy, np, tw2_for(LA)))); \
+                      CK((ntt_v2::launch_b<F, LB, CWB, TB, ntt_v2::TwWords<F>>(o, n, tw4_for(LB), log_n, rows, st))); \
+                    }});                                                                       \
+  }
   if constexpr (F::ID == 1) {
     if (log_n == 16) {
       V2(8, 3, 8, 8, 3, 8)
@@ -103,6 +134,7 @@ void bench(const char *fname, int log_n, size_t rows, bool with_copy = false) {
       V2(7, 3, 7, 9, 2, 8)
       V2(7, 4, 8, 9, 2, 8)
       V2(6, 4, 7, 10, 1, 8)
+      V2(8, 3, 7, 8, 3, 7)  // radix-2^4 rounds: half the threads per tile
     } else if (log_n == 14) {  // cfg2 (128 rows): the product shape first, then occupancy / tile sweeps
       V2(7, 4, 8, 7, 4, 8)
       V2(7, 3, 7, 7, 3, 7)
