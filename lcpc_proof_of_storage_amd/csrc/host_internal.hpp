@@ -1,6 +1,8 @@
 // host_internal.hpp -- shared host-side machinery of liblcpc_mi.so (per-device stream pools and
 // caching allocator, pinned staging, handle layouts, Fiat-Shamir helpers).  Internal: included by
-// lcpc_host.cpp and shard_native.cpp; one definition of every pool / thread-local across them.
+// every host unit (lcpc_host.cpp, shard_host.cpp, shard_native.cpp, batch_host.cpp and, through
+// pos_internal.hpp, pos_files_host.cpp and pos_repair_host.cpp); one definition of every pool /
+// thread-local across them.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -6,19 +6,14 @@
 // across PCIe, and runs the inherently serial Fiat-Shamir steps (transcript.cpp).
 // There is no CPU fallback: with no usable HIP device every compute entry point fails with
 // LCPC_ERR_NO_DEVICE.
-#include "host_internal.hpp"
-
-#include <unistd.h>
-
-#include <cerrno>
+#include "pos_internal.hpp"
 
 using namespace lcpc;
 using namespace lcpc_host;
 
 // ---------------------------------------------------------------- internal helpers
-namespace {
-lcpc_status make_rs_encoding(int fid, size_t n_per_row, size_t n_cols, size_t nco, size_t ndt,
-                             lcpc_encoding **out) {
+lcpc_status lcpc_host::make_rs_encoding(int fid, size_t n_per_row, size_t n_cols, size_t nco, size_t ndt,
+                                        lcpc_encoding **out) {
   if (!out) return fail(LCPC_ERR_INVALID_ARG, "null out");
   if (!valid_field(fid)) return fail(LCPC_ERR_INVALID_ARG, "unknown field");
   if (!field_gpu_supported(fid)) return fail(LCPC_ERR_UNSUPPORTED, "field has no gfx950 kernels");
@@ -48,6 +43,7 @@ lcpc_status make_rs_encoding(int fid, size_t n_per_row, size_t n_cols, size_t nc
   return LCPC_OK;
 }
 
+namespace {
 // SdigEncodingS::_new_from_np1 / new_from_dims (lcpc-brakedown-pc/src/lib.rs:69-137) with the
 // n_per_row already chosen; want_cols = 0 accepts the generated codeword length.
 lcpc_status make_sdig_encoding(int fid, int code, size_t n_per_row, size_t want_cols, uint64_t seed,
@@ -1444,37 +1440,6 @@ int lcpc_verify_column_value(lcpc_field f, const uint64_t *col, const uint64_t *
 // ================================================================= proof-of-storage producers
 namespace {
 
-// n^-1 mod p for n = 2^log_n | p - 1, canonical: p - (p - 1) / n
-void inv_pow2_canon(int fid, int log_n, uint32_t *words) {
-  const FieldInfo fi = field_info(fid);
-  uint64_t q[4] = {0, 0, 0, 0}, r[4] = {0, 0, 0, 0};
-  for (int i = 0; i < fi.limbs; i++) q[i] = fi.p[i];
-  q[0] -= 1;  // p odd: no borrow
-  for (int k = 0; k < log_n; k++) {  // q >>= 1 (multi-limb)
-    for (int i = 0; i < fi.limbs; i++) {
-      q[i] >>= 1;
-      if (i + 1 < fi.limbs) q[i] |= q[i + 1] << 63;
-    }
-  }
-  uint64_t br = 0;
-  for (int i = 0; i < fi.limbs; i++) {
-    const uint64_t a = fi.p[i], b = q[i];
-    const uint64_t d = a - b - br;
-    br = (a < b) || (a - b < br);
-    r[i] = d;
-  }
-  for (int i = 0; i < fi.limbs; i++) {
-    words[2 * i] = (uint32_t)r[i];
-    words[2 * i + 1] = (uint32_t)(r[i] >> 32);
-  }
-}
-
-lcpc_status check_fft_len(int fid, size_t len) {
-  if (len == 0 || (len & (len - 1))) return fail(LCPC_FFT_NOT_POWER_OF_TWO, "FFTError::NotPowerOfTwo");
-  if ((int)log2_np2(len) > field_info(fid).s) return fail(LCPC_FFT_TOO_BIG, "FFTError::TooBig");
-  return LCPC_OK;
-}
-
 // Encode `len` host elements with e into a temporary row-major codeword (Leaves /
 // ColumnsWithoutPath requests, lcpc_online.rs:144-224): no commitment, no Merkle tree.
 lcpc_status encode_matrix(const lcpc_encoding *e, const uint64_t *elems, size_t len, DBuf &comm,
@@ -1667,35 +1632,13 @@ lcpc_status lcpc_ifft_oi_rows(lcpc_field f, uint64_t *rows, size_t n_rows, size_
   HIP_TRY(hipSetDevice(dev->id));
   const int log_n = (int)log2_np2(len);
   const int wb = field_bytes(f);
-  NttPlan plan;
-  hipError_t he = ntt_plan_init(plan, f, log_n, true, lease.s);
-  if (he != hipSuccess) {
-    ntt_plan_free(plan);
-    if (he == hipErrorInvalidValue) return fail(LCPC_ERR_UNSUPPORTED, "length beyond the NTT range");
-    HIP_TRY(he);
-  }
-  struct PlanGuard {
-    NttPlan &p;
-    hipStream_t s;
-    ~PlanGuard() {
-      (void)hipStreamSynchronize(s);
-      ntt_plan_free(p);
-    }
-  } guard{plan, lease.s};
+  InversePlan inverse;
+  if ((st = inverse.init(f, log_n, lease.s))) return st;
   DBuf a, b;
   if ((st = upload(dev, a, rows, n_rows * len * wb))) return st;
   HIP_TRY(b.alloc(dev, n_rows * len * wb));
-  uint32_t inv[8] = {0};
-  inv_pow2_canon(f, log_n, inv);
-  // ifft_oi = reorder the evaluations to natural order (bit-reversed ones: include/
-  // lcpc_fft_convention.h), DIF with the inverse root, bit-reverse back and scale by len^-1
-  uint32_t *x = a.as<uint32_t>(), *y = b.as<uint32_t>();
-  if (LCPC_FFT_OUTPUT_BITREV) {
-    HIP_TRY(bitrev_scale(f, x, y, log_n, n_rows, nullptr, lease.s));
-    std::swap(x, y);
-  }
-  HIP_TRY(ntt_rows(plan, x, len, len, y, len, n_rows, lease.s));
-  HIP_TRY(bitrev_scale(f, y, x, log_n, n_rows, inv, lease.s));
+  uint32_t *x = nullptr, *y = nullptr;
+  if ((st = ifft_oi_device(inverse.plan, f, log_n, a.as<uint32_t>(), b.as<uint32_t>(), n_rows, lease.s, &x, &y))) return st;
   HIP_TRY(hipMemcpyAsync(rows, x, n_rows * len * wb, hipMemcpyDeviceToHost, lease.s));
   HIP_TRY(hipStreamSynchronize(lease.s));
   return LCPC_OK;
@@ -1986,2135 +1929,3 @@ lcpc_status lcpc_pos_update_evaluation(const lcpc_encoding *e_old, const void *d
 
 }  // extern "C"
 
-// ================================================================= row shards (multi-GPU commit)
-// One GPU's share of a Ligero commitment whose rows are split across processes:
-// the shard encodes its rows, computes the BLAKE3 chunk chaining values of the leaf-message
-// chunks its rows cover, its partial row combinations and its rows of opened columns.  The
-// exchanges between shards (chaining values by column block, subtree roots, partial sums,
-// challenge broadcasts) are the caller's (lcpc_proof_of_storage_amd/shard.py, RCCL through
-// torch.distributed); together they reproduce commit / prove bit for bit.
-struct lcpc_shard {
-  const lcpc_encoding *e = nullptr;
-  size_t row0 = 0, n_rows = 0, n_rows_total = 0;
-  DBuf coeffs, comm;
-};
-
-extern "C" {
-
-size_t lcpc_leaf_n_chunks(lcpc_field f, size_t n_rows) {
-  return valid_field(f) ? leaf_n_chunks(f, n_rows) : 0;
-}
-
-size_t lcpc_leaf_chunk_first_row(lcpc_field f, size_t chunk) {
-  // first row of the leaf message at or after byte 1024 * chunk (32-byte zero prefix)
-  if (!valid_field(f) || chunk == 0) return 0;
-  const size_t wb = (size_t)field_bytes(f);
-  return (1024 * chunk - 32 + wb - 1) / wb;
-}
-
-static lcpc_status shard_new_impl(const lcpc_encoding *e, const void *coeffs, bool on_device, size_t row0,
-                                  size_t n_shard_rows, size_t n_rows_total, lcpc_shard **out);
-
-lcpc_status lcpc_shard_new(const lcpc_encoding *e, const uint64_t *coeffs, size_t row0,
-                           size_t n_shard_rows, size_t n_rows_total, lcpc_shard **out) {
-  return shard_new_impl(e, coeffs, false, row0, n_shard_rows, n_rows_total, out);
-}
-
-lcpc_status lcpc_shard_new_device(const lcpc_encoding *e, const void *d_coeffs, size_t row0,
-                                  size_t n_shard_rows, size_t n_rows_total, lcpc_shard **out) {
-  return shard_new_impl(e, d_coeffs, true, row0, n_shard_rows, n_rows_total, out);
-}
-
-static lcpc_status shard_new_impl(const lcpc_encoding *e, const void *coeffs, bool on_device, size_t row0,
-                                  size_t n_shard_rows, size_t n_rows_total, lcpc_shard **out) {
-  if (!e || !out || (!coeffs && n_shard_rows)) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  if (lcpc_status bst = require_blake3(e, "a row shard (its exchange is BLAKE3 chunk chaining values)")) return bst;
-  if (e->kind != KIND_RS) return fail(LCPC_ERR_UNSUPPORTED, "row shards: Ligero / R-S encodings only");
-  if (row0 + n_shard_rows > n_rows_total) return fail(LCPC_ERR_INVALID_ARG, "shard rows out of range");
-  Device *dev = e->dev;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  auto sh = std::make_unique<lcpc_shard>();
-  sh->e = e;
-  sh->row0 = row0;
-  sh->n_rows = n_shard_rows;
-  sh->n_rows_total = n_rows_total;
-  const size_t np = e->n_per_row, nc = e->n_cols;
-  const int wb = field_bytes(e->fid);
-  HIP_TRY(sh->coeffs.alloc(dev, n_shard_rows * np * wb + 16));
-  HIP_TRY(sh->comm.alloc(dev, n_shard_rows * nc * wb + 16));
-  if (n_shard_rows && on_device) {  // encode straight from the caller's rows; pass A copies them
-    HIP_TRY(ntt_rows(e->plan, (const uint32_t *)coeffs, np, np, sh->comm.as<uint32_t>(), nc, n_shard_rows,
-                     lease.s, sh->coeffs.as<uint32_t>(), np, true));
-  } else if (n_shard_rows) {
-    HIP_TRY(hipMemcpyAsync(sh->coeffs.p, coeffs, n_shard_rows * np * wb, hipMemcpyHostToDevice, lease.s));
-    HIP_TRY(ntt_rows(e->plan, sh->coeffs.as<uint32_t>(), np, np, sh->comm.as<uint32_t>(), nc, n_shard_rows,
-                     lease.s, nullptr, 0, true));
-  }
-  HIP_TRY(hipStreamSynchronize(lease.s));
-  sh->coeffs.settle();
-  sh->comm.settle();
-  *out = sh.release();
-  return LCPC_OK;
-}
-
-void lcpc_shard_free(lcpc_shard *s) {
-  if (!s) return;
-  Lease lease(s->e->dev);
-  (void)hipStreamSynchronize(lease.s);
-  delete s;
-}
-
-lcpc_status lcpc_shard_chunk_cvs(const lcpc_shard *s, size_t chunk_lo, size_t chunk_hi,
-                                 uint8_t *out) {
-  if (!s || (!out && chunk_hi > chunk_lo)) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  const int fid = s->e->fid;
-  const size_t nc = s->e->n_cols;
-  if (chunk_hi > leaf_n_chunks(fid, s->n_rows_total) || chunk_lo > chunk_hi)
-    return fail(LCPC_ERR_INVALID_ARG, "chunk range");
-  // every row the chunks read must be in the shard
-  const size_t need_lo = lcpc_leaf_chunk_first_row((lcpc_field)fid, chunk_lo);
-  const size_t need_hi = chunk_hi >= leaf_n_chunks(fid, s->n_rows_total)
-                             ? s->n_rows_total
-                             : lcpc_leaf_chunk_first_row((lcpc_field)fid, chunk_hi);
-  if (chunk_hi > chunk_lo && (need_lo < s->row0 || need_hi > s->row0 + s->n_rows))
-    return fail(LCPC_ERR_INVALID_ARG, "the shard does not hold every row of those chunks");
-  if (chunk_hi == chunk_lo) return LCPC_OK;
-  Device *dev = s->e->dev;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  DBuf cvs;
-  HIP_TRY(cvs.alloc(dev, (chunk_hi - chunk_lo) * nc * 32));
-  HIP_TRY(leaf_chunk_cvs(fid, s->comm.as<uint32_t>(), s->row0, s->n_rows_total, nc, nc, chunk_lo, chunk_hi,
-                         cvs.as<uint32_t>(), lease.s, true));
-  HIP_TRY(hipMemcpyAsync(out, cvs.p, (chunk_hi - chunk_lo) * nc * 32, hipMemcpyDeviceToHost, lease.s));
-  HIP_TRY(hipStreamSynchronize(lease.s));
-  return LCPC_OK;
-}
-
-lcpc_status lcpc_leaves_from_cvs(const uint8_t *cvs, size_t n_chunks, size_t n_cols, uint8_t *leaves) {
-  if ((!cvs || !leaves) && n_cols) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  if (n_chunks == 0) return fail(LCPC_ERR_INVALID_ARG, "n_chunks");
-  if (!n_cols) return LCPC_OK;
-  lcpc_status st;
-  Device *dev = current_device(&st);
-  if (!dev) return st;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  DBuf dc, dl;
-  if ((st = upload(dev, dc, cvs, n_chunks * n_cols * 32))) return st;
-  HIP_TRY(dl.alloc(dev, n_cols * 32));
-  HIP_TRY(leaves_from_cvs(dc.as<uint32_t>(), n_cols, (int)n_chunks, dl.as<uint8_t>(), lease.s));
-  HIP_TRY(hipMemcpyAsync(leaves, dl.p, n_cols * 32, hipMemcpyDeviceToHost, lease.s));
-  HIP_TRY(hipStreamSynchronize(lease.s));
-  return LCPC_OK;
-}
-
-lcpc_status lcpc_shard_collapse(const lcpc_shard *s, const uint64_t *tensors, size_t n_tensors,
-                                uint64_t *out) {
-  // partial collapse_columns over the shard's rows: out[t][c] = sum_{r in shard} t[r] coeffs[r][c]
-  if (!s || !out || (!tensors && s->n_rows)) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  if (n_tensors < 1 || n_tensors > 4) return fail(LCPC_ERR_INVALID_ARG, "1..4 tensors");
-  const int fid = s->e->fid, wb = field_bytes(fid);
-  const size_t np = s->e->n_per_row;
-  Device *dev = s->e->dev;
-  Lease lease(dev, POOL_HIGH);
-  HIP_TRY(hipSetDevice(dev->id));
-  DBuf dt, dout, scratch;
-  lcpc_status st;
-  HIP_TRY(dout.alloc(dev, n_tensors * np * wb));
-  if (s->n_rows == 0) {
-    HIP_TRY(hipMemsetAsync(dout.p, 0, n_tensors * np * wb, lease.s));
-  } else {
-    if ((st = upload(dev, dt, tensors, n_tensors * s->n_rows * wb))) return st;
-    HIP_TRY(scratch.alloc(dev, collapse_scratch_bytes(fid, s->n_rows, np, (int)n_tensors)));
-    HIP_TRY(collapse_rows(fid, s->coeffs.as<uint32_t>(), s->n_rows, np, dt.as<uint32_t>(), (int)n_tensors,
-                          dout.as<uint32_t>(), scratch.p, lease.s));
-  }
-  HIP_TRY(hipMemcpyAsync(out, dout.p, n_tensors * np * wb, hipMemcpyDeviceToHost, lease.s));
-  HIP_TRY(hipStreamSynchronize(lease.s));
-  return LCPC_OK;
-}
-
-lcpc_status lcpc_shard_gather_columns(const lcpc_shard *s, const uint64_t *idx, size_t n, uint64_t *out) {
-  if (!s || (!idx && n) || (!out && n)) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  const size_t nc = s->e->n_cols;
-  for (size_t k = 0; k < n; k++)
-    if (idx[k] >= nc) return fail(LCPC_PROVER_COLUMN_NUMBER, "ProverError::ColumnNumber");
-  if (!n || !s->n_rows) return LCPC_OK;
-  const int fid = s->e->fid, wb = field_bytes(fid);
-  Device *dev = s->e->dev;
-  Lease lease(dev, POOL_HIGH);
-  HIP_TRY(hipSetDevice(dev->id));
-  DBuf didx, dcol;
-  lcpc_status st;
-  if ((st = upload(dev, didx, idx, n * 8))) return st;
-  HIP_TRY(dcol.alloc(dev, n * s->n_rows * wb));
-  HIP_TRY(gather_columns(fid, s->comm.as<uint32_t>(), s->n_rows, nc, didx.as<uint64_t>(), n,
-                         dcol.as<uint32_t>(), lease.s, false, true));
-  HIP_TRY(hipMemcpyAsync(out, dcol.p, n * s->n_rows * wb, hipMemcpyDeviceToHost, lease.s));
-  HIP_TRY(hipStreamSynchronize(lease.s));
-  return LCPC_OK;
-}
-
-lcpc_status lcpc_field_sum(lcpc_field f, const uint64_t *vecs, size_t n_vecs, size_t len, uint64_t *out) {
-  // out[i] = sum_k vecs[k][i] mod p (folds the shards' partial row combinations)
-  if (!valid_field(f) || (!vecs && n_vecs * len) || (!out && len)) return fail(LCPC_ERR_INVALID_ARG, "arguments");
-  if (!len) return LCPC_OK;
-  lcpc_status st;
-  Device *dev = current_device(&st);
-  if (!dev) return st;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  const int wb = field_bytes(f);
-  DBuf dv, dout;
-  if (n_vecs == 0) {
-    std::memset(out, 0, len * wb);
-    return LCPC_OK;
-  }
-  if ((st = upload(dev, dv, vecs, n_vecs * len * wb))) return st;
-  HIP_TRY(dout.alloc(dev, len * wb));
-  // the fold kernel of collapse: partial[split][t][c] with T = 1
-  HIP_TRY(collapse_fold_rows(f, dv.as<uint32_t>(), n_vecs, len, dout.as<uint32_t>(), lease.s));
-  HIP_TRY(hipMemcpyAsync(out, dout.p, len * wb, hipMemcpyDeviceToHost, lease.s));
-  HIP_TRY(hipStreamSynchronize(lease.s));
-  return LCPC_OK;
-}
-
-// ---- device-resident exchanges: the same steps with the exchanged buffers in device memory
-// (torch tensors that RCCL moves over xGMI), so nothing crosses PCIe but the transcript inputs.
-// Each call runs on a leased library stream and returns once its results are in memory.
-lcpc_status lcpc_shard_chunk_cvs_device(const lcpc_shard *s, size_t chunk_lo, size_t chunk_hi, void *d_out) {
-  if (!s || (!d_out && chunk_hi > chunk_lo)) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  const int fid = s->e->fid;
-  const size_t nc = s->e->n_cols;
-  if (chunk_hi > leaf_n_chunks(fid, s->n_rows_total) || chunk_lo > chunk_hi)
-    return fail(LCPC_ERR_INVALID_ARG, "chunk range");
-  const size_t need_lo = lcpc_leaf_chunk_first_row((lcpc_field)fid, chunk_lo);
-  const size_t need_hi = chunk_hi >= leaf_n_chunks(fid, s->n_rows_total)
-                             ? s->n_rows_total
-                             : lcpc_leaf_chunk_first_row((lcpc_field)fid, chunk_hi);
-  if (chunk_hi > chunk_lo && (need_lo < s->row0 || need_hi > s->row0 + s->n_rows))
-    return fail(LCPC_ERR_INVALID_ARG, "the shard does not hold every row of those chunks");
-  if (chunk_hi == chunk_lo) return LCPC_OK;
-  Device *dev = s->e->dev;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  HIP_TRY(leaf_chunk_cvs(fid, s->comm.as<uint32_t>(), s->row0, s->n_rows_total, nc, nc, chunk_lo, chunk_hi,
-                         (uint32_t *)d_out, lease.s, true));
-  HIP_TRY(hipStreamSynchronize(lease.s));
-  return LCPC_OK;
-}
-
-lcpc_status lcpc_leaves_tree_device(void *d_cvs, size_t n_chunks, size_t n_cols, void *d_hashes) {
-  // d_cvs [chunk][col][32] (consumed as scratch) -> d_hashes = leaves || merkle levels || root
-  if ((!d_cvs || !d_hashes) && n_cols) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  if (n_chunks == 0 || n_cols == 0 || (n_cols & (n_cols - 1)))
-    return fail(LCPC_ERR_INVALID_ARG, "n_chunks >= 1, n_cols a power of two");
-  lcpc_status st;
-  Device *dev = current_device(&st);
-  if (!dev) return st;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  HIP_TRY(leaves_from_cvs((uint32_t *)d_cvs, n_cols, (int)n_chunks, (uint8_t *)d_hashes, lease.s));
-  if (n_cols > 1) HIP_TRY(merkle_tree((uint8_t *)d_hashes, n_cols, lease.s));
-  HIP_TRY(hipStreamSynchronize(lease.s));
-  return LCPC_OK;
-}
-
-lcpc_status lcpc_shard_collapse_device(const lcpc_shard *s, const void *d_tensors, size_t n_tensors, void *d_out) {
-  if (!s || !d_out || (!d_tensors && s->n_rows)) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  if (n_tensors < 1 || n_tensors > 4) return fail(LCPC_ERR_INVALID_ARG, "1..4 tensors");
-  const int fid = s->e->fid, wb = field_bytes(fid);
-  const size_t np = s->e->n_per_row;
-  Device *dev = s->e->dev;
-  Lease lease(dev, POOL_HIGH);
-  HIP_TRY(hipSetDevice(dev->id));
-  if (s->n_rows == 0) {
-    HIP_TRY(hipMemsetAsync(d_out, 0, n_tensors * np * wb, lease.s));
-  } else {
-    DBuf scratch;
-    HIP_TRY(scratch.alloc(dev, collapse_scratch_bytes(fid, s->n_rows, np, (int)n_tensors)));
-    HIP_TRY(collapse_rows(fid, s->coeffs.as<uint32_t>(), s->n_rows, np, (const uint32_t *)d_tensors,
-                          (int)n_tensors, (uint32_t *)d_out, scratch.p, lease.s));
-  }
-  HIP_TRY(hipStreamSynchronize(lease.s));
-  return LCPC_OK;
-}
-
-lcpc_status lcpc_shard_gather_columns_device(const lcpc_shard *s, const uint64_t *idx, size_t n, void *d_out) {
-  if (!s || (!idx && n) || (!d_out && n)) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  const size_t nc = s->e->n_cols;
-  for (size_t k = 0; k < n; k++)
-    if (idx[k] >= nc) return fail(LCPC_PROVER_COLUMN_NUMBER, "ProverError::ColumnNumber");
-  if (!n || !s->n_rows) return LCPC_OK;
-  const int fid = s->e->fid;
-  Device *dev = s->e->dev;
-  Lease lease(dev, POOL_HIGH);
-  HIP_TRY(hipSetDevice(dev->id));
-  DBuf didx;
-  lcpc_status st;
-  if ((st = upload(dev, didx, idx, n * 8))) return st;
-  HIP_TRY(gather_columns(fid, s->comm.as<uint32_t>(), s->n_rows, nc, didx.as<uint64_t>(), n, (uint32_t *)d_out,
-                         lease.s, false, true));
-  HIP_TRY(hipStreamSynchronize(lease.s));
-  return LCPC_OK;
-}
-
-lcpc_status lcpc_field_sum_device(lcpc_field f, const void *d_vecs, size_t n_vecs, size_t len, uint64_t *out) {
-  if (!valid_field(f) || (!d_vecs && n_vecs * len) || (!out && len)) return fail(LCPC_ERR_INVALID_ARG, "arguments");
-  if (!len) return LCPC_OK;
-  const int wb = field_bytes(f);
-  if (n_vecs == 0) {
-    std::memset(out, 0, len * wb);
-    return LCPC_OK;
-  }
-  lcpc_status st;
-  Device *dev = current_device(&st);
-  if (!dev) return st;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  DBuf dout;
-  HIP_TRY(dout.alloc(dev, len * wb));
-  HIP_TRY(collapse_fold_rows(f, (const uint32_t *)d_vecs, n_vecs, len, dout.as<uint32_t>(), lease.s));
-  HIP_TRY(hipMemcpyAsync(out, dout.p, len * wb, hipMemcpyDeviceToHost, lease.s));
-  HIP_TRY(hipStreamSynchronize(lease.s));
-  return LCPC_OK;
-}
-
-lcpc_status lcpc_challenge_tensor(lcpc_transcript *tr, lcpc_field f, size_t n, uint64_t *out) {
-  // prove / verify degree-test tensor (lcpc-2d/src/lib.rs:1056-1062, 899-907)
-  if (!tr || !valid_field(f) || (!out && n)) return fail(LCPC_ERR_INVALID_ARG, "arguments");
-  std::vector<uint64_t> t;
-  challenge_tensor(*tr, f, n, t);
-  if (n) std::memcpy(out, t.data(), t.size() * 8);
-  return transcript_status(tr);
-}
-
-lcpc_status lcpc_challenge_columns(lcpc_transcript *tr, size_t n_cols, size_t n, uint64_t *out) {
-  // column choice (lcpc-2d/src/lib.rs:1101-1110, 932-941)
-  if (!tr || !n_cols || (!out && n)) return fail(LCPC_ERR_INVALID_ARG, "arguments");
-  std::vector<uint64_t> idx;
-  challenge_columns(*tr, n_cols, n, idx);
-  if (n) std::memcpy(out, idx.data(), n * 8);
-  return transcript_status(tr);
-}
-
-lcpc_status lcpc_transcript_append_field_elems(lcpc_transcript *tr, const uint8_t *label, size_t ln,
-                                               lcpc_field f, const uint64_t *elems, size_t n) {
-  // append_message(label, to_repr(e)) for every e (lcpc-2d/src/lib.rs:1075-1077, 1096-1098)
-  if (!tr || !valid_field(f) || (!elems && n)) return fail(LCPC_ERR_INVALID_ARG, "arguments");
-  if (!n) return LCPC_OK;
-  lcpc_status st;
-  Device *dev = current_device(&st);
-  if (!dev) return st;
-  Lease lease(dev, POOL_HIGH);
-  HIP_TRY(hipSetDevice(dev->id));
-  const int wb = field_bytes(f);
-  DBuf de;
-  if ((st = upload(dev, de, elems, n * wb))) return st;
-  const uint8_t *repr = nullptr;
-  if ((st = to_repr_host(dev, f, de.as<uint32_t>(), n, &repr))) return st;
-  tr->append_messages(label, ln, repr, wb, n);
-  return transcript_status(tr);
-}
-
-}  // extern "C"
-
-// ================================================================= PoS encoded files
-// The `.porenc` / `.portree` formats of proof-of-storage/src/lcpc_online.
-// The whole data path (byte packing, Ligero encode, canonical conversion + transpose to the
-// column-major file layout, BLAKE3 column digests, Merkle tree) runs on the GPU in row batches
-// that end on BLAKE3 chunk boundaries of the column messages, so each batch contributes whole
-// chunk chaining values and the file streams through bounded device memory.  The host only
-// moves bytes between the caller's buffers (typically mmaps of the files) and page-locked
-// staging, with the copies of one batch overlapping the GPU work of the next.
-namespace {
-
-constexpr int POS_FID = LCPC_FT63;  // WriteableFt63: Ft63's modulus (writable_ft63.rs:8-12)
-constexpr size_t POS_WB = 8;        // F::WRITTEN_BYTES_WIDTH = size_of::<F>() (data_field.rs:24)
-constexpr size_t POS_DB = 7;        // F::DATA_BYTE_CAPACITY (data_field.rs:22)
-constexpr size_t POS_STAGE_BYTES = (size_t)256 << 20;  // encoded bytes per pipelined batch
-
-template <class Fn>
-void parallel_for(size_t n, Fn fn) {
-  const size_t hw = std::max(1u, std::thread::hardware_concurrency());
-  const size_t T = std::min<size_t>(n, std::min<size_t>(16, hw));
-  if (T <= 1) {
-    for (size_t i = 0; i < n; i++) fn(i);
-    return;
-  }
-  std::atomic<size_t> next{0};
-  const size_t grain = std::max<size_t>(1, n / (T * 8));
-  std::vector<std::thread> th;
-  for (size_t t = 0; t < T; t++)
-    th.emplace_back([&] {
-      for (;;) {
-        const size_t i0 = next.fetch_add(grain);
-        if (i0 >= n) break;
-        const size_t i1 = std::min(n, i0 + grain);
-        for (size_t i = i0; i < i1; i++) fn(i);
-      }
-    });
-  for (auto &t : th) t.join();
-}
-
-// large memcpy split over host threads
-void par_memcpy(uint8_t *dst, const uint8_t *src, size_t n) {
-  constexpr size_t BLK = (size_t)8 << 20;
-  if (n <= BLK) {
-    if (n) std::memcpy(dst, src, n);
-    return;
-  }
-  parallel_for((n + BLK - 1) / BLK, [&](size_t i) {
-    const size_t o = i * BLK;
-    std::memcpy(dst + o, src + o, std::min(BLK, n - o));
-  });
-}
-
-// a page-locked block from the device's pool, returned at scope exit
-struct Pinned {
-  Device *d = nullptr;
-  void *p = nullptr;
-  size_t n = 0;
-  Pinned() = default;
-  Pinned(const Pinned &) = delete;
-  Pinned &operator=(const Pinned &) = delete;
-  ~Pinned() { reset(); }
-  void reset() {
-    if (d && p) d->pinned_put(p);
-    p = nullptr;
-    n = 0;
-  }
-  bool get(Device *dev, size_t bytes) {
-    reset();
-    d = dev;
-    p = dev->pinned_get(bytes);
-    n = p ? bytes : 0;
-    return p != nullptr;
-  }
-  uint8_t *b() const { return (uint8_t *)p; }
-};
-
-// events destroyed at scope exit
-struct Events {
-  hipEvent_t e[2] = {nullptr, nullptr};
-  ~Events() {
-    for (auto &x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-  hipError_t init() {
-    for (auto &x : e)
-      if (!x) {
-        hipError_t r = hipEventCreateWithFlags(&x, hipEventDisableTiming);
-        if (r != hipSuccess) return r;
-      }
-    return hipSuccess;
-  }
-};
-
-lcpc_status pos_dims_check(size_t pre, size_t enc) {
-  // EncodedFileWriter::convert_unencoded_file / new (encoded_file_writer.rs:53-67, 146-163)
-  if (pre < 1) return fail(LCPC_ERR_INVALID_ARG, "Number of pre-encoded columns must be greater than 0");
-  if (enc < 2 || (enc & (enc - 1)))
-    return fail(LCPC_ERR_INVALID_ARG, "Number of encoded columns must be a power of 2 (>= 2)");
-  if (enc <= pre)
-    return fail(LCPC_ERR_INVALID_ARG, "Number of encoded columns must be greater than the number of columns");
-  if ((int)log2_np2(enc) > field_info(POS_FID).s) return fail(LCPC_FFT_TOO_BIG, "FFTError::TooBig");
-  return LCPC_OK;
-}
-
-}  // namespace
-
-// EncodedFileWriter (encoded_file_writer.rs:24-38): bytes arrive in pushes; whole batches of
-// rows are encoded once the data provably continues past them (so no chunk they close can be
-// a column message's last chunk), the rest at finalize when the row count is known.
-struct lcpc_pos_writer {
-  std::unique_ptr<lcpc_encoding> e;
-  size_t pre = 0, enc = 0, row_capacity = 0;
-  uint8_t *porenc = nullptr;
-  size_t cpb = 1, bmax = 1;        // chunks per batch, rows per batch (at most)
-  size_t rows_done = 0, chunks_done = 0, bytes_received = 0;
-  bool finalized = false;
-  Pinned pend;                     // data bytes from row rows_done on (page-locked)
-  size_t pend_len = 0;
-  std::vector<uint8_t> cvs;        // [chunk][column] chaining values of the chunks done
-  size_t buf_rows = 0;             // rows the batch buffers below hold (grown on demand)
-  DBuf dbytes, coeffs, comm, dout, dcv;
-  Pinned stg[2];
-  Events ev;
-};
-
-namespace {
-
-size_t pos_row_bytes(const lcpc_pos_writer *w) { return w->pre * POS_DB; }
-
-lcpc_status writer_append(lcpc_pos_writer *w, const uint8_t *bytes, size_t n) {
-  if (!n) return LCPC_OK;
-  if (w->pend_len + n > w->pend.n) {
-    Pinned bigger;
-    if (!bigger.get(w->e->dev, std::max(w->pend_len + n, std::max<size_t>(1 << 20, 2 * w->pend.n))))
-      return fail(LCPC_ERR_OUT_OF_MEMORY, "pinned host staging");
-    par_memcpy(bigger.b(), w->pend.b(), w->pend_len);
-    std::swap(w->pend.p, bigger.p);
-    std::swap(w->pend.n, bigger.n);
-    std::swap(w->pend.d, bigger.d);
-  }
-  par_memcpy(w->pend.b() + w->pend_len, bytes, n);
-  w->pend_len += n;
-  return LCPC_OK;
-}
-
-// Encode chunks [chunks_done, c_end) (rows from pend), n_rows_cv = the row count the chunk
-// chaining values are computed for (exact at finalize; any larger-than-covered count before).
-lcpc_status writer_run(lcpc_pos_writer *w, size_t c_end, size_t n_rows_cv, size_t n_rows_max) {
-  if (c_end <= w->chunks_done) return LCPC_OK;
-  const int fid = POS_FID;
-  const size_t pre = w->pre, enc = w->enc, rb = pos_row_bytes(w);
-  Device *dev = w->e->dev;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  hipStream_t s = lease.s;
-  for (auto *b : {&w->dbytes, &w->coeffs, &w->comm, &w->dout, &w->dcv}) b->s = s;
-  lcpc_status st;
-  struct Pending {
-    int slot = -1;
-    size_t r0 = 0, rows = 0;
-  } pend;
-  auto scatter = [&](const Pending &p) -> lcpc_status {
-    if (p.slot < 0) return LCPC_OK;
-    HIP_TRY(hipEventSynchronize(w->ev.e[p.slot]));
-    const uint8_t *src = w->stg[p.slot].b();
-    uint8_t *dst = w->porenc;
-    const size_t cap = w->row_capacity;
-    parallel_for(enc, [&](size_t c) {
-      std::memcpy(dst + (c * cap + p.r0) * POS_WB, src + c * p.rows * POS_WB, p.rows * POS_WB);
-    });
-    return LCPC_OK;
-  };
-  const size_t pend_row0 = w->rows_done;
-  // batch buffers sized for the largest batch of this run (small files stay small)
-  const size_t need_rows = std::min(w->bmax, std::max<size_t>(1, n_rows_max - std::min(n_rows_max, pend_row0)));
-  if (need_rows > w->buf_rows) {
-    HIP_TRY(w->dbytes.alloc(dev, need_rows * pre * POS_DB + 64));
-    HIP_TRY(w->coeffs.alloc(dev, need_rows * pre * POS_WB));
-    HIP_TRY(w->comm.alloc(dev, need_rows * enc * POS_WB));
-    HIP_TRY(w->dout.alloc(dev, need_rows * enc * POS_WB));
-    for (auto &x : w->stg)
-      if (!x.get(dev, need_rows * enc * POS_WB)) return fail(LCPC_ERR_OUT_OF_MEMORY, "pinned host staging");
-    w->buf_rows = need_rows;
-  }
-  // chaining values land in w->cvs by async copies: no reallocation while they are queued
-  w->cvs.reserve(c_end * w->enc * 32);
-  int k = 0;
-  for (size_t c_lo = w->chunks_done; c_lo < c_end; c_lo += w->cpb, k++) {
-    const size_t c_hi = std::min(c_end, c_lo + w->cpb);
-    const size_t r0 = std::min(n_rows_max, lcpc_leaf_chunk_first_row((lcpc_field)fid, c_lo));
-    const size_t r1 = std::min(n_rows_max, lcpc_leaf_chunk_first_row((lcpc_field)fid, c_hi));
-    const size_t rr1 = c_hi == leaf_n_chunks(fid, n_rows_cv) ? n_rows_max : r1;
-    const size_t B = rr1 - r0;
-    if (B > w->buf_rows) return fail(LCPC_ERR_INVALID_ARG, "internal: batch larger than its buffers");
-    if (B) {
-      if (w->porenc && r0 + B > w->row_capacity) return fail(LCPC_ERR_INVALID_ARG, "row capacity exceeded");
-      // rows r0..r0+B are data bytes [rb (r0 - pend_row0), ...) of pend (the last may be short)
-      const size_t b0 = (r0 - pend_row0) * rb;
-      const size_t b1 = std::min(w->pend_len, b0 + B * rb);
-      const size_t ne = (b1 - b0 + POS_DB - 1) / POS_DB;
-      HIP_TRY(hipMemcpyAsync(w->dbytes.p, w->pend.b() + b0, b1 - b0, hipMemcpyHostToDevice, s));
-      if (B * pre > ne)
-        HIP_TRY(hipMemsetAsync(w->coeffs.as<uint8_t>() + ne * POS_WB, 0, (B * pre - ne) * POS_WB, s));
-      HIP_TRY(pos_pack7(w->dbytes.as<uint8_t>(), b1 - b0, w->coeffs.as<uint64_t>(), s));
-      // canonical codeword: the file's repr words and the leaves' input without conversion
-      HIP_TRY(ntt_rows(w->e->plan, w->coeffs.as<uint32_t>(), pre, pre, w->comm.as<uint32_t>(), enc, B, s,
-                       nullptr, 0, true));
-      if (w->porenc)  // (digest-only writers keep no image)
-        HIP_TRY(transpose_elems(fid, w->comm.as<uint32_t>(), B, enc, enc, enc, w->dout.as<uint32_t>(), B, s));
-    }
-    // column-digest chunks of these rows (ColumnDigestAccumulator::update, :62-87)
-    HIP_TRY(leaf_chunk_cvs(fid, w->comm.as<uint32_t>(), r0, n_rows_cv, enc, enc, c_lo, c_hi,
-                           w->dcv.as<uint32_t>(), s, true));
-    const size_t cv_bytes = (c_hi - c_lo) * enc * 32;
-    const size_t cv_off = w->cvs.size();
-    w->cvs.resize(cv_off + cv_bytes);
-    HIP_TRY(hipMemcpyAsync(w->cvs.data() + cv_off, w->dcv.p, cv_bytes, hipMemcpyDeviceToHost, s));
-    if (B && w->porenc) {
-      const int slot = k & 1;
-      HIP_TRY(hipMemcpyAsync(w->stg[slot].p, w->dout.p, B * enc * POS_WB, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipEventRecord(w->ev.e[slot], s));
-      if ((st = scatter(pend))) return st;  // overlaps this batch's GPU work
-      pend = Pending{slot, r0, B};
-    }
-    w->chunks_done = c_hi;
-    w->rows_done = rr1;
-  }
-  if ((st = scatter(pend))) return st;
-  HIP_TRY(hipStreamSynchronize(s));
-  for (auto *b : {&w->dbytes, &w->coeffs, &w->comm, &w->dout, &w->dcv}) b->settle();
-  const size_t used = std::min(w->pend_len, (w->rows_done - pend_row0) * rb);
-  std::memmove(w->pend.b(), w->pend.b() + used, w->pend_len - used);
-  w->pend_len -= used;
-  return LCPC_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-lcpc_status lcpc_pos_writer_new(size_t pre, size_t enc, uint8_t *porenc, size_t row_capacity,
-                                size_t batch_rows, lcpc_pos_writer **out) {
-  lcpc_status st = pos_dims_check(pre, enc);
-  if (st) return st;
-  if (!out || (!porenc && row_capacity)) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  lcpc_encoding *ep = nullptr;
-  if ((st = make_rs_encoding(POS_FID, pre, enc, 0, 0, &ep))) return st;
-  auto w = std::make_unique<lcpc_pos_writer>();
-  w->e.reset(ep);
-  w->pre = pre;
-  w->enc = enc;
-  w->porenc = porenc;
-  w->row_capacity = row_capacity;
-  const size_t rows_per_chunk = 1024 / POS_WB;
-  size_t want = batch_rows;
-  if (!want) want = std::max<size_t>(rows_per_chunk, POS_STAGE_BYTES / (enc * POS_WB));
-  w->cpb = std::max<size_t>(1, want / rows_per_chunk);
-  w->bmax = w->cpb * rows_per_chunk;
-  Device *dev = w->e->dev;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  HIP_TRY(w->dcv.alloc(dev, w->cpb * enc * 32));
-  HIP_TRY(w->ev.init());
-  HIP_TRY(hipStreamSynchronize(lease.s));
-  for (auto *b : {&w->dbytes, &w->coeffs, &w->comm, &w->dout, &w->dcv}) b->settle();
-  *out = w.release();
-  return LCPC_OK;
-}
-
-void lcpc_pos_writer_free(lcpc_pos_writer *w) { delete w; }
-
-lcpc_status lcpc_pos_writer_set_target(lcpc_pos_writer *w, uint8_t *porenc, size_t row_capacity) {
-  // after the caller grew the file (EncodedFileReader::set_new_capacity layout, :348-381)
-  if (!w || (!porenc && row_capacity)) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  if (row_capacity < w->rows_done) return fail(LCPC_ERR_INVALID_ARG, "row_capacity < rows written");
-  w->porenc = porenc;
-  w->row_capacity = row_capacity;
-  return LCPC_OK;
-}
-
-size_t lcpc_pos_writer_rows_written(const lcpc_pos_writer *w) { return w ? w->rows_done : 0; }
-
-lcpc_status lcpc_pos_writer_push_bytes(lcpc_pos_writer *w, const uint8_t *bytes, size_t n) {
-  // push_bytes (encoded_file_writer.rs:233-262)
-  if (!w || (!bytes && n)) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  if (w->finalized) return fail(LCPC_ERR_INVALID_ARG, "writer already finalized");
-  lcpc_status st;
-  const size_t rb = pos_row_bytes(w);
-  // large pushes are taken a batch at a time, so the staging stays about a batch
-  const size_t step = std::max<size_t>(1, w->bmax * rb);
-  for (size_t off = 0; off < n || (n == 0 && off == 0); off += step) {
-    const size_t m = std::min(step, n - off);
-    if ((st = writer_append(w, bytes + off, m))) return st;
-    w->bytes_received += m;
-    // whole batches whose rows are followed by at least one more full row
-    const size_t full_rows = w->rows_done + w->pend_len / rb;
-    size_t c_end = w->chunks_done;
-    while (lcpc_leaf_chunk_first_row(LCPC_FT63, c_end + w->cpb) < full_rows) c_end += w->cpb;
-    if (c_end > w->chunks_done &&
-        (st = writer_run(w, c_end, full_rows, lcpc_leaf_chunk_first_row(LCPC_FT63, c_end))))
-      return st;
-    if (n == 0) break;
-  }
-  return LCPC_OK;
-}
-
-lcpc_status lcpc_pos_writer_finalize(lcpc_pos_writer *w, uint8_t *digests, uint8_t *tree,
-                                     size_t *rows_written, size_t *bytes_of_data) {
-  // finalize_to_column_digest / _to_commit / _to_merkle_tree (encoded_file_writer.rs:452-501):
-  // digests = the enc column digests, tree = MerkleTree::to_bytes (2 enc - 1 digests); either
-  // may be NULL
-  if (!w) return fail(LCPC_ERR_INVALID_ARG, "null writer");
-  if (w->finalized) return fail(LCPC_ERR_INVALID_ARG, "writer already finalized");
-  const size_t rb = pos_row_bytes(w);
-  const size_t n_rows = w->rows_done + (w->pend_len + rb - 1) / rb;
-  if (w->porenc && n_rows > w->row_capacity) return fail(LCPC_ERR_INVALID_ARG, "row capacity exceeded");
-  const int fid = POS_FID;
-  const size_t n_chunks = leaf_n_chunks(fid, n_rows);
-  lcpc_status st = writer_run(w, n_chunks, n_rows, n_rows);
-  if (st) return st;
-  w->finalized = true;
-  const size_t enc = w->enc;
-  Device *dev = w->e->dev;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  hipStream_t s = lease.s;
-  DBuf dc, hashes;
-  if ((st = upload(dev, dc, w->cvs.data(), w->cvs.size()))) return st;
-  HIP_TRY(hashes.alloc(dev, (2 * enc - 1) * 32));
-  HIP_TRY(leaves_from_cvs(dc.as<uint32_t>(), enc, (int)n_chunks, hashes.as<uint8_t>(), s));
-  if (tree) {
-    HIP_TRY(merkle_tree(hashes.as<uint8_t>(), enc, s));
-    HIP_TRY(hipMemcpyAsync(tree, hashes.p, (2 * enc - 1) * 32, hipMemcpyDeviceToHost, s));
-  }
-  if (digests) HIP_TRY(hipMemcpyAsync(digests, hashes.p, enc * 32, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (rows_written) *rows_written = w->rows_done;
-  if (bytes_of_data) *bytes_of_data = w->bytes_received;
-  return LCPC_OK;
-}
-
-lcpc_status lcpc_pos_encode_file_batched(const uint8_t *data, size_t n_bytes, size_t pre, size_t enc,
-                                         size_t row_capacity, uint8_t *porenc, uint8_t *tree,
-                                         size_t *rows_written, size_t batch_rows) {
-  lcpc_status st = pos_dims_check(pre, enc);
-  if (st) return st;
-  if (!tree || (!data && n_bytes)) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  const size_t n_rows = ((n_bytes + POS_DB - 1) / POS_DB + pre - 1) / pre;
-  if (rows_written) *rows_written = n_rows;
-  if (row_capacity < n_rows) return fail(LCPC_ERR_INVALID_ARG, "row_capacity < rows to write");
-  lcpc_pos_writer *w = nullptr;
-  if ((st = lcpc_pos_writer_new(pre, enc, porenc, row_capacity, batch_rows, &w))) return st;
-  std::unique_ptr<lcpc_pos_writer> guard(w);
-  if ((st = lcpc_pos_writer_push_bytes(w, data, n_bytes))) return st;
-  return lcpc_pos_writer_finalize(w, nullptr, tree, rows_written, nullptr);
-}
-
-lcpc_status lcpc_pos_encode_file(const uint8_t *data, size_t n_bytes, size_t pre, size_t enc,
-                                 size_t row_capacity, uint8_t *porenc, uint8_t *tree,
-                                 size_t *rows_written) {
-  return lcpc_pos_encode_file_batched(data, n_bytes, pre, enc, row_capacity, porenc, tree, rows_written, 0);
-}
-
-lcpc_status lcpc_pos_reencode_rows(const uint8_t *bytes, size_t n_bytes, size_t pre, size_t enc,
-                                   size_t row_lo, uint8_t *porenc, size_t row_capacity) {
-  // FileHandler::reencode_row / EncodedFileReader::replace_row_with_decoded_bytes +
-  // replace_encoded_row (file_handler.rs:380-402, encoded_file_reader.rs:196-315) for the rows
-  // [row_lo, row_lo + ceil(n_bytes / (7 pre))): pack each row's bytes (the last row may be
-  // short: zero-padded), encode, and write the canonical repr into the column-major image at
-  // column stride row_capacity.  Batches of rows go through the GPU like the writer's.
-  lcpc_status st = pos_dims_check(pre, enc);
-  if (st) return st;
-  if ((!bytes || !porenc) && n_bytes) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  const size_t rb = pre * POS_DB;
-  const size_t n_rows = (n_bytes + rb - 1) / rb;
-  if (!n_rows) return LCPC_OK;
-  if (row_lo + n_rows > row_capacity) return fail(LCPC_ERR_INVALID_ARG, "rows beyond row_capacity");
-  lcpc_encoding *ep = nullptr;
-  if ((st = make_rs_encoding(POS_FID, pre, enc, 0, 0, &ep))) return st;
-  std::unique_ptr<lcpc_encoding> eg(ep);
-  Device *dev = ep->dev;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  hipStream_t s = lease.s;
-  const size_t bmax = std::min(n_rows, std::max<size_t>(1, POS_STAGE_BYTES / (enc * POS_WB)));
-  DBuf dbytes, coeffs, comm, dout;
-  for (auto *b : {&dbytes, &coeffs, &comm, &dout}) b->s = s;
-  HIP_TRY(dbytes.alloc(dev, bmax * rb + 64));
-  HIP_TRY(coeffs.alloc(dev, bmax * pre * POS_WB));
-  HIP_TRY(comm.alloc(dev, bmax * enc * POS_WB));
-  HIP_TRY(dout.alloc(dev, bmax * enc * POS_WB));
-  Pinned stg;
-  if (!stg.get(dev, bmax * enc * POS_WB)) return fail(LCPC_ERR_OUT_OF_MEMORY, "pinned host staging");
-  for (size_t r0 = 0; r0 < n_rows; r0 += bmax) {
-    const size_t B = std::min(bmax, n_rows - r0);
-    const size_t b0 = r0 * rb, b1 = std::min(n_bytes, b0 + B * rb);
-    const size_t ne = (b1 - b0 + POS_DB - 1) / POS_DB;
-    HIP_TRY(hipMemcpyAsync(dbytes.p, bytes + b0, b1 - b0, hipMemcpyHostToDevice, s));
-    if (B * pre > ne) HIP_TRY(hipMemsetAsync(coeffs.as<uint8_t>() + ne * POS_WB, 0, (B * pre - ne) * POS_WB, s));
-    HIP_TRY(pos_pack7(dbytes.as<uint8_t>(), b1 - b0, coeffs.as<uint64_t>(), s));
-    HIP_TRY(ntt_rows(ep->plan, coeffs.as<uint32_t>(), pre, pre, comm.as<uint32_t>(), enc, B, s, nullptr, 0, true));
-    HIP_TRY(transpose_elems(POS_FID, comm.as<uint32_t>(), B, enc, enc, enc, dout.as<uint32_t>(), B, s));
-    HIP_TRY(hipMemcpyAsync(stg.p, dout.p, B * enc * POS_WB, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    const uint8_t *src = stg.b();
-    parallel_for(enc, [&](size_t c) {
-      std::memcpy(porenc + (c * row_capacity + row_lo + r0) * POS_WB, src + c * B * POS_WB, B * POS_WB);
-    });
-  }
-  for (auto *b : {&dbytes, &coeffs, &comm, &dout}) b->settle();
-  return LCPC_OK;
-}
-
-lcpc_status lcpc_pos_porenc_tree(const uint8_t *porenc, size_t enc, size_t rows_written,
-                                 size_t row_capacity, uint8_t *tree) {
-  // EncodedFileReader::process_file_to_merkle_tree (encoded_file_reader.rs:328-346): every
-  // column's first rows_written elements, hashed after the 32-byte zero block
-  if (enc < 2 || (enc & (enc - 1))) return fail(LCPC_ERR_INVALID_ARG, "encoded width must be a power of 2 (>= 2)");
-  if (!tree || (!porenc && rows_written)) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  if (rows_written > row_capacity) return fail(LCPC_ERR_INVALID_ARG, "rows_written > row_capacity");
-  lcpc_status st;
-  Device *dev = current_device(&st);
-  if (!dev) return st;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  hipStream_t s = lease.s;
-  const int fid = POS_FID;
-  const size_t col_bytes = rows_written * POS_WB;
-  const size_t cpb = col_bytes ? std::max<size_t>(1, std::min(enc, POS_STAGE_BYTES / col_bytes)) : enc;
-  DBuf hashes, dcols[2], scratch[2], dbad;
-  HIP_TRY(hashes.alloc(dev, (2 * enc - 1) * 32));
-  for (int i = 0; i < 2; i++) {
-    HIP_TRY(dcols[i].alloc(dev, cpb * col_bytes));
-    HIP_TRY(scratch[i].alloc(dev, leaf_hash_scratch_bytes(fid, rows_written, cpb)));
-  }
-  HIP_TRY(dbad.alloc(dev, 4));
-  HIP_TRY(hipMemsetAsync(dbad.p, 0, 4, s));
-  Pinned stg[2];
-  Events ev;
-  HIP_TRY(ev.init());
-  if (col_bytes)
-    for (auto &x : stg)
-      if (!x.get(dev, cpb * col_bytes)) return fail(LCPC_ERR_OUT_OF_MEMORY, "pinned host staging");
-  int k = 0;
-  for (size_t c0 = 0; c0 < enc; c0 += cpb, k++) {
-    const size_t nc = std::min(enc, c0 + cpb) - c0;
-    const int slot = k & 1;
-    if (col_bytes) {
-      if (k >= 2) HIP_TRY(hipEventSynchronize(ev.e[slot]));  // its last upload has left it
-      parallel_for(nc, [&](size_t c) {
-        std::memcpy(stg[slot].b() + c * col_bytes, porenc + (c0 + c) * row_capacity * POS_WB, col_bytes);
-      });
-      HIP_TRY(hipMemcpyAsync(dcols[slot].p, stg[slot].p, nc * col_bytes, hipMemcpyHostToDevice, s));
-      HIP_TRY(hipEventRecord(ev.e[slot], s));
-      // raw_bytes_to_field_vec: from_repr(..).unwrap() (data_field.rs:72-81)
-      HIP_TRY(convert(fid, dcols[slot].as<uint32_t>(), dcols[slot].as<uint32_t>(), nc * rows_written, true, s,
-                      dbad.as<uint32_t>()));
-    }
-    HIP_TRY(leaf_hashes_cols(fid, dcols[slot].as<uint32_t>(), rows_written, nc, hashes.as<uint8_t>() + c0 * 32,
-                             scratch[slot].p, s));
-  }
-  HIP_TRY(merkle_tree(hashes.as<uint8_t>(), enc, s));
-  uint32_t bad = 0;
-  HIP_TRY(hipMemcpyAsync(&bad, dbad.p, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(tree, hashes.p, (2 * enc - 1) * 32, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (bad) return fail(LCPC_ERR_INVALID_ARG, "encoded file holds a non-canonical element (from_repr fails)");
-  return LCPC_OK;
-}
-
-lcpc_status lcpc_pos_decode_porenc(const uint8_t *porenc, size_t pre, size_t enc, size_t row_capacity,
-                                   size_t row_lo, size_t row_hi, uint8_t *out) {
-  // EncodedFileReader::get_unencoded_row_bytes / decode_to_target_file (encoded_file_reader.rs:
-  // 59-91): gather each row's enc elements from the columns, decode_row (ifft_oi), keep the
-  // first pre coefficients, 7 data bytes each
-  lcpc_status st = pos_dims_check(pre, enc);
-  if (st) return st;
-  if (row_lo > row_hi || row_hi > row_capacity) return fail(LCPC_ERR_INVALID_ARG, "row range");
-  const size_t n = row_hi - row_lo;
-  if (!n) return LCPC_OK;
-  if (!porenc || !out) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  Device *dev = current_device(&st);
-  if (!dev) return st;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  hipStream_t s = lease.s;
-  const int fid = POS_FID;
-  const int log_n = (int)log2_np2(enc);
-  NttPlan plan;
-  hipError_t he = ntt_plan_init(plan, fid, log_n, true, s);
-  if (he != hipSuccess) {
-    ntt_plan_free(plan);
-    if (he == hipErrorInvalidValue) return fail(LCPC_ERR_UNSUPPORTED, "length beyond the NTT range");
-    HIP_TRY(he);
-  }
-  struct PlanGuard {
-    NttPlan &p;
-    hipStream_t s;
-    ~PlanGuard() {
-      (void)hipStreamSynchronize(s);
-      ntt_plan_free(p);
-    }
-  } guard{plan, s};
-  uint32_t inv[8] = {0};
-  inv_pow2_canon(fid, log_n, inv);
-  const size_t bmax = std::max<size_t>(1, std::min(n, POS_STAGE_BYTES / (enc * POS_WB)));
-  DBuf a, b, dbytes, dbad;
-  HIP_TRY(a.alloc(dev, bmax * enc * POS_WB));
-  HIP_TRY(b.alloc(dev, bmax * enc * POS_WB));
-  HIP_TRY(dbytes.alloc(dev, bmax * pre * POS_DB + 64));
-  HIP_TRY(dbad.alloc(dev, 4));
-  HIP_TRY(hipMemsetAsync(dbad.p, 0, 4, s));
-  Pinned stg[2], ostg[2];
-  Events in_ev, out_ev;
-  HIP_TRY(in_ev.init());
-  HIP_TRY(out_ev.init());
-  for (int i = 0; i < 2; i++)
-    if (!stg[i].get(dev, bmax * enc * POS_WB) || !ostg[i].get(dev, bmax * pre * POS_DB))
-      return fail(LCPC_ERR_OUT_OF_MEMORY, "pinned host staging");
-  struct Done {
-    int slot = -1;
-    size_t r0 = 0, rows = 0;
-  } done;
-  auto copy_out = [&](const Done &d) -> lcpc_status {
-    if (d.slot < 0) return LCPC_OK;
-    HIP_TRY(hipEventSynchronize(out_ev.e[d.slot]));
-    par_memcpy(out + (d.r0 - row_lo) * pre * POS_DB, ostg[d.slot].b(), d.rows * pre * POS_DB);
-    return LCPC_OK;
-  };
-  int k = 0;
-  for (size_t r0 = row_lo; r0 < row_hi; r0 += bmax, k++) {
-    const size_t B = std::min(row_hi, r0 + bmax) - r0;
-    const int slot = k & 1;
-    if (k >= 2) HIP_TRY(hipEventSynchronize(in_ev.e[slot]));  // its last upload has left it
-    parallel_for(enc, [&](size_t c) {
-      std::memcpy(stg[slot].b() + c * B * POS_WB, porenc + (c * row_capacity + r0) * POS_WB, B * POS_WB);
-    });
-    HIP_TRY(hipMemcpyAsync(a.p, stg[slot].p, enc * B * POS_WB, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(in_ev.e[slot], s));
-    // [enc][B] canonical -> [B][enc] Montgomery (get_encoded_row + raw_bytes_to_field_vec)
-    HIP_TRY(transpose_elems(fid, a.as<uint32_t>(), enc, B, B, B, b.as<uint32_t>(), enc, s, TR_TO_MONT,
-                            dbad.as<uint32_t>()));
-    // ifft_oi (see lcpc_ifft_oi_rows): the decoded rows end in x, y is free
-    uint32_t *x = b.as<uint32_t>(), *y = a.as<uint32_t>();
-    if (LCPC_FFT_OUTPUT_BITREV) {
-      HIP_TRY(bitrev_scale(fid, x, y, log_n, B, nullptr, s));
-      std::swap(x, y);
-    }
-    HIP_TRY(ntt_rows(plan, x, enc, enc, y, enc, B, s));
-    HIP_TRY(bitrev_scale(fid, y, x, log_n, B, inv, s));
-    // decoded_row.drain(pre..) then field_vec_to_byte_vec
-    HIP_TRY(hipMemcpy2DAsync(y, pre * POS_WB, x, enc * POS_WB, pre * POS_WB, B, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(pos_unpack7(reinterpret_cast<const uint64_t *>(y), B * pre, dbytes.as<uint8_t>(), B * pre * POS_DB, s));
-    if (k >= 2) HIP_TRY(hipEventSynchronize(out_ev.e[slot]));
-    HIP_TRY(hipMemcpyAsync(ostg[slot].p, dbytes.p, B * pre * POS_DB, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipEventRecord(out_ev.e[slot], s));
-    if ((st = copy_out(done))) return st;  // overlaps this batch's GPU work
-    done = Done{slot, r0, B};
-  }
-  if ((st = copy_out(done))) return st;
-  uint32_t bad = 0;
-  HIP_TRY(hipMemcpyAsync(&bad, dbad.p, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (bad) return fail(LCPC_ERR_INVALID_ARG, "encoded file holds a non-canonical element (from_repr fails)");
-  return LCPC_OK;
-}
-
-}  // extern "C"
-
-// Column chunk-CV cache of a stored file: the chaining value of every 1-KiB BLAKE3 chunk of every
-// column message (32 zero bytes || the column's rows_written canonical elements), [chunk][column],
-// kept in device memory.  A chunk's value depends only on its bytes, its counter and whether it is
-// the message's only chunk, so after an edit or an append only the chunks whose rows, length or
-// one-chunk flag changed are read from the image and rehashed; the column digests are one
-// non-clobbering fold of the cache (leaves_fold_cvs) and the tree follows as everywhere else.
-struct lcpc_pos_chunk_cache {
-  Device *dev = nullptr;
-  size_t enc = 0, rows = 0, n_chunks = 0, cap_chunks = 0;
-  DBuf cvs;  // cap_chunks x enc x 32 B, the first n_chunks chunk rows valid
-};
-
-namespace {
-
-size_t pos_chunk_of_row(size_t row) { return (32 + row * POS_WB) / 1024; }
-
-lcpc_status pos_update_chunk_range(size_t old_rows, size_t new_rows, size_t row_lo, size_t row_hi,
-                                   size_t *chunk_lo, size_t *chunk_hi) {
-  if (new_rows < old_rows) return fail(LCPC_ERR_INVALID_ARG, "a stored file's row count cannot shrink");
-  if (row_lo > row_hi || row_hi > new_rows) return fail(LCPC_ERR_INVALID_ARG, "row range");
-  size_t lo = 0, hi = 0;
-  if (row_lo < row_hi) {
-    lo = pos_chunk_of_row(row_lo);
-    hi = pos_chunk_of_row(row_hi - 1) + 1;
-  }
-  if (new_rows > old_rows) {
-    // the old last chunk changes length (or, the only chunk so far, loses ROOT); every later one is new
-    const size_t old_last = leaf_n_chunks(POS_FID, old_rows) - 1;
-    lo = row_lo < row_hi ? std::min(lo, old_last) : old_last;
-    hi = leaf_n_chunks(POS_FID, new_rows);
-  }
-  *chunk_lo = lo;
-  *chunk_hi = hi;
-  return LCPC_OK;
-}
-
-// Chunks [c_lo, c_hi) of every column of the image (messages of n_rows rows) hashed into dst, a
-// device [chunk][enc] array whose first chunk row is chunk c_lo: only those chunks' rows are read,
-// enc strided slices staged through page-locked memory a block of columns at a time, each block's
-// host copy overlapping the previous block's upload and hashing.  *bad (device) collects the
-// not-< p flag.  The image is the mapping porenc or, with fd >= 0, the open file fd read with
-// pread: mapping and unmapping a multi-GB file costs more than an update's 1 KiB per column.
-lcpc_status cache_hash_chunks(Device *dev, hipStream_t s, const uint8_t *porenc, int fd, size_t enc,
-                              size_t row_capacity, size_t n_rows, size_t c_lo, size_t c_hi, uint32_t *dst,
-                              uint32_t *bad) {
-  const int fid = POS_FID;
-  const size_t n_chunks = leaf_n_chunks(fid, n_rows);
-  const size_t r_lo = std::min(n_rows, lcpc_leaf_chunk_first_row((lcpc_field)fid, c_lo));
-  const size_t r_hi = c_hi == n_chunks ? n_rows : lcpc_leaf_chunk_first_row((lcpc_field)fid, c_hi);
-  const size_t R = r_hi - r_lo;
-  const size_t col_elems = R + (R & 1);  // 16-byte aligned slices (the kernel masks the pad)
-  const size_t col_bytes = col_elems * POS_WB;
-  const size_t cpb = col_bytes ? std::max<size_t>(1, std::min(enc, POS_STAGE_BYTES / col_bytes)) : enc;
-  DBuf dcols[2];
-  Pinned stg[2];
-  Events ev;
-  HIP_TRY(ev.init());
-  for (int i = 0; i < 2; i++) {
-    HIP_TRY(dcols[i].alloc(dev, cpb * col_bytes));
-    if (col_bytes && !stg[i].get(dev, cpb * col_bytes)) return fail(LCPC_ERR_OUT_OF_MEMORY, "pinned host staging");
-  }
-  int k = 0;
-  for (size_t c0 = 0; c0 < enc; c0 += cpb, k++) {
-    const size_t nc = std::min(enc, c0 + cpb) - c0;
-    const int slot = k & 1;
-    if (col_bytes) {
-      if (k >= 2) HIP_TRY(hipEventSynchronize(ev.e[slot]));  // its last upload has left it
-      {
-        prof::HostScope hs("cache_image_read");
-        std::atomic<bool> short_read{false};
-        parallel_for(nc, [&](size_t c) {
-          uint8_t *to = stg[slot].b() + c * col_bytes;
-          const size_t at = ((c0 + c) * row_capacity + r_lo) * POS_WB, want = R * POS_WB;
-          if (fd < 0) {
-            std::memcpy(to, porenc + at, want);
-            return;
-          }
-          for (size_t got = 0; got < want;) {
-            const ssize_t n = pread(fd, to + got, want - got, (off_t)(at + got));
-            if (n <= 0) {
-              if (n < 0 && errno == EINTR) continue;
-              short_read = true;
-              return;
-            }
-            got += (size_t)n;
-          }
-        });
-        if (short_read) {
-          (void)hipStreamSynchronize(s);  // the other slot's upload may still be reading its staging
-          return fail(LCPC_ERR_INVALID_ARG, "encoded file shorter than row_capacity * encoded_size elements");
-        }
-      }
-      prof::Scope ps("cache_h2d", s);
-      HIP_TRY(hipMemcpyAsync(dcols[slot].p, stg[slot].p, nc * col_bytes, hipMemcpyHostToDevice, s));
-      HIP_TRY(hipEventRecord(ev.e[slot], s));
-    }
-    HIP_TRY(leaf_chunk_cvs_slices(fid, dcols[slot].as<uint32_t>(), col_elems, n_rows, nc, c_lo, c_hi, dst + c0 * 8,
-                                  c_lo, enc, bad, s));
-  }
-  HIP_TRY(hipStreamSynchronize(s));
-  for (auto &b : dcols) b.settle();
-  return LCPC_OK;
-}
-
-lcpc_status cache_check_enc(size_t enc) {
-  if (enc < 2 || (enc & (enc - 1))) return fail(LCPC_ERR_INVALID_ARG, "encoded width must be a power of 2 (>= 2)");
-  return LCPC_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-lcpc_status lcpc_pos_update_chunk_range(size_t old_rows, size_t new_rows, size_t row_lo, size_t row_hi,
-                                        size_t *chunk_lo, size_t *chunk_hi) {
-  if (!chunk_lo || !chunk_hi) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  return pos_update_chunk_range(old_rows, new_rows, row_lo, row_hi, chunk_lo, chunk_hi);
-}
-
-size_t lcpc_pos_writer_n_chunks(const lcpc_pos_writer *w) {
-  return w && w->finalized ? w->chunks_done : 0;
-}
-
-lcpc_status lcpc_pos_writer_copy_cvs(const lcpc_pos_writer *w, uint8_t *out) {
-  if (!w || !out) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  if (!w->finalized) return fail(LCPC_ERR_INVALID_ARG, "writer not finalized");
-  std::memcpy(out, w->cvs.data(), w->cvs.size());
-  return LCPC_OK;
-}
-
-lcpc_status lcpc_pos_chunk_cache_from_porenc(const uint8_t *porenc, size_t enc, size_t rows_written,
-                                             size_t row_capacity, lcpc_pos_chunk_cache **out) {
-  lcpc_status st = cache_check_enc(enc);
-  if (st) return st;
-  if (!out || (!porenc && rows_written)) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  if (rows_written > row_capacity) return fail(LCPC_ERR_INVALID_ARG, "rows_written > row_capacity");
-  Device *dev = current_device(&st);
-  if (!dev) return st;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  hipStream_t s = lease.s;
-  auto c = std::make_unique<lcpc_pos_chunk_cache>();
-  c->dev = dev;
-  c->enc = enc;
-  c->rows = rows_written;
-  c->n_chunks = c->cap_chunks = leaf_n_chunks(POS_FID, rows_written);
-  HIP_TRY(c->cvs.alloc(dev, c->cap_chunks * enc * 32));
-  DBuf dbad;
-  HIP_TRY(dbad.alloc(dev, 4));
-  HIP_TRY(hipMemsetAsync(dbad.p, 0, 4, s));
-  if ((st = cache_hash_chunks(dev, s, porenc, -1, enc, row_capacity, rows_written, 0, c->n_chunks, c->cvs.as<uint32_t>(),
-                              dbad.as<uint32_t>())))
-    return st;
-  uint32_t bad = 0;
-  HIP_TRY(hipMemcpyAsync(&bad, dbad.p, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  c->cvs.settle();
-  if (bad) return fail(LCPC_ERR_INVALID_ARG, "encoded file holds a non-canonical element (from_repr fails)");
-  *out = c.release();
-  return LCPC_OK;
-}
-
-lcpc_status lcpc_pos_chunk_cache_from_cvs(const uint8_t *cvs, size_t enc, size_t rows_written,
-                                          lcpc_pos_chunk_cache **out) {
-  lcpc_status st = cache_check_enc(enc);
-  if (st) return st;
-  if (!out || !cvs) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  Device *dev = current_device(&st);
-  if (!dev) return st;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  auto c = std::make_unique<lcpc_pos_chunk_cache>();
-  c->dev = dev;
-  c->enc = enc;
-  c->rows = rows_written;
-  c->n_chunks = c->cap_chunks = leaf_n_chunks(POS_FID, rows_written);
-  if ((st = upload(dev, c->cvs, cvs, c->n_chunks * enc * 32))) return st;
-  HIP_TRY(hipStreamSynchronize(lease.s));
-  c->cvs.settle();
-  *out = c.release();
-  return LCPC_OK;
-}
-
-void lcpc_pos_chunk_cache_free(lcpc_pos_chunk_cache *c) { delete c; }
-size_t lcpc_pos_chunk_cache_enc(const lcpc_pos_chunk_cache *c) { return c ? c->enc : 0; }
-size_t lcpc_pos_chunk_cache_rows(const lcpc_pos_chunk_cache *c) { return c ? c->rows : 0; }
-size_t lcpc_pos_chunk_cache_n_chunks(const lcpc_pos_chunk_cache *c) { return c ? c->n_chunks : 0; }
-
-lcpc_status lcpc_pos_chunk_cache_copy_cvs(const lcpc_pos_chunk_cache *c, size_t chunk_lo, size_t chunk_hi,
-                                          uint8_t *out) {
-  if (!c) return fail(LCPC_ERR_INVALID_ARG, "null cache");
-  if (chunk_lo > chunk_hi || chunk_hi > c->n_chunks) return fail(LCPC_ERR_INVALID_ARG, "chunk range");
-  if (chunk_lo == chunk_hi) return LCPC_OK;
-  if (!out) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  Lease lease(c->dev);
-  HIP_TRY(hipSetDevice(c->dev->id));
-  HIP_TRY(hipMemcpyAsync(out, c->cvs.as<uint8_t>() + chunk_lo * c->enc * 32, (chunk_hi - chunk_lo) * c->enc * 32,
-                         hipMemcpyDeviceToHost, lease.s));
-  HIP_TRY(hipStreamSynchronize(lease.s));
-  return LCPC_OK;
-}
-
-static lcpc_status chunk_cache_update(lcpc_pos_chunk_cache *c, const uint8_t *porenc, int fd, size_t row_capacity,
-                                      size_t row_lo, size_t row_hi, size_t new_rows_written, size_t *chunk_lo,
-                                      size_t *chunk_hi) {
-  if (!c) return fail(LCPC_ERR_INVALID_ARG, "null cache");
-  size_t c_lo = 0, c_hi = 0;
-  lcpc_status st = pos_update_chunk_range(c->rows, new_rows_written, row_lo, row_hi, &c_lo, &c_hi);
-  if (st) return st;
-  if (new_rows_written > row_capacity) return fail(LCPC_ERR_INVALID_ARG, "rows_written > row_capacity");
-  if (!porenc && fd < 0 && new_rows_written) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  if (chunk_lo) *chunk_lo = c_lo;
-  if (chunk_hi) *chunk_hi = c_hi;
-  if (c_lo == c_hi) return LCPC_OK;
-  Device *dev = c->dev;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  hipStream_t s = lease.s;
-  const size_t enc = c->enc, new_chunks = leaf_n_chunks(POS_FID, new_rows_written);
-  // rehash into a side buffer: the cache is touched only once every element has passed the check
-  DBuf fresh, dbad;
-  HIP_TRY(fresh.alloc(dev, (c_hi - c_lo) * enc * 32));
-  HIP_TRY(dbad.alloc(dev, 4));
-  HIP_TRY(hipMemsetAsync(dbad.p, 0, 4, s));
-  if ((st = cache_hash_chunks(dev, s, porenc, fd, enc, row_capacity, new_rows_written, c_lo, c_hi, fresh.as<uint32_t>(),
-                              dbad.as<uint32_t>())))
-    return st;
-  uint32_t bad = 0;
-  HIP_TRY(hipMemcpyAsync(&bad, dbad.p, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (bad) return fail(LCPC_ERR_INVALID_ARG, "encoded file holds a non-canonical element (from_repr fails)");
-  if (new_chunks > c->cap_chunks) {  // grow by whole chunk rows (doubling, so appends stay amortised)
-    const size_t cap = std::max(new_chunks, 2 * c->cap_chunks);
-    DBuf bigger;
-    HIP_TRY(bigger.alloc(dev, cap * enc * 32));
-    HIP_TRY(hipMemcpyAsync(bigger.p, c->cvs.p, c->n_chunks * enc * 32, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    bigger.settle();
-    c->cvs = std::move(bigger);
-    c->cap_chunks = cap;
-  }
-  HIP_TRY(hipMemcpyAsync(c->cvs.as<uint8_t>() + c_lo * enc * 32, fresh.p, (c_hi - c_lo) * enc * 32,
-                         hipMemcpyDeviceToDevice, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  c->rows = new_rows_written;
-  c->n_chunks = new_chunks;
-  return LCPC_OK;
-}
-
-lcpc_status lcpc_pos_chunk_cache_update(lcpc_pos_chunk_cache *c, const uint8_t *porenc, size_t row_capacity,
-                                        size_t row_lo, size_t row_hi, size_t new_rows_written, size_t *chunk_lo,
-                                        size_t *chunk_hi) {
-  return chunk_cache_update(c, porenc, -1, row_capacity, row_lo, row_hi, new_rows_written, chunk_lo, chunk_hi);
-}
-
-lcpc_status lcpc_pos_chunk_cache_update_fd(lcpc_pos_chunk_cache *c, int fd, size_t row_capacity, size_t row_lo,
-                                           size_t row_hi, size_t new_rows_written, size_t *chunk_lo,
-                                           size_t *chunk_hi) {
-  if (fd < 0) return fail(LCPC_ERR_INVALID_ARG, "file descriptor");
-  return chunk_cache_update(c, nullptr, fd, row_capacity, row_lo, row_hi, new_rows_written, chunk_lo, chunk_hi);
-}
-
-lcpc_status lcpc_pos_chunk_cache_tree(const lcpc_pos_chunk_cache *c, uint8_t *digests, uint8_t *tree) {
-  if (!c) return fail(LCPC_ERR_INVALID_ARG, "null cache");
-  Device *dev = c->dev;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  hipStream_t s = lease.s;
-  const size_t enc = c->enc;
-  DBuf hashes;
-  HIP_TRY(hashes.alloc(dev, (2 * enc - 1) * 32));
-  HIP_TRY(leaves_fold_cvs(c->cvs.as<uint32_t>(), enc, c->n_chunks, hashes.as<uint8_t>(), s));
-  if (tree) {
-    HIP_TRY(merkle_tree(hashes.as<uint8_t>(), enc, s));
-    HIP_TRY(hipMemcpyAsync(tree, hashes.p, (2 * enc - 1) * 32, hipMemcpyDeviceToHost, s));
-  }
-  if (digests) HIP_TRY(hipMemcpyAsync(digests, hashes.p, enc * 32, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return LCPC_OK;
-}
-
-lcpc_status lcpc_leaves_fold_cvs(const uint8_t *cvs, size_t n_chunks, size_t n_cols, uint8_t *leaves,
-                                 uint8_t *cvs_after) {
-  if ((!cvs || !leaves) && n_cols) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  if (n_chunks == 0) return fail(LCPC_ERR_INVALID_ARG, "n_chunks");
-  if (!n_cols) return LCPC_OK;
-  lcpc_status st;
-  Device *dev = current_device(&st);
-  if (!dev) return st;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  DBuf dc, dl;
-  if ((st = upload(dev, dc, cvs, n_chunks * n_cols * 32))) return st;
-  HIP_TRY(dl.alloc(dev, n_cols * 32));
-  HIP_TRY(leaves_fold_cvs(dc.as<uint32_t>(), n_cols, n_chunks, dl.as<uint8_t>(), lease.s));
-  HIP_TRY(hipMemcpyAsync(leaves, dl.p, n_cols * 32, hipMemcpyDeviceToHost, lease.s));
-  if (cvs_after) HIP_TRY(hipMemcpyAsync(cvs_after, dc.p, n_chunks * n_cols * 32, hipMemcpyDeviceToHost, lease.s));
-  HIP_TRY(hipStreamSynchronize(lease.s));
-  return LCPC_OK;
-}
-
-}  // extern "C"
-
-// ColumnDigestAccumulator<Blake3, F> with ColumnsToCareAbout::All (column_digest_accumulator.rs:
-// 17-118): encoded rows pushed one batch at a time; every column's message is the 32 zero bytes
-// then the repr of its elements, hashed in 1-KiB BLAKE3 chunks on the GPU as soon as a chunk is
-// complete and the message is known to continue past it (so no chunk is hashed as the only one).
-struct lcpc_column_digests {
-  Device *dev = nullptr;
-  int fid = 0;
-  size_t width = 0, chunks_done = 0, rows_in = 0, batch_rows = 0;
-  std::vector<uint64_t> pend;  // rows from leaf_chunk_first_row(chunks_done) on
-  std::vector<uint8_t> cvs;    // [chunk][column] chaining values of the chunks done
-  bool finalized = false;
-};
-
-namespace {
-
-constexpr size_t ACC_BATCH_BYTES = (size_t)256 << 20;  // default rows per GPU pass: about this much input
-
-// hash chunks [a->chunks_done, c_end) of messages n_rows_cv rows long (exact, or any count past
-// the covered rows while the message continues) from the pending rows
-lcpc_status acc_run(lcpc_column_digests *a, size_t c_end, size_t n_rows_cv) {
-  if (c_end <= a->chunks_done) return LCPC_OK;
-  const int fid = a->fid;
-  const size_t nl = (size_t)field_bytes(fid) / 8, w = a->width;
-  const size_t r0 = lcpc_leaf_chunk_first_row((lcpc_field)fid, a->chunks_done);
-  const size_t r1 = std::min(a->rows_in, lcpc_leaf_chunk_first_row((lcpc_field)fid, c_end));
-  Lease lease(a->dev);
-  HIP_TRY(hipSetDevice(a->dev->id));
-  DBuf drows, dcv;
-  lcpc_status st;
-  if ((st = upload(a->dev, drows, a->pend.data(), (r1 - r0) * w * nl * 8))) return st;
-  HIP_TRY(dcv.alloc(a->dev, (c_end - a->chunks_done) * w * 32));
-  HIP_TRY(leaf_chunk_cvs(fid, drows.as<uint32_t>(), r0, n_rows_cv, w, w, a->chunks_done, c_end,
-                         dcv.as<uint32_t>(), lease.s));
-  const size_t off = a->cvs.size();
-  a->cvs.resize(off + (c_end - a->chunks_done) * w * 32);
-  HIP_TRY(hipMemcpyAsync(a->cvs.data() + off, dcv.p, (c_end - a->chunks_done) * w * 32, hipMemcpyDeviceToHost,
-                         lease.s));
-  HIP_TRY(hipStreamSynchronize(lease.s));
-  a->pend.erase(a->pend.begin(), a->pend.begin() + (r1 - r0) * w * nl);
-  a->chunks_done = c_end;
-  return LCPC_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-lcpc_status lcpc_column_digests_new(lcpc_field f, size_t width, size_t batch_rows, lcpc_column_digests **out) {
-  if (!out) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  if (!valid_field(f) || !field_gpu_supported(f)) return fail(LCPC_ERR_UNSUPPORTED, "field");
-  if (992 % field_bytes(f)) return fail(LCPC_ERR_UNSUPPORTED, "elements that straddle BLAKE3 chunks (Ft191)");
-  if (!width) return fail(LCPC_ERR_INVALID_ARG, "width must be > 0");
-  lcpc_status st;
-  Device *dev = current_device(&st);
-  if (!dev) return st;
-  auto a = std::make_unique<lcpc_column_digests>();
-  a->dev = dev;
-  a->fid = f;
-  a->width = width;
-  a->batch_rows = batch_rows ? batch_rows : std::max<size_t>(1, ACC_BATCH_BYTES / (width * field_bytes(f)));
-  *out = a.release();
-  return LCPC_OK;
-}
-
-void lcpc_column_digests_free(lcpc_column_digests *a) { delete a; }
-
-size_t lcpc_column_digests_width(const lcpc_column_digests *a) { return a ? a->width : 0; }
-
-lcpc_status lcpc_column_digests_update(lcpc_column_digests *a, const uint64_t *rows, size_t n_rows) {
-  // update (:62-87), for n_rows encoded rows of `width` elements at once
-  if (!a || (!rows && n_rows)) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  if (a->finalized) return fail(LCPC_ERR_INVALID_ARG, "accumulator already finalized");
-  const size_t nl = (size_t)field_bytes(a->fid) / 8, w = a->width;
-  a->pend.insert(a->pend.end(), rows, rows + n_rows * w * nl);
-  a->rows_in += n_rows;
-  // chunks that end at or before the last row but one: complete, and not their column's last
-  size_t c_end = a->chunks_done;
-  while (lcpc_leaf_chunk_first_row((lcpc_field)a->fid, c_end + 1) < a->rows_in) c_end++;
-  const size_t r0 = lcpc_leaf_chunk_first_row((lcpc_field)a->fid, a->chunks_done);
-  if (lcpc_leaf_chunk_first_row((lcpc_field)a->fid, c_end) - r0 < a->batch_rows) return LCPC_OK;  // keep buffering
-  return acc_run(a, c_end, a->rows_in);
-}
-
-lcpc_status lcpc_column_digests_finalize(lcpc_column_digests *a, uint8_t *digests, uint8_t *tree) {
-  // get_column_digests (:89-96) into digests (width x 32 B), and / or finalize_to_merkle_tree
-  // (:109-118) into tree (MerkleTree::to_bytes: 2 width - 1 digests, root last; width a power
-  // of two >= 2, MerkleTree::new's requirement); either may be NULL
-  if (!a) return fail(LCPC_ERR_INVALID_ARG, "null accumulator");
-  if (a->finalized) return fail(LCPC_ERR_INVALID_ARG, "accumulator already finalized");
-  const size_t w = a->width;
-  if (tree && (w < 2 || (w & (w - 1)))) return fail(LCPC_ERR_INVALID_ARG, "Input needs to be a power of two, at least two.");
-  // With no rows pushed every column's message is the 32-byte zero prefix alone: one chunk of one
-  // 32-byte block with ROOT, so each digest is BLAKE3(32 zero bytes), as the reference's untouched
-  // hashers give.  acc_run covers it: its upload of zero rows is an allocation only and the chunk
-  // kernel loads no element of a zero-row message.
-  const size_t n_chunks = leaf_n_chunks(a->fid, a->rows_in);
-  lcpc_status st = acc_run(a, n_chunks, a->rows_in);
-  if (st) return st;
-  a->finalized = true;
-  Lease lease(a->dev);
-  HIP_TRY(hipSetDevice(a->dev->id));
-  DBuf dc, hashes;
-  if ((st = upload(a->dev, dc, a->cvs.data(), a->cvs.size()))) return st;
-  HIP_TRY(hashes.alloc(a->dev, (2 * w - 1) * 32));
-  HIP_TRY(leaves_from_cvs(dc.as<uint32_t>(), w, (int)n_chunks, hashes.as<uint8_t>(), lease.s));
-  if (tree) {
-    HIP_TRY(merkle_tree(hashes.as<uint8_t>(), w, lease.s));
-    HIP_TRY(hipMemcpyAsync(tree, hashes.p, (2 * w - 1) * 32, hipMemcpyDeviceToHost, lease.s));
-  }
-  if (digests) HIP_TRY(hipMemcpyAsync(digests, hashes.p, w * 32, hipMemcpyDeviceToHost, lease.s));
-  HIP_TRY(hipStreamSynchronize(lease.s));
-  return LCPC_OK;
-}
-
-}  // extern "C"
-
-// ================================================================= R-S erasure decoding, scrub, repair
-// No counterpart in the reference (its decode_row is a plain ifft_oi and verify_all_files_agree can
-// only say "trees differ"): the redundancy of the rate <= 1/2 code is used to locate damaged columns
-// of a stored file against its Merkle leaves and to recompute them.  Kernels: erasure.hip.
-namespace {
-
-// a * b R^-1 mod p on 32-bit words (CIOS), host side: only lcpc_rs_domain_points needs it
-template <class F>
-void host_mont_mul(const uint32_t *a, const uint32_t *b, uint32_t *out) {
-  constexpr int N = F::N;
-  uint32_t t[N + 2] = {0};
-  for (int i = 0; i < N; i++) {
-    uint64_t c = 0;
-    for (int j = 0; j < N; j++) {
-      const uint64_t x = (uint64_t)a[j] * b[i] + t[j] + c;
-      t[j] = (uint32_t)x;
-      c = x >> 32;
-    }
-    uint64_t x = (uint64_t)t[N] + c;
-    t[N] = (uint32_t)x;
-    t[N + 1] = (uint32_t)(x >> 32);
-    const uint32_t m = t[0] * F::NP;
-    x = (uint64_t)m * F::P[0] + t[0];
-    c = x >> 32;
-    for (int j = 1; j < N; j++) {
-      x = (uint64_t)m * F::P[j] + t[j] + c;
-      t[j - 1] = (uint32_t)x;
-      c = x >> 32;
-    }
-    x = (uint64_t)t[N] + c;
-    t[N - 1] = (uint32_t)x;
-    t[N] = t[N + 1] + (uint32_t)(x >> 32);
-  }
-  bool ge = t[N] != 0;
-  if (!ge) {
-    ge = true;  // t == p also subtracts
-    for (int i = N - 1; i >= 0; i--)
-      if (t[i] != F::P[i]) {
-        ge = t[i] > F::P[i];
-        break;
-      }
-  }
-  if (ge) {
-    uint64_t br = 0;
-    for (int i = 0; i < N; i++) {
-      const uint64_t d = (uint64_t)t[i] - F::P[i] - br;
-      t[i] = (uint32_t)d;
-      br = (d >> 32) & 1;
-    }
-  }
-  for (int i = 0; i < N; i++) out[i] = t[i];
-}
-
-inline size_t bitrev_host(size_t i, int log_n) {
-  size_t r = 0;
-  for (int b = 0; b < log_n; b++) r |= ((i >> b) & 1) << (log_n - 1 - b);
-  return r;
-}
-
-// the erasure set as the kernels take it; the argument rules of lcpc_rs_erasure_decode_rows
-lcpc_status erasure_check(size_t len, size_t n_per_row, const uint64_t *erased, size_t n_erased,
-                          std::vector<uint32_t> &e32) {
-  if (n_per_row < 1 || n_per_row >= len) return fail(LCPC_ERR_INVALID_ARG, "n_per_row outside [1, len)");
-  if (!erased && n_erased) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  if (len > ((size_t)1 << 24)) return fail(LCPC_ERR_UNSUPPORTED, "length beyond the NTT range");
-  std::vector<bool> seen(len, false);
-  e32.resize(n_erased);
-  for (size_t i = 0; i < n_erased; i++) {
-    if (erased[i] >= len) return fail(LCPC_ERR_INVALID_ARG, "erased index out of range");
-    if (seen[erased[i]]) return fail(LCPC_ERR_INVALID_ARG, "duplicate erased index");
-    seen[erased[i]] = true;
-    e32[i] = (uint32_t)erased[i];
-  }
-  if (n_erased > len - n_per_row)
-    return fail(LCPC_ERR_UNRECOVERABLE, "more erasures than the code's redundancy (len - n_per_row)");
-  return LCPC_OK;
-}
-
-// Per-call device state of an erasure decode: both plans, the locator's tables, the check flag.
-struct ErasureCtx {
-  int fid = 0, log_n = 0;
-  size_t n = 0, n_erased = 0, deg_bound = 0;
-  hipStream_t s = nullptr;
-  NttPlan fwd, inv;
-  DBuf erased, slot, lambda, dinv, dscale, flag;
-  ~ErasureCtx() {
-    if (s) (void)hipStreamSynchronize(s);
-    ntt_plan_free(fwd);
-    ntt_plan_free(inv);
-  }
-};
-
-lcpc_status erasure_ctx_init(ErasureCtx &c, Device *dev, hipStream_t s, int fid, size_t len, size_t n_per_row,
-                             const std::vector<uint32_t> &e32) {
-  c.fid = fid;
-  c.log_n = (int)log2_np2(len);
-  c.n = len;
-  c.n_erased = e32.size();
-  c.deg_bound = n_per_row + e32.size();
-  c.s = s;
-  const int wb = field_bytes(fid);
-  for (bool inverse : {false, true}) {
-    const hipError_t he = ntt_plan_init(inverse ? c.inv : c.fwd, fid, c.log_n, inverse, s);
-    if (he == hipErrorInvalidValue) return fail(LCPC_ERR_UNSUPPORTED, "length beyond the NTT range");
-    HIP_TRY(he);
-  }
-  HIP_TRY(c.erased.alloc(dev, e32.size() * 4));
-  HIP_TRY(c.slot.alloc(dev, len * 4));
-  HIP_TRY(c.lambda.alloc(dev, len * wb));
-  HIP_TRY(c.dinv.alloc(dev, e32.size() * wb));
-  HIP_TRY(c.dscale.alloc(dev, len * wb));
-  HIP_TRY(c.flag.alloc(dev, 8));
-  HIP_TRY(hipMemsetAsync(c.flag.p, 0, 8, s));
-  if (!e32.empty()) HIP_TRY(hipMemcpyAsync(c.erased.p, e32.data(), e32.size() * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(erasure_locator(fid, c.fwd.d_tw, c.log_n, c.erased.as<uint32_t>(), c.n_erased, c.slot.as<int32_t>(),
-                          c.lambda.as<uint32_t>(), c.dinv.as<uint32_t>(), s));
-  uint32_t inv[8] = {0};
-  inv_pow2_canon(fid, c.log_n, inv);
-  HIP_TRY(erasure_dscale(fid, c.log_n, inv, c.dscale.as<uint32_t>(), s));
-  // (e32 is pageable host memory: the copy above has left it once the stream drains)
-  HIP_TRY(hipStreamSynchronize(s));
-  return LCPC_OK;
-}
-
-// g: B masked rows in the inverse plan's input order (clobbered).  On return h holds P'(x_c) in
-// codeword order (not computed when nothing is erased) and the flag has the degree check's verdict.
-lcpc_status erasure_core(ErasureCtx &c, uint32_t *g, uint32_t *h, size_t B) {
-  HIP_TRY(ntt_rows(c.inv, g, c.n, c.n, h, c.n, B, c.s));
-  HIP_TRY(erasure_deriv(c.fid, h, g, c.log_n, B, c.dscale.as<uint32_t>(), c.deg_bound, c.flag.as<uint32_t>(), c.s));
-  if (c.n_erased) HIP_TRY(ntt_rows(c.fwd, g, c.n, c.n, h, c.n, B, c.s));
-  return LCPC_OK;
-}
-
-// The values of the erased positions e32 of every row (filled[r][j], Montgomery), rows untouched;
-// LCPC_ERR_UNRECOVERABLE if a row fails the degree check.
-lcpc_status erasure_decode_values(Device *dev, hipStream_t s, int f, const uint64_t *rows, size_t n_rows, size_t len,
-                                  size_t n_per_row, const std::vector<uint32_t> &e32, std::vector<uint64_t> &filled) {
-  lcpc_status st;
-  const size_t n_erased = e32.size();
-  const size_t wb = (size_t)field_bytes(f), nl = wb / 8;
-  ErasureCtx c;
-  if ((st = erasure_ctx_init(c, dev, s, f, len, n_per_row, e32))) return st;
-  // 16 MiB of row elements per batch (2^21 Ft63 elements still fill the device): 64 rows at the
-  // stored files' 2^15-point shape
-  const size_t bmax = std::max<size_t>(1, std::min(n_rows, ((size_t)16 << 20) / (len * wb)));
-  DBuf a, g, h, vals;
-  HIP_TRY(a.alloc(dev, bmax * len * wb));
-  HIP_TRY(g.alloc(dev, bmax * len * wb));
-  HIP_TRY(h.alloc(dev, bmax * len * wb));
-  HIP_TRY(vals.alloc(dev, bmax * n_erased * wb));
-  filled.assign(n_rows * n_erased * nl, 0);
-  for (size_t r0 = 0; r0 < n_rows; r0 += bmax) {
-    const size_t B = std::min(bmax, n_rows - r0);
-    HIP_TRY(hipMemcpyAsync(a.p, rows + r0 * len * nl, B * len * wb, hipMemcpyHostToDevice, s));
-    HIP_TRY(erasure_masked_rows(f, a.as<uint32_t>(), g.as<uint32_t>(), c.log_n, B, c.slot.as<int32_t>(),
-                                c.lambda.as<uint32_t>(), s));
-    if ((st = erasure_core(c, g.as<uint32_t>(), h.as<uint32_t>(), B))) return st;
-    if (n_erased) {
-      HIP_TRY(erasure_fill(f, h.as<uint32_t>(), c.log_n, B, c.erased.as<uint32_t>(), n_erased, c.dinv.as<uint32_t>(),
-                           vals.as<uint32_t>(), nullptr, nullptr, false, s));
-      HIP_TRY(hipMemcpyAsync(filled.data() + r0 * n_erased * nl, vals.p, B * n_erased * wb, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-  }
-  uint32_t flag = 0;
-  HIP_TRY(hipMemcpyAsync(&flag, c.flag.p, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (flag)
-    return fail(LCPC_ERR_UNRECOVERABLE, "a row is not a codeword on its surviving positions (degree check failed)");
-  return LCPC_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-lcpc_status lcpc_rs_domain_points(lcpc_field f, size_t len, uint64_t *out) {
-  if (!valid_field(f) || !out) return fail(LCPC_ERR_INVALID_ARG, "arguments");
-  lcpc_status st = check_fft_len(f, len);
-  if (st) return st;
-  const int log_n = (int)log2_np2(len);
-  dispatch_field(f, [&]<class F>() {
-    constexpr int N = F::N;
-    // the forward transform's root (ntt_plan_init): ROOT_OF_UNITY^(2^(S - log_n)), or its inverse
-    uint32_t w[N], x[N];
-    for (int i = 0; i < N; i++) w[i] = LCPC_FFT_OMEGA_INVERSE ? F::ROOT_INV[i] : F::ROOT[i];
-    for (int k = 0; k < F::S - log_n; k++) host_mont_mul<F>(w, w, w);
-    for (int i = 0; i < N; i++) x[i] = F::ONE[i];
-    uint32_t *o = reinterpret_cast<uint32_t *>(out);
-    for (size_t e = 0; e < len; e++) {  // x = w^e is the point of position bitrev(e) (or e)
-      const size_t c = LCPC_FFT_OUTPUT_BITREV ? bitrev_host(e, log_n) : e;
-      std::memcpy(o + c * N, x, sizeof(x));
-      host_mont_mul<F>(x, w, x);
-    }
-    return 0;
-  });
-  return LCPC_OK;
-}
-
-lcpc_status lcpc_rs_erasure_decode_rows(lcpc_field f, uint64_t *rows, size_t n_rows, size_t len, size_t n_per_row,
-                                        const uint64_t *erased, size_t n_erased) {
-  if (!valid_field(f) || (!rows && n_rows)) return fail(LCPC_ERR_INVALID_ARG, "arguments");
-  if (!field_gpu_supported(f)) return fail(LCPC_ERR_UNSUPPORTED, "field has no gfx950 kernels");
-  lcpc_status st = check_fft_len(f, len);
-  if (st) return st;
-  std::vector<uint32_t> e32;
-  if ((st = erasure_check(len, n_per_row, erased, n_erased, e32))) return st;
-  if (n_rows == 0) return LCPC_OK;
-  Device *dev = current_device(&st);
-  if (!dev) return st;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  const size_t wb = (size_t)field_bytes(f), nl = wb / 8;
-  // the recovered values of every row stay here until the degree check has passed for all rows
-  std::vector<uint64_t> filled;
-  if ((st = erasure_decode_values(dev, lease.s, f, rows, n_rows, len, n_per_row, e32, filled))) return st;
-  // only the erased positions are written: every other limb keeps its bits
-  for (size_t r = 0; r < n_rows; r++)
-    for (size_t j = 0; j < n_erased; j++)
-      std::memcpy(rows + (r * len + e32[j]) * nl, filled.data() + (r * n_erased + j) * nl, wb);
-  return LCPC_OK;
-}
-
-lcpc_status lcpc_pos_scrub_porenc(const uint8_t *porenc, size_t enc, size_t rows_written, size_t row_capacity,
-                                  const uint8_t *leaves, uint8_t *digests, uint8_t *status, size_t *n_bad) {
-  if (enc < 2 || (enc & (enc - 1))) return fail(LCPC_ERR_INVALID_ARG, "encoded width must be a power of 2 (>= 2)");
-  if (!leaves || !status || (!porenc && rows_written)) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  if (rows_written > row_capacity) return fail(LCPC_ERR_INVALID_ARG, "rows_written > row_capacity");
-  lcpc_status st;
-  Device *dev = current_device(&st);
-  if (!dev) return st;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  hipStream_t s = lease.s;
-  const int fid = POS_FID;
-  const size_t col_bytes = rows_written * POS_WB;
-  const size_t cpb = col_bytes ? std::max<size_t>(1, std::min(enc, POS_STAGE_BYTES / col_bytes)) : enc;
-  DBuf hashes, dleaves, dcols[2], scratch[2], dbad, dstatus;
-  HIP_TRY(hashes.alloc(dev, enc * 32));
-  HIP_TRY(dleaves.alloc(dev, enc * 32));
-  HIP_TRY(dbad.alloc(dev, enc * 4));
-  HIP_TRY(dstatus.alloc(dev, enc));
-  for (int i = 0; i < 2; i++) {
-    HIP_TRY(dcols[i].alloc(dev, cpb * col_bytes));
-    HIP_TRY(scratch[i].alloc(dev, leaf_hash_scratch_bytes(fid, rows_written, cpb)));
-  }
-  HIP_TRY(hipMemsetAsync(dbad.p, 0, enc * 4, s));
-  HIP_TRY(hipMemcpyAsync(dleaves.p, leaves, enc * 32, hipMemcpyHostToDevice, s));
-  Pinned stg[2];
-  Events ev;
-  HIP_TRY(ev.init());
-  if (col_bytes)
-    for (auto &x : stg)
-      if (!x.get(dev, cpb * col_bytes)) return fail(LCPC_ERR_OUT_OF_MEMORY, "pinned host staging");
-  int k = 0;
-  for (size_t c0 = 0; c0 < enc; c0 += cpb, k++) {
-    const size_t nc = std::min(enc, c0 + cpb) - c0;
-    const int slot = k & 1;
-    if (col_bytes) {
-      if (k >= 2) HIP_TRY(hipEventSynchronize(ev.e[slot]));  // its last upload has left it
-      parallel_for(nc, [&](size_t c) {
-        std::memcpy(stg[slot].b() + c * col_bytes, porenc + (c0 + c) * row_capacity * POS_WB, col_bytes);
-      });
-      HIP_TRY(hipMemcpyAsync(dcols[slot].p, stg[slot].p, nc * col_bytes, hipMemcpyHostToDevice, s));
-      HIP_TRY(hipEventRecord(ev.e[slot], s));
-      // a non-canonical element is a finding of its column, not an error of the call
-      HIP_TRY(scrub_col_canon(fid, dcols[slot].as<uint32_t>(), rows_written, nc, dbad.as<uint32_t>() + c0, s));
-    }
-    // the leaves hash canonical bytes: the slice is hashed as it is, without a conversion round trip
-    HIP_TRY(leaf_hashes_cols(fid, dcols[slot].as<uint32_t>(), rows_written, nc, hashes.as<uint8_t>() + c0 * 32,
-                             scratch[slot].p, s, true));
-  }
-  HIP_TRY(scrub_status(hashes.as<uint8_t>(), dleaves.as<uint8_t>(), dbad.as<uint32_t>(), enc, dstatus.as<uint8_t>(), s));
-  HIP_TRY(hipMemcpyAsync(status, dstatus.p, enc, hipMemcpyDeviceToHost, s));
-  if (digests) HIP_TRY(hipMemcpyAsync(digests, hashes.p, enc * 32, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (n_bad) {
-    size_t n = 0;
-    for (size_t c = 0; c < enc; c++) n += status[c] != 0;
-    *n_bad = n;
-  }
-  return LCPC_OK;
-}
-
-lcpc_status lcpc_pos_repair_columns(const uint8_t *porenc, size_t pre, size_t enc, size_t rows_written,
-                                    size_t row_capacity, const uint64_t *bad_cols, size_t n_bad, uint8_t *cols_out,
-                                    uint8_t *digests_out, uint8_t *data_out) {
-  lcpc_status st = pos_dims_check(pre, enc);
-  if (st) return st;
-  if (rows_written > row_capacity) return fail(LCPC_ERR_INVALID_ARG, "rows_written > row_capacity");
-  if (!porenc && rows_written) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  std::vector<uint32_t> e32;
-  if ((st = erasure_check(enc, pre, bad_cols, n_bad, e32))) return st;
-  Device *dev = current_device(&st);
-  if (!dev) return st;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  hipStream_t s = lease.s;
-  const int fid = POS_FID;
-  const size_t rows = rows_written;
-  ErasureCtx c;
-  if ((st = erasure_ctx_init(c, dev, s, fid, enc, pre, e32))) return st;
-  std::vector<uint8_t> is_bad(enc, 0);
-  for (uint32_t j : e32) is_bad[j] = 1;
-  // batches of whole BLAKE3 chunks of the column messages, as the writer's
-  const size_t rows_per_chunk = 1024 / POS_WB;
-  const size_t n_chunks = leaf_n_chunks(fid, rows);
-  // LCPC_POS_REPAIR_BATCH_ROWS: rows per batch instead of a staging buffer's worth (tests of the
-  // batch seams on small files, A/B runs); rounded down to whole chunks, at least one
-  size_t want_rows = std::max<size_t>(rows_per_chunk, POS_STAGE_BYTES / (enc * POS_WB));
-  if (const char *env = std::getenv("LCPC_POS_REPAIR_BATCH_ROWS")) {
-    const unsigned long long v = std::strtoull(env, nullptr, 10);
-    if (v) want_rows = std::min<size_t>(want_rows, (size_t)v);
-  }
-  const size_t cpb = std::max<size_t>(1, want_rows / rows_per_chunk);
-  const size_t bmax = std::max<size_t>(1, std::min(rows, cpb * rows_per_chunk));
-  const bool want_vals = n_bad && (cols_out || digests_out);
-  DBuf src, a, g, h, vals, cm, dcv, dbytes, dbad;
-  HIP_TRY(src.alloc(dev, bmax * enc * POS_WB));
-  HIP_TRY(g.alloc(dev, bmax * enc * POS_WB));
-  HIP_TRY(h.alloc(dev, bmax * enc * POS_WB));
-  if (data_out) {
-    HIP_TRY(a.alloc(dev, bmax * enc * POS_WB));
-    HIP_TRY(dbytes.alloc(dev, bmax * pre * POS_DB + 64));
-  }
-  HIP_TRY(vals.alloc(dev, bmax * n_bad * POS_WB));
-  HIP_TRY(cm.alloc(dev, bmax * n_bad * POS_WB));
-  HIP_TRY(dcv.alloc(dev, n_chunks * n_bad * 32));
-  HIP_TRY(dbad.alloc(dev, 8));
-  HIP_TRY(hipMemsetAsync(dbad.p, 0, 8, s));
-  Pinned stg[2], ocols, odata;
-  for (auto &x : stg)
-    if (!x.get(dev, bmax * enc * POS_WB)) return fail(LCPC_ERR_OUT_OF_MEMORY, "pinned host staging");
-  if (cols_out && n_bad && !ocols.get(dev, bmax * n_bad * POS_WB)) return fail(LCPC_ERR_OUT_OF_MEMORY, "pinned host staging");
-  if (data_out && !odata.get(dev, bmax * pre * POS_DB)) return fail(LCPC_ERR_OUT_OF_MEMORY, "pinned host staging");
-  uint32_t inv[8] = {0};
-  inv_pow2_canon(fid, c.log_n, inv);
-  auto batch_rows = [&](size_t c_lo, size_t *r0, size_t *B, size_t *c_hi) {
-    *c_hi = std::min(n_chunks, c_lo + cpb);
-    *r0 = std::min(rows, lcpc_leaf_chunk_first_row((lcpc_field)fid, c_lo));
-    const size_t r1 = *c_hi == n_chunks ? rows : std::min(rows, lcpc_leaf_chunk_first_row((lcpc_field)fid, *c_hi));
-    *B = r1 - *r0;
-  };
-  // the damaged columns are never read, neither here nor by the kernels
-  auto stage = [&](int slot, size_t r0, size_t B) {
-    if (!B) return;
-    parallel_for(enc, [&](size_t col) {
-      if (!is_bad[col])
-        std::memcpy(stg[slot].b() + col * B * POS_WB, porenc + (col * row_capacity + r0) * POS_WB, B * POS_WB);
-    });
-  };
-  size_t r0 = 0, B = 0, c_hi = 0;
-  batch_rows(0, &r0, &B, &c_hi);
-  stage(0, r0, B);
-  int k = 0;
-  for (size_t c_lo = 0; c_lo < n_chunks; c_lo = c_hi, k++) {
-    batch_rows(c_lo, &r0, &B, &c_hi);
-    const int slot = k & 1;
-    if (B) {
-      HIP_TRY(hipMemcpyAsync(src.p, stg[slot].p, enc * B * POS_WB, hipMemcpyHostToDevice, s));
-      HIP_TRY(erasure_masked_cols(fid, src.as<uint32_t>(), B, c.log_n, g.as<uint32_t>(),
-                                  data_out ? a.as<uint32_t>() : nullptr, c.slot.as<int32_t>(),
-                                  c.lambda.as<uint32_t>(), dbad.as<uint32_t>(), s));
-      if ((st = erasure_core(c, g.as<uint32_t>(), h.as<uint32_t>(), B))) return st;
-      if (n_bad && (want_vals || data_out))
-        HIP_TRY(erasure_fill(fid, h.as<uint32_t>(), c.log_n, B, c.erased.as<uint32_t>(), n_bad, c.dinv.as<uint32_t>(),
-                             vals.as<uint32_t>(), cols_out ? cm.as<uint32_t>() : nullptr,
-                             data_out ? a.as<uint32_t>() : nullptr, true, s));
-      if (cols_out && n_bad)
-        HIP_TRY(hipMemcpyAsync(ocols.p, cm.p, n_bad * B * POS_WB, hipMemcpyDeviceToHost, s));
-      if (data_out) {
-        // decode of the completed rows: ifft_oi as in lcpc_pos_decode_porenc
-        uint32_t *x = a.as<uint32_t>(), *y = g.as<uint32_t>();
-        if (LCPC_FFT_OUTPUT_BITREV) {
-          HIP_TRY(bitrev_scale(fid, x, y, c.log_n, B, nullptr, s));
-          std::swap(x, y);
-        }
-        uint32_t *z = h.as<uint32_t>();
-        HIP_TRY(ntt_rows(c.inv, x, enc, enc, z, enc, B, s));
-        HIP_TRY(bitrev_scale(fid, z, x, c.log_n, B, inv, s));
-        HIP_TRY(hipMemcpy2DAsync(z, pre * POS_WB, x, enc * POS_WB, pre * POS_WB, B, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(pos_unpack7(reinterpret_cast<const uint64_t *>(z), B * pre, dbytes.as<uint8_t>(), B * pre * POS_DB, s));
-        HIP_TRY(hipMemcpyAsync(odata.p, dbytes.p, B * pre * POS_DB, hipMemcpyDeviceToHost, s));
-      }
-    }
-    // column-digest chunks of the repaired columns' rows (the writer's chunk machinery)
-    if (digests_out && n_bad)
-      HIP_TRY(leaf_chunk_cvs(fid, vals.as<uint32_t>(), r0, rows, n_bad, n_bad, c_lo, c_hi,
-                             dcv.as<uint32_t>() + c_lo * n_bad * 8, s, true));
-    // the next batch's rows gather on the host while this one runs
-    const size_t this_r0 = r0, this_B = B;
-    if (c_hi < n_chunks) {
-      size_t nr0, nB, nchi;
-      batch_rows(c_hi, &nr0, &nB, &nchi);
-      stage((k + 1) & 1, nr0, nB);
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    if (this_B && cols_out && n_bad)
-      parallel_for(n_bad, [&](size_t j) {
-        std::memcpy(cols_out + (j * rows + this_r0) * POS_WB, ocols.b() + j * this_B * POS_WB, this_B * POS_WB);
-      });
-    if (this_B && data_out) par_memcpy(data_out + this_r0 * pre * POS_DB, odata.b(), this_B * pre * POS_DB);
-  }
-  uint32_t flags[2] = {0, 0};
-  HIP_TRY(hipMemcpyAsync(&flags[0], c.flag.p, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(&flags[1], dbad.p, 4, hipMemcpyDeviceToHost, s));
-  if (digests_out && n_bad) {
-    DBuf leaves;
-    HIP_TRY(leaves.alloc(dev, n_bad * 32));
-    HIP_TRY(leaves_from_cvs(dcv.as<uint32_t>(), n_bad, (int)n_chunks, leaves.as<uint8_t>(), s));
-    HIP_TRY(hipMemcpyAsync(digests_out, leaves.p, n_bad * 32, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-  }
-  HIP_TRY(hipStreamSynchronize(s));
-  if (flags[1])
-    return fail(LCPC_ERR_UNRECOVERABLE, "a column not listed as damaged holds a non-canonical element");
-  if (flags[0])
-    return fail(LCPC_ERR_UNRECOVERABLE, "a row is not a codeword on the columns not listed as damaged (degree check failed)");
-  return LCPC_OK;
-}
-
-}  // extern "C"
-
-// ================================================================= R-S error location by syndromes
-// No counterpart in the reference.  The erasure decoder above needs to be told where the damage is;
-// here the rows say it themselves: the coefficients its degree check tests for zero are power sums
-// of the wrong positions, Berlekamp-Massey finds their shortest recurrence and one forward
-// transform of its connection polynomial has its zeros at the wrong positions.  Kernels: rs_locate.hip.
-namespace {
-
-// Per-call device state of the locator, for batches of at most bmax rows.
-struct LocateCtx {
-  size_t bmax = 0, n_synd = 0;
-  DBuf flag, dirty, bm_len, n_zero, on_erased, dstatus, mask, status, nerr, col_any, coef;
-  std::vector<uint8_t> hflag;
-  std::vector<uint32_t> hdirty;  // the batch's rows with a non-zero syndrome, ascending
-};
-
-lcpc_status locate_ctx_init(LocateCtx &lc, const ErasureCtx &c, Device *dev, size_t bmax) {
-  lc.bmax = bmax;
-  lc.n_synd = c.n - c.deg_bound;
-  const size_t wb = (size_t)field_bytes(c.fid);
-  HIP_TRY(lc.flag.alloc(dev, bmax));
-  HIP_TRY(lc.dirty.alloc(dev, bmax * 4));
-  HIP_TRY(lc.bm_len.alloc(dev, bmax * 4));
-  HIP_TRY(lc.n_zero.alloc(dev, bmax * 4));
-  HIP_TRY(lc.on_erased.alloc(dev, bmax * 4));
-  HIP_TRY(lc.dstatus.alloc(dev, bmax));
-  HIP_TRY(lc.status.alloc(dev, bmax));
-  HIP_TRY(lc.nerr.alloc(dev, bmax * 4));
-  HIP_TRY(lc.col_any.alloc(dev, c.n));
-  HIP_TRY(hipMemsetAsync(lc.col_any.p, 0, c.n, c.s));
-  if (lc.n_synd) {
-    HIP_TRY(lc.mask.alloc(dev, bmax * c.n));
-    HIP_TRY(lc.coef.alloc(dev, bmax * c.n * wb));
-  }
-  lc.hflag.assign(bmax, 0);
-  return LCPC_OK;
-}
-
-// g: B masked rows in the inverse plan's input order; h: B rows of room.  Queues the inverse
-// transform, the syndrome scan and the copy of the row flags to lc.hflag; the caller drains the
-// stream before locate_dirty.
-lcpc_status locate_scan(ErasureCtx &c, LocateCtx &lc, uint32_t *g, uint32_t *h, size_t B) {
-  HIP_TRY(hipMemsetAsync(lc.status.p, 0, B, c.s));
-  HIP_TRY(hipMemsetAsync(lc.nerr.p, 0, B * 4, c.s));
-  if (!lc.n_synd) return LCPC_OK;
-  HIP_TRY(hipMemsetAsync(lc.flag.p, 0, B, c.s));
-  HIP_TRY(ntt_rows(c.inv, g, c.n, c.n, h, c.n, B, c.s));
-  HIP_TRY(rs_locate_scan(c.fid, h, c.log_n, B, c.deg_bound, lc.flag.as<uint8_t>(), c.s));
-  HIP_TRY(hipMemcpyAsync(lc.hflag.data(), lc.flag.p, B, hipMemcpyDeviceToHost, c.s));
-  return LCPC_OK;
-}
-
-// After locate_scan and a drained stream: the flagged rows go through gather, Berlekamp-Massey, the
-// root transform and the zero scan (g and h are clobbered).  On return the stream is drained,
-// lc.hdirty lists the flagged rows, lc.status / lc.nerr hold the batch's verdicts, lc.mask[d] the
-// located positions of row lc.hdirty[d], and lc.col_any has accumulated them.
-lcpc_status locate_dirty(ErasureCtx &c, LocateCtx &lc, uint32_t *g, uint32_t *h, size_t B) {
-  lc.hdirty.clear();
-  if (!lc.n_synd) return LCPC_OK;
-  for (size_t r = 0; r < B; r++)
-    if (lc.hflag[r]) lc.hdirty.push_back((uint32_t)r);
-  const size_t nd = lc.hdirty.size();
-  if (!nd) return LCPC_OK;  // codewords: nothing more to pay
-  HIP_TRY(hipMemcpyAsync(lc.dirty.p, lc.hdirty.data(), nd * 4, hipMemcpyHostToDevice, c.s));
-  HIP_TRY(rs_locate_gather(c.fid, h, c.log_n, lc.dirty.as<uint32_t>(), nd, c.deg_bound, lc.n_synd, g, c.s));
-  HIP_TRY(rs_locate_bm(c.fid, g, nd, lc.n_synd, c.log_n, lc.coef.as<uint32_t>(), lc.bm_len.as<uint32_t>(), c.s));
-  {
-    prof::Scope ps("rs_locate_root_ntt", c.s);
-    HIP_TRY(ntt_rows(c.fwd, lc.coef.as<uint32_t>(), c.n, c.n, h, c.n, nd, c.s));
-  }
-  HIP_TRY(rs_locate_zeros(c.fid, h, c.log_n, nd, c.slot.as<int32_t>(), lc.mask.as<uint8_t>(),
-                          lc.n_zero.as<uint32_t>(), lc.on_erased.as<uint32_t>(), c.s));
-  HIP_TRY(rs_locate_finish(lc.dirty.as<uint32_t>(), nd, c.log_n, lc.bm_len.as<uint32_t>(), lc.n_zero.as<uint32_t>(),
-                           lc.on_erased.as<uint32_t>(), lc.dstatus.as<uint8_t>(), lc.mask.as<uint8_t>(),
-                           lc.status.as<uint8_t>(), lc.nerr.as<uint32_t>(), lc.col_any.as<uint8_t>(), c.s));
-  HIP_TRY(hipStreamSynchronize(c.s));
-  return LCPC_OK;
-}
-
-// lcpc_rs_locate_errors_rows after its argument checks; every output may be null
-lcpc_status locate_rows(Device *dev, hipStream_t s, int f, const uint64_t *rows, size_t n_rows, size_t len,
-                        size_t n_per_row, const std::vector<uint32_t> &e32, uint8_t *row_status,
-                        uint32_t *row_n_errors, uint8_t *err_mask, uint8_t *col_any) {
-  lcpc_status st;
-  const size_t wb = (size_t)field_bytes(f), nl = wb / 8;
-  ErasureCtx c;
-  if ((st = erasure_ctx_init(c, dev, s, f, len, n_per_row, e32))) return st;
-  const size_t bmax = std::max<size_t>(1, std::min(n_rows, ((size_t)16 << 20) / (len * wb)));
-  LocateCtx lc;
-  if ((st = locate_ctx_init(lc, c, dev, bmax))) return st;
-  DBuf a, g, h;
-  HIP_TRY(a.alloc(dev, bmax * len * wb));
-  HIP_TRY(g.alloc(dev, bmax * len * wb));
-  HIP_TRY(h.alloc(dev, bmax * len * wb));
-  std::vector<uint8_t> hmask;
-  for (size_t r0 = 0; r0 < n_rows; r0 += bmax) {
-    const size_t B = std::min(bmax, n_rows - r0);
-    HIP_TRY(hipMemcpyAsync(a.p, rows + r0 * len * nl, B * len * wb, hipMemcpyHostToDevice, s));
-    HIP_TRY(erasure_masked_rows(f, a.as<uint32_t>(), g.as<uint32_t>(), c.log_n, B, c.slot.as<int32_t>(),
-                                c.lambda.as<uint32_t>(), s));
-    if ((st = locate_scan(c, lc, g.as<uint32_t>(), h.as<uint32_t>(), B))) return st;
-    HIP_TRY(hipStreamSynchronize(s));
-    if ((st = locate_dirty(c, lc, g.as<uint32_t>(), h.as<uint32_t>(), B))) return st;
-    const size_t nd = lc.hdirty.size();
-    if (row_status) HIP_TRY(hipMemcpyAsync(row_status + r0, lc.status.p, B, hipMemcpyDeviceToHost, s));
-    if (row_n_errors) HIP_TRY(hipMemcpyAsync(row_n_errors + r0, lc.nerr.p, B * 4, hipMemcpyDeviceToHost, s));
-    if (err_mask) {
-      std::memset(err_mask + r0 * len, 0, B * len);
-      if (nd) {
-        hmask.resize(nd * len);
-        HIP_TRY(hipMemcpyAsync(hmask.data(), lc.mask.p, nd * len, hipMemcpyDeviceToHost, s));
-      }
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    if (err_mask)
-      for (size_t d = 0; d < nd; d++) std::memcpy(err_mask + (r0 + lc.hdirty[d]) * len, hmask.data() + d * len, len);
-  }
-  if (col_any) HIP_TRY(hipMemcpyAsync(col_any, lc.col_any.p, len, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return LCPC_OK;
-}
-
-lcpc_status locate_args(lcpc_field f, const void *rows, size_t n_rows, size_t len, size_t n_per_row,
-                        const uint64_t *erased, size_t n_erased, std::vector<uint32_t> &e32) {
-  if (!valid_field(f) || (!rows && n_rows)) return fail(LCPC_ERR_INVALID_ARG, "arguments");
-  if (!field_gpu_supported(f)) return fail(LCPC_ERR_UNSUPPORTED, "field has no gfx950 kernels");
-  lcpc_status st = check_fft_len(f, len);
-  if (st) return st;
-  return erasure_check(len, n_per_row, erased, n_erased, e32);
-}
-
-// One pass of lcpc_pos_locate_porenc over the image with the columns e32 never read.  col_any[c] = 1
-// where a row located a wrong element; *noncanon = 1 if a column that was read holds an element
-// that is not < p (the verdicts are then void: such elements were taken as zero).
-lcpc_status pos_locate_pass(Device *dev, hipStream_t s, const uint8_t *porenc, size_t pre, size_t enc, size_t rows,
-                            size_t row_capacity, const std::vector<uint32_t> &e32, uint8_t *col_any, size_t *n_dirty,
-                            size_t *n_unlocatable, uint32_t *noncanon) {
-  lcpc_status st;
-  const int fid = POS_FID;
-  ErasureCtx c;
-  if ((st = erasure_ctx_init(c, dev, s, fid, enc, pre, e32))) return st;
-  std::vector<uint8_t> is_bad(enc, 0);
-  for (uint32_t j : e32) is_bad[j] = 1;
-  // batches of whole BLAKE3 chunks of the column messages, as lcpc_pos_repair_columns
-  const size_t rows_per_chunk = 1024 / POS_WB;
-  const size_t n_chunks = leaf_n_chunks(fid, rows);
-  size_t want_rows = std::max<size_t>(rows_per_chunk, POS_STAGE_BYTES / (enc * POS_WB));
-  if (const char *env = std::getenv("LCPC_POS_REPAIR_BATCH_ROWS")) {
-    const unsigned long long v = std::strtoull(env, nullptr, 10);
-    if (v) want_rows = std::min<size_t>(want_rows, (size_t)v);
-  }
-  const size_t cpb = std::max<size_t>(1, want_rows / rows_per_chunk);
-  const size_t bmax = std::max<size_t>(1, std::min(rows, cpb * rows_per_chunk));
-  LocateCtx lc;
-  if ((st = locate_ctx_init(lc, c, dev, bmax))) return st;
-  DBuf src, g, h, dbad;
-  HIP_TRY(src.alloc(dev, bmax * enc * POS_WB));
-  HIP_TRY(g.alloc(dev, bmax * enc * POS_WB));
-  HIP_TRY(h.alloc(dev, bmax * enc * POS_WB));
-  HIP_TRY(dbad.alloc(dev, 8));
-  HIP_TRY(hipMemsetAsync(dbad.p, 0, 8, s));
-  Pinned stg[2];
-  for (auto &x : stg)
-    if (!x.get(dev, bmax * enc * POS_WB)) return fail(LCPC_ERR_OUT_OF_MEMORY, "pinned host staging");
-  auto batch_rows = [&](size_t c_lo, size_t *r0, size_t *B, size_t *c_hi) {
-    *c_hi = std::min(n_chunks, c_lo + cpb);
-    *r0 = std::min(rows, lcpc_leaf_chunk_first_row((lcpc_field)fid, c_lo));
-    const size_t r1 = *c_hi == n_chunks ? rows : std::min(rows, lcpc_leaf_chunk_first_row((lcpc_field)fid, *c_hi));
-    *B = r1 - *r0;
-  };
-  // the known columns are never read, neither here nor by the kernels
-  auto stage = [&](int slot, size_t r0, size_t B) {
-    if (!B) return;
-    parallel_for(enc, [&](size_t col) {
-      if (!is_bad[col])
-        std::memcpy(stg[slot].b() + col * B * POS_WB, porenc + (col * row_capacity + r0) * POS_WB, B * POS_WB);
-    });
-  };
-  std::vector<uint8_t> hstatus(bmax);
-  size_t nd_total = 0, nu_total = 0;
-  size_t r0 = 0, B = 0, c_hi = 0;
-  batch_rows(0, &r0, &B, &c_hi);
-  stage(0, r0, B);
-  int k = 0;
-  for (size_t c_lo = 0; c_lo < n_chunks; c_lo = c_hi, k++) {
-    batch_rows(c_lo, &r0, &B, &c_hi);
-    const int slot = k & 1;
-    if (B) {
-      HIP_TRY(hipMemcpyAsync(src.p, stg[slot].p, enc * B * POS_WB, hipMemcpyHostToDevice, s));
-      HIP_TRY(erasure_masked_cols(fid, src.as<uint32_t>(), B, c.log_n, g.as<uint32_t>(), nullptr,
-                                  c.slot.as<int32_t>(), c.lambda.as<uint32_t>(), dbad.as<uint32_t>(), s));
-      if ((st = locate_scan(c, lc, g.as<uint32_t>(), h.as<uint32_t>(), B))) return st;
-    }
-    // the next batch's rows gather on the host while this one runs
-    if (c_hi < n_chunks) {
-      size_t nr0, nB, nchi;
-      batch_rows(c_hi, &nr0, &nB, &nchi);
-      stage((k + 1) & 1, nr0, nB);
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    if (!B) continue;
-    if ((st = locate_dirty(c, lc, g.as<uint32_t>(), h.as<uint32_t>(), B))) return st;
-    if (!lc.hdirty.empty()) {
-      HIP_TRY(hipMemcpyAsync(hstatus.data(), lc.status.p, B, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      nd_total += lc.hdirty.size();
-      for (uint32_t r : lc.hdirty) nu_total += hstatus[r] == 2;
-    }
-  }
-  HIP_TRY(hipMemcpyAsync(noncanon, dbad.p, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(col_any, lc.col_any.p, enc, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  *n_dirty = nd_total;
-  *n_unlocatable = nu_total;
-  return LCPC_OK;
-}
-
-// col_bad[c] = 1 for the columns not in `skip` that hold an element that is not < p
-lcpc_status pos_noncanonical_columns(Device *dev, hipStream_t s, const uint8_t *porenc, size_t enc, size_t rows,
-                                     size_t row_capacity, const std::vector<uint8_t> &skip,
-                                     std::vector<uint32_t> &col_bad) {
-  col_bad.assign(enc, 0);
-  const size_t col_bytes = rows * POS_WB;
-  if (!col_bytes) return LCPC_OK;
-  const size_t cpb = std::max<size_t>(1, std::min(enc, POS_STAGE_BYTES / col_bytes));
-  DBuf dcols, dbad;
-  HIP_TRY(dcols.alloc(dev, cpb * col_bytes));
-  HIP_TRY(dbad.alloc(dev, enc * 4));
-  HIP_TRY(hipMemsetAsync(dbad.p, 0, enc * 4, s));
-  Pinned stg;
-  if (!stg.get(dev, cpb * col_bytes)) return fail(LCPC_ERR_OUT_OF_MEMORY, "pinned host staging");
-  for (size_t c0 = 0; c0 < enc; c0 += cpb) {
-    const size_t nc = std::min(enc, c0 + cpb) - c0;
-    parallel_for(nc, [&](size_t c) {
-      if (skip[c0 + c])  // never read: zeros are canonical
-        std::memset(stg.b() + c * col_bytes, 0, col_bytes);
-      else
-        std::memcpy(stg.b() + c * col_bytes, porenc + (c0 + c) * row_capacity * POS_WB, col_bytes);
-    });
-    HIP_TRY(hipMemcpyAsync(dcols.p, stg.p, nc * col_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(scrub_col_canon(POS_FID, dcols.as<uint32_t>(), rows, nc, dbad.as<uint32_t>() + c0, s));
-    HIP_TRY(hipStreamSynchronize(s));
-  }
-  HIP_TRY(hipMemcpyAsync(col_bad.data(), dbad.p, enc * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return LCPC_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-size_t lcpc_rs_locate_max_errors(lcpc_field f) { return valid_field(f) ? rs_locate_cap(f) : 0; }
-
-lcpc_status lcpc_rs_locate_errors_rows(lcpc_field f, const uint64_t *rows, size_t n_rows, size_t len, size_t n_per_row,
-                                       const uint64_t *erased, size_t n_erased, uint8_t *row_status,
-                                       uint32_t *row_n_errors, uint8_t *err_mask, uint8_t *col_any) {
-  std::vector<uint32_t> e32;
-  lcpc_status st = locate_args(f, rows, n_rows, len, n_per_row, erased, n_erased, e32);
-  if (st) return st;
-  if (!row_status && n_rows) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  if (n_rows == 0) {
-    if (col_any) std::memset(col_any, 0, len);
-    return LCPC_OK;
-  }
-  Device *dev = current_device(&st);
-  if (!dev) return st;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  return locate_rows(dev, lease.s, f, rows, n_rows, len, n_per_row, e32, row_status, row_n_errors, err_mask, col_any);
-}
-
-lcpc_status lcpc_rs_decode_rows(lcpc_field f, uint64_t *rows, size_t n_rows, size_t len, size_t n_per_row,
-                                const uint64_t *erased, size_t n_erased, uint8_t *row_status) {
-  std::vector<uint32_t> e32;
-  lcpc_status st = locate_args(f, rows, n_rows, len, n_per_row, erased, n_erased, e32);
-  if (st) return st;
-  if (n_rows == 0) return LCPC_OK;
-  Device *dev = current_device(&st);
-  if (!dev) return st;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  hipStream_t s = lease.s;
-  const size_t wb = (size_t)field_bytes(f), nl = wb / 8;
-  std::vector<uint8_t> status(n_rows), mask(n_rows * len);
-  if ((st = locate_rows(dev, s, f, rows, n_rows, len, n_per_row, e32, status.data(), nullptr, mask.data(), nullptr)))
-    return st;
-  if (row_status) std::memcpy(row_status, status.data(), n_rows);
-  for (size_t r = 0; r < n_rows; r++)
-    if (status[r] == 2)
-      return fail(LCPC_ERR_UNRECOVERABLE, "a row has more wrong positions than can be located (row " +
-                                              std::to_string(r) + ")");
-  // Erasure decoding with the known and the located positions as the erasure set: the same codeword,
-  // which any n_per_row positions fix.  Consecutive rows share a set while its size fits the code's
-  // redundancy; a row alone always fits (n_erased + its errors <= n_erased + (len - n_per_row - n_erased) / 2).
-  struct Write {
-    size_t r, pos;
-    size_t val;  // index of the value's first limb in `vals`
-  };
-  std::vector<Write> writes;
-  std::vector<uint64_t> vals, filled;
-  const size_t room = len - n_per_row;
-  std::vector<uint8_t> in_union(len);
-  size_t lo = 0;
-  while (lo < n_rows) {
-    std::fill(in_union.begin(), in_union.end(), 0);
-    for (uint32_t j : e32) in_union[j] = 1;
-    size_t count = n_erased, hi = lo;
-    std::vector<uint32_t> set = e32;
-    for (; hi < n_rows; hi++) {
-      const uint8_t *m = mask.data() + hi * len;
-      size_t extra = 0;
-      for (size_t p = 0; p < len; p++) extra += m[p] && !in_union[p];
-      if (hi > lo && count + extra > room) break;
-      for (size_t p = 0; p < len; p++)
-        if (m[p] && !in_union[p]) {
-          in_union[p] = 1;
-          set.push_back((uint32_t)p);
-        }
-      count += extra;
-    }
-    if ((st = erasure_decode_values(dev, s, f, rows + lo * len * nl, hi - lo, len, n_per_row, set, filled))) return st;
-    for (size_t r = lo; r < hi; r++)
-      for (size_t j = 0; j < set.size(); j++)
-        if (j < n_erased || mask[r * len + set[j]]) {
-          writes.push_back({r, set[j], vals.size()});
-          const uint64_t *v = filled.data() + ((r - lo) * set.size() + j) * nl;
-          vals.insert(vals.end(), v, v + nl);
-        }
-    lo = hi;
-  }
-  // nothing was written so far: only the located and the erased positions are, every other limb keeps its bits
-  for (const Write &w : writes) std::memcpy(rows + (w.r * len + w.pos) * nl, vals.data() + w.val, wb);
-  return LCPC_OK;
-}
-
-lcpc_status lcpc_pos_locate_porenc(const uint8_t *porenc, size_t pre, size_t enc, size_t rows_written,
-                                   size_t row_capacity, const uint64_t *known_bad, size_t n_known, uint8_t *col_status,
-                                   size_t *n_bad_cols, size_t *n_dirty_rows, size_t *n_unlocatable_rows) {
-  lcpc_status st = pos_dims_check(pre, enc);
-  if (st) return st;
-  if (rows_written > row_capacity) return fail(LCPC_ERR_INVALID_ARG, "rows_written > row_capacity");
-  if (!col_status || (!porenc && rows_written)) return fail(LCPC_ERR_INVALID_ARG, "null argument");
-  std::vector<uint32_t> e32;
-  if ((st = erasure_check(enc, pre, known_bad, n_known, e32))) return st;
-  Device *dev = current_device(&st);
-  if (!dev) return st;
-  Lease lease(dev);
-  HIP_TRY(hipSetDevice(dev->id));
-  hipStream_t s = lease.s;
-  std::vector<uint8_t> col_any(enc, 0), is_known(enc, 0), is_noncanon(enc, 0);
-  for (uint32_t j : e32) is_known[j] = 1;
-  size_t n_dirty = 0, n_unloc = 0;
-  if (rows_written) {
-    // optimistic: the masked load's flag says whether any column it read is non-canonical; only then
-    // the image is scanned to name those columns, which join the erasure set for a second pass
-    uint32_t noncanon = 0;
-    if ((st = pos_locate_pass(dev, s, porenc, pre, enc, rows_written, row_capacity, e32, col_any.data(), &n_dirty,
-                              &n_unloc, &noncanon)))
-      return st;
-    if (noncanon) {
-      std::vector<uint32_t> col_bad;
-      if ((st = pos_noncanonical_columns(dev, s, porenc, enc, rows_written, row_capacity, is_known, col_bad)))
-        return st;
-      for (size_t c = 0; c < enc; c++)
-        if (col_bad[c] && !is_known[c]) {
-          is_noncanon[c] = 1;
-          e32.push_back((uint32_t)c);
-        }
-      if (e32.size() > enc - pre)
-        return fail(LCPC_ERR_UNRECOVERABLE, "more known and non-canonical columns than the code's redundancy (enc - pre)");
-      if ((st = pos_locate_pass(dev, s, porenc, pre, enc, rows_written, row_capacity, e32, col_any.data(), &n_dirty,
-                                &n_unloc, &noncanon)))
-        return st;
-    }
-  }
-  size_t n_bad = 0;
-  for (size_t c = 0; c < enc; c++) {
-    col_status[c] = is_known[c] ? 3 : is_noncanon[c] ? 2 : col_any[c] ? 1 : 0;
-    n_bad += col_status[c] != 0;
-  }
-  if (n_bad_cols) *n_bad_cols = n_bad;
-  if (n_dirty_rows) *n_dirty_rows = n_dirty;
-  if (n_unlocatable_rows) *n_unlocatable_rows = n_unloc;
-  return LCPC_OK;
-}
-
-}  // extern "C"
