@@ -704,6 +704,76 @@ lcpc_status lcpc_pos_writer_copy_cvs(const lcpc_pos_writer *w, uint8_t *out);
 lcpc_status lcpc_leaves_fold_cvs(const uint8_t *cvs, size_t n_chunks, size_t n_cols, uint8_t *leaves,
                                  uint8_t *cvs_after);
 
+/* ------------------------------------------------------------------ PoS checkable reads
+ * Reading bytes [byte_start, byte_end) of a stored file so that the client can check them against
+ * the 32-byte root it keeps (no counterpart in the reference: RequestFileRow, networking/server.rs:
+ * 474-493, answers with bytes the client must trust, or the client downloads the whole file and
+ * recommits it, client.rs:306-429).  Additive within version 3; WriteableFt63 and BLAKE3 only.
+ *
+ * Two messages, IN THIS ORDER -- the order is a soundness condition, not a convention:
+ *   1. the client asks for the range and receives the raw bytes of the whole rows that cover it,
+ *      [row_lo * 7 pre, min(row_hi * 7 pre, file_len));
+ *   2. ONLY THEN the client draws the column indices (strictly increasing, < enc) and sends them;
+ *      the server answers with one opening per column.
+ * A server that knows the columns before it sends the rows can interpolate a wrong row that agrees
+ * with the committed one at all of them (fewer than pre columns are opened).
+ *
+ * A column's leaf is BLAKE3(32 zero bytes || its rows_written 8-byte elements), a left-balanced tree
+ * over n = lcpc_leaf_n_chunks(LCPC_FT63, rows_written) 1-KiB chunks.  An opening covers only the
+ * chunks [chunk_lo, chunk_hi) that hold the rows read:
+ *   segment  the column's elements of rows [seg_row_lo, seg_row_hi) -- the rows of those chunks,
+ *            clipped to rows_written -- as 8-byte canonical reprs, the bytes of the `.porenc`;
+ *   covers   walk the tree from the root [0, n); a node [lo, hi) of more than one chunk splits at
+ *            lo + (the largest power of two < hi - lo).  A node disjoint from [chunk_lo, chunk_hi)
+ *            contributes its chaining value (never with ROOT) and is not descended; a node inside
+ *            the range contributes nothing; any other node is descended, left then right.  The
+ *            covers are those values in walk order: none when n = 1 or the range is every chunk,
+ *            at most 2 log2(n) otherwise;
+ *   path     the column's Merkle path, as everywhere.
+ * The client rebuilds each leaf from the segment's chunk CVs (their true chunk counters) and the
+ * covers, ROOT on the last parent (a one-chunk leaf carries ROOT on the chunk), checks the paths
+ * with lcpc_verify_leaf_paths, and checks the rows against the segments: with a private random u over
+ * rows [row_lo, row_hi) (zero on the segment's other rows), v = u^T M over the received bytes
+ * (lcpc_pos_left_multiply_bytes) and Enc(v), every opened column j must have
+ * Enc(v)[j] = sum_r u_r segment_j[r].  If the committed rows are codewords, a wrong row differs from
+ * the committed one in at least enc - pre + 1 columns; u keeps the difference non-zero except with
+ * probability 1/p, and each column, drawn after the rows were sent, misses it with probability at
+ * most pre / enc. */
+/* Host-only, no device.  rows = ceil(ceil(file_len / 7) / pre) and rb = 7 pre:
+ * *row_lo = byte_start / rb, *row_hi = ceil(byte_end / rb); [*chunk_lo, *chunk_hi) = the chunks
+ * that hold those rows; [*seg_row_lo, *seg_row_hi) = the rows of those chunks clipped to rows;
+ * *n_cover = the number of cover nodes, and cover_nodes[2 j], cover_nodes[2 j + 1] = the chunk range
+ * [lo, hi) of cover j in order.  Any result pointer may be NULL; cover_cap = the pairs cover_nodes
+ * has room for (128 is enough for any size_t; too few is LCPC_ERR_INVALID_ARG).
+ * byte_start >= byte_end, byte_end > file_len or pre == 0: LCPC_ERR_INVALID_ARG. */
+lcpc_status lcpc_pos_read_plan(size_t file_len, size_t byte_start, size_t byte_end, size_t pre,
+                               size_t *row_lo, size_t *row_hi, size_t *chunk_lo, size_t *chunk_hi,
+                               size_t *seg_row_lo, size_t *seg_row_hi, size_t *n_cover,
+                               size_t *cover_nodes, size_t cover_cap);
+/* The server's cover values for the columns idx[0..n_idx) (each < enc) opened on chunks
+ * [chunk_lo, chunk_hi): covers_out[n_idx][n_cover][32], from the chunk-CV cache, which is only read.
+ * An empty range or chunk_hi past the cache's chunks: LCPC_ERR_INVALID_ARG. */
+lcpc_status lcpc_pos_segment_covers_from_cache(const lcpc_pos_chunk_cache *cache, const uint64_t *idx,
+                                               size_t n_idx, size_t chunk_lo, size_t chunk_hi,
+                                               uint8_t *covers_out);
+/* The same bytes without a cache, from the opened columns themselves: cols[n_idx][rows_written]
+ * canonical 8-byte elements as the `.porenc` holds them.  An element that is not < p is
+ * LCPC_ERR_INVALID_ARG (as lcpc_pos_porenc_tree). */
+lcpc_status lcpc_pos_segment_covers_from_columns(const uint64_t *cols, size_t rows_written, size_t n_idx,
+                                                 size_t chunk_lo, size_t chunk_hi, uint8_t *covers_out);
+/* The client's side: leaves_out[n_idx][32] rebuilt from segs[n_idx][seg_rows] (canonical 8-byte
+ * elements, seg_rows = seg_row_hi - seg_row_lo of the plan) and covers[n_idx][n_cover][32].
+ * weights: NULL, or seg_rows elements (Montgomery limbs) u_r for the segment's rows; then
+ * dots_out[k] = sum_r weights[r] segs[k][r] (Montgomery limbs, summed in the pass that hashes the
+ * segments).  dots_out is NULL iff weights is.  A segment element that is not < p is a verdict, not
+ * an error: canonical_ok[k] = 0 (else 1), the call still returns LCPC_OK, and leaf and dot of that
+ * column are unspecified.  n_cover that is not the plan's count for (rows_written, chunk_lo,
+ * chunk_hi), chunk_hi past the column's chunks or an empty range: LCPC_ERR_INVALID_ARG. */
+lcpc_status lcpc_pos_segment_leaves(const uint64_t *segs, size_t n_idx, size_t rows_written,
+                                    size_t chunk_lo, size_t chunk_hi, const uint8_t *covers,
+                                    size_t n_cover, const uint64_t *weights, uint8_t *leaves_out,
+                                    uint64_t *dots_out, uint8_t *canonical_ok);
+
 /* ------------------------------------------------------------------ row shards (multi-GPU)
  * One process per GPU holds rows [row0, row0 + n_shard_rows) of an n_rows x n_per_row Ligero
  * coefficient matrix.  With the exchanges done by the caller (lcpc_proof_of_storage_amd/

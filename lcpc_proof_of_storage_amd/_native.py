@@ -239,6 +239,10 @@ SIGNATURES = {
     "lcpc_pos_writer_n_chunks": (sz, [vp]),
     "lcpc_pos_writer_copy_cvs": (i32, [vp, u8p]),
     "lcpc_leaves_fold_cvs": (i32, [u8p, sz, sz, u8p, u8p]),
+    "lcpc_pos_read_plan": (i32, [sz, sz, sz, sz, szp, szp, szp, szp, szp, szp, szp, szp, sz]),
+    "lcpc_pos_segment_covers_from_cache": (i32, [vp, u64p, sz, sz, sz, u8p]),
+    "lcpc_pos_segment_covers_from_columns": (i32, [u64p, sz, sz, sz, sz, u8p]),
+    "lcpc_pos_segment_leaves": (i32, [u64p, sz, sz, sz, sz, u8p, sz, u64p, u8p, u64p, u8p]),
     "lcpc_rs_domain_points": (i32, [i32, sz, u64p]),
     "lcpc_rs_erasure_decode_rows": (i32, [i32, u64p, sz, sz, sz, u64p, sz]),
     "lcpc_pos_scrub_porenc": (i32, [u8p, sz, sz, sz, u8p, u8p, u8p, szp]),

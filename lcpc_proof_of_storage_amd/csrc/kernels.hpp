@@ -147,6 +147,46 @@ hipError_t merkle_tree_io(const uint8_t *ins, size_t n_ins, uint8_t *outs, hipSt
 // two) into levels 0..log2(B) of the whole tree of G B leaves ([leaves | level 1 | ...] layout)
 hipError_t assemble_subtrees(const uint8_t *subs, size_t B, size_t G, uint8_t *tree, hipStream_t s);
 
+// ------------------------------------------------------------------ checkable reads (pos_read.hip)
+// A column opened on the chunk range [chunk_lo, chunk_hi) of its n_chunks-chunk leaf message: the
+// leaf is rebuilt from the chunk CVs of the range and the CVs of the subtrees that cover the rest.
+// Which nodes those are depends only on (n_chunks, chunk_lo, chunk_hi), so the host flattens
+// BLAKE3's left-balanced tree, pruned at the covers and at the nodes inside the range, into a
+// post-order program that every column runs on a register stack of chaining values:
+//   COVER  push covers[col][a]
+//   CHUNKS push the subtree over the range's chunk CVs [a, a + b) (indices from chunk_lo)
+//   GROUPS the same over b group nodes from group a of group_cvs (groups of READ_GROUP chunks,
+//          aligned, are whole subtrees: the argument of blake3.hip's k_leaf_merge_groups)
+//   MERGE  pop right and left, push their parent
+// root: the last parent this op makes carries ROOT (the program's last op only).
+constexpr int READ_GROUP = 8;
+enum : uint32_t { READ_OP_COVER = 0, READ_OP_CHUNKS = 1, READ_OP_GROUPS = 2, READ_OP_MERGE = 3 };
+struct ReadOp {
+  uint32_t kind, root;
+  uint64_t a, b;
+};
+// covers[(k * n_cover + j) * 32] = the CV of the subtree over chunks [nodes[2 j], nodes[2 j + 1]) of
+// column idx[k] (k with idx null) of cvs, a [chunk][cv_stride columns] array of chunk CVs that is
+// only read.  One thread per (column, node); never ROOT (a cover is never the whole tree).
+// n_chunks <= 2^20.
+hipError_t read_cover_values(const uint32_t *cvs, size_t cv_stride, size_t n_chunks, const uint64_t *idx,
+                             size_t n_idx, const uint64_t *nodes, size_t n_cover, uint8_t *covers, hipStream_t s);
+// leaf_chunk_cvs_slices for n_idx segments (rows from row0 = the first row of chunk_lo on) that also
+// sums partials[(chunk - chunk_lo) * n_idx + k] = sum of weights[r - row0] * element r over the
+// chunk's rows (Montgomery weights, canonical sums) and flags the columns, bad_cols[k] = 1, that hold
+// an element not < p.  cvs[(chunk - chunk_lo) * n_idx + k].
+hipError_t read_segment_chunks(int fid, const uint32_t *segs, size_t col_elems, size_t n_rows, size_t n_idx,
+                               size_t chunk_lo, size_t chunk_hi, uint32_t *cvs, const uint32_t *weights,
+                               uint32_t *partials, uint32_t *bad_cols, hipStream_t s);
+// group_cvs[g * n_idx + k] = the node over chunks [first + 8 g, min(first + 8 g + 8, chunk_end)) of
+// seg_cvs (whose chunk row 0 is chunk chunk_lo), g < n_groups: one thread per (column, group)
+hipError_t read_segment_groups(const uint32_t *seg_cvs, size_t n_idx, size_t chunk_lo, size_t first,
+                               size_t chunk_end, size_t n_groups, uint32_t *group_cvs, hipStream_t s);
+// leaves[k] = the program's result for column k; n_chunks (<= 2^20) sizes the stack
+hipError_t read_segment_leaves(const uint32_t *seg_cvs, const uint32_t *group_cvs, const uint8_t *covers,
+                               size_t n_idx, size_t n_cover, size_t n_chunks, const ReadOp *ops, size_t n_ops,
+                               uint8_t *leaves, hipStream_t s);
+
 // ------------------------------------------------------------------ other digests (digest.hip)
 // The commitment's digest D (lcpc_digest): BLAKE3 goes to the functions above, SHA-256 and the
 // Keccak-f[1600] sponge (SHA3-256, Keccak-256: one kernel, the padding byte a parameter) to

@@ -410,11 +410,7 @@ lcpc_status lcpc_pos_decode_porenc(const uint8_t *porenc, size_t pre, size_t enc
 // the message's only chunk, so after an edit or an append only the chunks whose rows, length or
 // one-chunk flag changed are read from the image and rehashed; the column digests are one
 // non-clobbering fold of the cache (leaves_fold_cvs) and the tree follows as everywhere else.
-struct lcpc_pos_chunk_cache {
-  Device *dev = nullptr;
-  size_t enc = 0, rows = 0, n_chunks = 0, cap_chunks = 0;
-  DBuf cvs;  // cap_chunks x enc x 32 B, the first n_chunks chunk rows valid
-};
+// (struct lcpc_pos_chunk_cache: pos_internal.hpp; the checkable read opens columns from it too.)
 
 namespace {
 

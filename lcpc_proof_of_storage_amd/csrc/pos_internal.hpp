@@ -238,3 +238,11 @@ lcpc_status for_column_blocks(Device *dev, hipStream_t s, const ImageSrc &img, s
 }
 
 }  // namespace lcpc_host
+
+// The column chunk-CV cache of a stored file (pos_files_host.cpp keeps it up to date;
+// pos_read_host.cpp reads it): [chunk][column] chaining values in device memory.
+struct lcpc_pos_chunk_cache {
+  lcpc_host::Device *dev = nullptr;
+  size_t enc = 0, rows = 0, n_chunks = 0, cap_chunks = 0;
+  lcpc_host::DBuf cvs;  // cap_chunks x enc x 32 B, the first n_chunks chunk rows valid
+};

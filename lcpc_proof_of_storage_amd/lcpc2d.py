@@ -43,7 +43,9 @@ TRANSCRIPT_CALLBACK = 35  # LCPC_ERR_TRANSCRIPT: a CallerTranscript callback fai
 VERIFIER = {10: "NumColOpens", 11: "ColumnPath", 12: "ColumnEval", 13: "ColumnDegree", 14: "OuterTensor",
             15: "InnerTensor", 16: "EncodingDims", 17: "Encode",
             # the update audit's client-side verdicts (pos.py): raised in Python, no C status
-            40: "UpdateMismatch", 41: "RowsMismatch", 42: "ReshapeMismatch"}
+            40: "UpdateMismatch", 41: "RowsMismatch", 42: "ReshapeMismatch",
+            # the checkable read's (pos.client_verify_read), Python-only as well
+            43: "ReadMismatch"}
 FFT = {20: "NotPowerOfTwo", 21: "TooBig", 22: "WrongSizePrecomp"}
 
 

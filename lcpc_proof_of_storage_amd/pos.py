@@ -24,6 +24,9 @@ commitment (names kept):
                                                          lcpc_online.rs:80-627
   lcpc_online::file_handler::left_multiply_unencoded_matrix_by_vector   file_handler.rs:614-638
 The field is WriteableFt63: the modulus, arithmetic and repr of FT63.
+
+Without a counterpart in the reference: the update audits' client checks and the
+checkable read, read_plan / ReadOpening / client_verify_read (§5e).
 """
 from __future__ import annotations
 
@@ -35,8 +38,8 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _native as N
-from .lcpc2d import (FT63, VERIFIER, LcColumn, LcCommit, LigeroEncoding, ProverError, VerifierError,
-                     _p64, _raise, collapse_columns, limbs, verify_column_path)
+from .lcpc2d import (FT63, VERIFIER, DeviceError, LcColumn, LcCommit, LigeroEncoding, ProverError, VerifierError,
+                     _p64, _raise, collapse_columns, digest_name, limbs, verify_column_path)
 
 WRITTEN_BYTES_WIDTH = 8   # size_of::<WriteableFt63>() (data_field.rs:24)
 DATA_BYTE_CAPACITY = 7    # CAPACITY / 8 (data_field.rs:22)
@@ -874,3 +877,174 @@ def client_verify_append_evaluation(old_root: bytes, new_root: bytes, old_len: i
                                     point, cols, response: UpdateEvaluation) -> np.ndarray:
     """The append flow (client.rs:1009-1135): an update at the old end."""
     return client_verify_update_evaluation(old_root, new_root, old_len, old_len, data, pre, enc, point, cols, response)
+
+
+# ---------------------------------------------------------------- checkable reads
+# Reading a byte range so that the client can check it against its root (include/lcpc_mi.h, "PoS
+# checkable reads"; DESIGN.md §5e).  No counterpart in the reference: RequestFileRow (networking/
+# server.rs:474-493) answers with bytes the client has to trust.
+#
+# THE ORDER OF THE TWO MESSAGES IS A SOUNDNESS CONDITION.  The client first receives the rows
+# (FileHandler.read_rows_response) and only then draws the columns and asks for the openings
+# (FileHandler.read_opening_response).  A server that knows the columns before it sends the rows
+# can interpolate a wrong row that agrees with the committed one at every one of them.
+READ_COVER_CAP = 128   # cover nodes of any size_t chunk count
+
+
+@dataclass
+class ReadPlan:
+    """lcpc_pos_read_plan: the rows [row_lo, row_hi) that hold the byte range, the 1-KiB leaf chunks
+    [chunk_lo, chunk_hi) that hold those rows, the rows [seg_row_lo, seg_row_hi) of those chunks, and
+    the cover nodes (chunk lo, chunk hi) in walk order."""
+    row_lo: int
+    row_hi: int
+    chunk_lo: int
+    chunk_hi: int
+    seg_row_lo: int
+    seg_row_hi: int
+    cover_nodes: List[tuple]
+
+    @property
+    def n_cover(self) -> int:
+        return len(self.cover_nodes)
+
+
+@dataclass
+class ReadOpening:
+    """The server's second message: per requested column its segment (rows [seg_row_lo, seg_row_hi)
+    as canonical 8-byte values, the `.porenc`'s own bytes), its cover values and its Merkle path."""
+    segments: np.ndarray          # (n_columns, seg_rows) uint64, canonical
+    covers: np.ndarray            # (n_columns, n_cover, 32) uint8
+    paths: List[List[bytes]]      # per column log2(enc) digests
+
+    def n_bytes(self) -> int:
+        return int(np.asarray(self.segments).size * 8 + np.asarray(self.covers).size
+                   + sum(len(d) for p in self.paths for d in p))
+
+
+def read_plan(file_len: int, byte_start: int, byte_end: int, pre: int) -> ReadPlan:
+    """lcpc_pos_read_plan.  Host only."""
+    r = [C.c_size_t() for _ in range(7)]
+    nodes = (C.c_size_t * (2 * READ_COVER_CAP))()
+    _raise(N.load().lcpc_pos_read_plan(file_len, byte_start, byte_end, pre, *[C.byref(v) for v in r], nodes,
+                                       READ_COVER_CAP))
+    v = [x.value for x in r]
+    return ReadPlan(*v[:6], [(nodes[2 * j], nodes[2 * j + 1]) for j in range(v[6])])
+
+
+def _n_covers(rows_written: int, chunk_lo: int, chunk_hi: int) -> int:
+    """The cover count of a chunk range: the plan of a byte range that selects exactly those chunks."""
+    n_chunks = N.load().lcpc_leaf_n_chunks(FT63, rows_written)
+    first = N.load().lcpc_leaf_chunk_first_row(FT63, chunk_lo)
+    last = (rows_written if chunk_hi >= n_chunks else N.load().lcpc_leaf_chunk_first_row(FT63, chunk_hi)) - 1
+    return read_plan(7 * rows_written, 7 * first, 7 * last + 1, 1).n_cover
+
+
+def segment_covers_from_cache(cache, columns, chunk_lo: int, chunk_hi: int) -> np.ndarray:
+    """lcpc_pos_segment_covers_from_cache: (n_columns, n_cover, 32) cover values of the columns opened
+    on chunks [chunk_lo, chunk_hi), from a pos_files.ColumnChunkCache (left untouched)."""
+    idx = np.ascontiguousarray(list(columns), dtype=np.uint64)
+    out = np.zeros((idx.size, _n_covers(cache.rows, chunk_lo, chunk_hi), 32), np.uint8)
+    _raise(N.load().lcpc_pos_segment_covers_from_cache(cache._h, _p64(idx) if idx.size else None, idx.size,
+                                                       chunk_lo, chunk_hi, out.ctypes.data_as(N.u8p)))
+    return out
+
+
+def segment_covers_from_columns(cols, rows_written: int, chunk_lo: int, chunk_hi: int) -> np.ndarray:
+    """lcpc_pos_segment_covers_from_columns: the same bytes from the whole opened columns
+    ((n_columns, rows_written) canonical values) when the server keeps no cache."""
+    a = np.ascontiguousarray(cols, dtype=np.uint64).reshape(-1, rows_written)
+    out = np.zeros((a.shape[0], _n_covers(rows_written, chunk_lo, chunk_hi), 32), np.uint8)
+    _raise(N.load().lcpc_pos_segment_covers_from_columns(_p64(a), rows_written, a.shape[0], chunk_lo, chunk_hi,
+                                                         out.ctypes.data_as(N.u8p)))
+    return out
+
+
+def segment_leaves(segments, rows_written: int, chunk_lo: int, chunk_hi: int, covers, weights=None):
+    """lcpc_pos_segment_leaves: (leaves (n, 32) uint8, dots (n,) Montgomery limbs or None,
+    canonical_ok (n,) bool) for n segments (n, seg_rows) and their covers (n, n_cover, 32)."""
+    seg = np.ascontiguousarray(segments, dtype=np.uint64)
+    n = seg.shape[0]
+    seg = seg.reshape(n, -1)
+    cov = np.ascontiguousarray(covers, dtype=np.uint8).reshape(n, -1, 32)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint64).reshape(-1)
+    if w is not None and w.size != seg.shape[1]:
+        raise ValueError("one weight per segment row")
+    leaves = np.zeros((n, 32), np.uint8)
+    dots = None if w is None else np.zeros(n, np.uint64)
+    ok = np.zeros(n, np.uint8)
+    _raise(N.load().lcpc_pos_segment_leaves(
+        _p64(seg) if seg.size else None, n, rows_written, chunk_lo, chunk_hi,
+        cov.ctypes.data_as(N.u8p) if cov.size else None, cov.shape[1],
+        None if w is None else _p64(w), leaves.ctypes.data_as(N.u8p), None if dots is None else _p64(dots),
+        ok.ctypes.data_as(N.u8p)))
+    return leaves, dots, ok.astype(bool)
+
+
+def _verify_read(code: LigeroEncoding, root: bytes, file_len: int, byte_start: int, byte_end: int, data: bytes,
+                 columns, opening: ReadOpening, seed: Optional[int] = None) -> bytes:
+    """client_verify_read under a given encoding (its dims are the file's)."""
+    if code.digest != 0:
+        raise DeviceError(34, "a checkable read is BLAKE3-only; the encoding's digest is "
+                          f"{digest_name(code.digest)}")   # LCPC_ERR_UNSUPPORTED, as the other stored-file entries
+    pre, enc = code.n_per_row, code.n_cols
+    plan = read_plan(file_len, byte_start, byte_end, pre)
+    cols = [int(c) for c in columns]
+    if any(b <= a for a, b in zip(cols, cols[1:])) or any(not 0 <= c < enc for c in cols):
+        raise ValueError("requested columns must be strictly increasing and below enc")
+    rb = pre * DATA_BYTE_CAPACITY
+    rows_written = _file_rows(file_len, pre)
+    data = bytes(data)
+    lo_byte = plan.row_lo * rb
+    if len(data) != min(plan.row_hi * rb, file_len) - lo_byte:
+        raise _verifier_error("ColumnEval", "data is not the whole rows that cover the range")
+    n, seg_rows = len(cols), plan.seg_row_hi - plan.seg_row_lo
+    seg = np.asarray(opening.segments)
+    cov = np.asarray(opening.covers)
+    if seg.dtype != np.uint64 or seg.shape != (n, seg_rows):
+        raise _verifier_error("ColumnEval", "segments are not one per column of the chunk range's rows")
+    if cov.dtype != np.uint8 or cov.shape != (n, plan.n_cover, 32):
+        raise _verifier_error("ColumnEval", "cover count")
+    if len(opening.paths) != n:
+        raise _verifier_error("ColumnEval", "path count")
+    if n == 0:
+        return data[byte_start - lo_byte:byte_end - lo_byte]
+    # a private u over the rows read; the segment's other rows are only hashed (weight zero)
+    n_rows = plan.row_hi - plan.row_lo
+    if seed is None:
+        import secrets
+        u = np.array([secrets.randbelow(FT63_MODULUS) for _ in range(n_rows)], np.uint64)
+    else:
+        u = np.random.default_rng(seed).integers(0, FT63_MODULUS, n_rows, dtype=np.uint64)
+    weights = np.zeros(seg_rows, np.uint64)
+    weights[plan.row_lo - plan.seg_row_lo:plan.row_hi - plan.seg_row_lo] = u
+    # (1) canonical elements and (2) the rebuilt leaves reach the root
+    leaves, dots, ok = segment_leaves(seg, rows_written, plan.chunk_lo, plan.chunk_hi, cov, weights)
+    if not ok.all():
+        raise _verifier_error("ColumnEval", "a segment element is not canonical")
+    client_online_verify_column_paths_without_full_columns(root, cols, [leaves[k].tobytes() for k in range(n)],
+                                                           opening.paths)
+    # (3) Enc(u^T M) over the received bytes agrees with u^T segment at every opened column
+    row = np.zeros((enc, 1), np.uint64)
+    row[:pre] = left_multiply_unencoded_matrix_by_vector(data, pre, u)
+    encoded = code.encode(row).reshape(-1)
+    if not np.array_equal(encoded[np.array(cols, dtype=np.int64)], dots):
+        raise _verifier_error("ReadMismatch", "the rows received are not the rows the opened columns commit to")
+    return data[byte_start - lo_byte:byte_end - lo_byte]
+
+
+def client_verify_read(root: bytes, file_len: int, pre: int, enc: int, byte_start: int, byte_end: int, data: bytes,
+                       columns, opening: ReadOpening, seed: Optional[int] = None) -> bytes:
+    """Accepts bytes [byte_start, byte_end) of the file committed as root (file_len bytes, dims pre /
+    enc) and returns exactly them, or raises.  data: the server's first message, the whole rows that
+    cover the range; columns: the indices the client drew AFTER it held data (strictly increasing,
+    below enc; get_PoS_soudness_n_cols(pre, enc) of them for the full soundness) -- a server that
+    learns them before it sends data can forge a row that passes; opening: its second message.
+
+    Checks: every segment element is canonical; each leaf rebuilt from segment and covers hashes up
+    its path to root; and with a private random u over the rows read (secrets; `seed` only for tests),
+    Enc(u^T data)[j] = sum_r u_r segment_j[r] at every opened column j.  Wrong lengths, a wrong cover
+    count, a non-canonical element or a leaf that does not reach root raise VerifierError(ColumnEval);
+    rows that disagree with the openings raise VerifierError(ReadMismatch)."""
+    return _verify_read(LigeroEncoding.new_from_dims(FT63, pre, enc), root, file_len, byte_start, byte_end, data,
+                        columns, opening, seed)

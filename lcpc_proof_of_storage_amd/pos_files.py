@@ -1190,6 +1190,52 @@ class FileHandler:
                 for c in self.read_full_columns(columns)]
         return result, cols
 
+    # -- checkable reads (pos.client_verify_read)
+    def _read_plan(self, byte_start: int, byte_end: int):
+        from .pos import read_plan
+        return read_plan(self.total_data_bytes, byte_start, byte_end, self.pre_encoded_size)
+
+    def read_rows_response(self, byte_start: int, byte_end: int) -> bytes:
+        """The first message of a checkable read: the raw bytes of the whole rows that cover
+        [byte_start, byte_end), [row_lo * 7 pre, min(row_hi * 7 pre, file length)).  It is sent BEFORE
+        the client names any column: the order is what makes the read sound (pos.client_verify_read)."""
+        plan = self._read_plan(byte_start, byte_end)
+        rb = self._row_bytes()
+        return self.get_unencoded_bytes(plan.row_lo * rb, min(plan.row_hi * rb, self.total_data_bytes))
+
+    def _read_column_rows(self, f, column: int, row_lo: int, row_hi: int) -> np.ndarray:
+        """Rows [row_lo, row_hi) of one column: one positioned read of the column-major .porenc."""
+        want = (row_hi - row_lo) * WRITTEN_BYTES_WIDTH
+        b = os.pread(f.fileno(), want, (column * self.row_capacity + row_lo) * WRITTEN_BYTES_WIDTH)
+        if len(b) != want:
+            raise EOFError("encoded file shorter than its metadata says")
+        return np.frombuffer(b, "<u8").astype(np.uint64)
+
+    def read_opening_response(self, byte_start: int, byte_end: int, columns):
+        """The second message: a pos.ReadOpening of the requested columns (strictly increasing, below
+        encoded_size) on the leaf chunks that hold the rows of the range -- per column its elements
+        there (a contiguous read of the .porenc), the chaining values that cover the rest of the
+        column, and its Merkle path.  The cover values come from the chunk cache when the handler
+        has one (chunk_cache=True), else from the opened columns read whole; the bytes are the same."""
+        from .pos import ReadOpening, segment_covers_from_cache, segment_covers_from_columns
+        cols = [int(c) for c in columns]
+        if any(b <= a for a, b in zip(cols, cols[1:])) or any(not 0 <= c < self.encoded_size for c in cols):
+            raise IndexError("columns must be strictly increasing and below encoded_size")
+        plan = self._read_plan(byte_start, byte_end)
+        seg_rows = plan.seg_row_hi - plan.seg_row_lo
+        segments = np.zeros((len(cols), seg_rows), np.uint64)
+        with open(self.encoded_file_handle, "rb") as f:
+            for k, c in enumerate(cols):
+                segments[k] = self._read_column_rows(f, c, plan.seg_row_lo, plan.seg_row_hi)
+            if not cols or plan.n_cover == 0:
+                covers = np.zeros((len(cols), plan.n_cover, DIGEST_BYTES), np.uint8)
+            elif self.chunk_cache is not None:
+                covers = segment_covers_from_cache(self.chunk_cache, cols, plan.chunk_lo, plan.chunk_hi)
+            else:
+                whole = np.stack([self._read_column_rows(f, c, 0, self.rows_written) for c in cols])
+                covers = segment_covers_from_columns(whole, self.rows_written, plan.chunk_lo, plan.chunk_hi)
+        return ReadOpening(segments, covers, [self.merkle_tree.get_path(c) for c in cols])
+
     # -- re-encoding
     def _reencode_rows(self, row_lo: int, row_hi: int) -> None:
         """Rows [row_lo, row_hi) from the raw file into the .porenc (one batched GPU pass)."""
