@@ -38,7 +38,9 @@ extern "C" {
  * its signature and its BLAKE3 meaning.  So is the update-audit block (lcpc_eval_poly*,
  * lcpc_pos_eval_poly_bytes*, lcpc_pos_left_multiply_bytes*, lcpc_pos_update_rows,
  * lcpc_pos_update_evaluation).  So are the diagnostics added since (lcpc_selftest_field_op,
- * lcpc_selftest_recombine, lcpc_selftest_twiddle_words, lcpc_selftest_ntt_rows, lcpc_selftest_spmm, lcpc_selftest_reed_solomon). */
+ * lcpc_selftest_recombine, lcpc_selftest_twiddle_words, lcpc_selftest_ntt_rows, lcpc_selftest_spmm, lcpc_selftest_reed_solomon).
+ * So is the batched stored-file audit (lcpc_pos_left_multiply_bytes_many*, lcpc_pos_left_multiply_many_kernel,
+ * lcpc_selftest_recombine63). */
 #define LCPC_ABI_VERSION 3
 
 typedef enum lcpc_status {
@@ -547,6 +549,26 @@ lcpc_status lcpc_pos_left_multiply_bytes(const uint8_t *bytes, size_t n_bytes, s
                                          const uint64_t *left, size_t n_left, uint64_t *out);
 lcpc_status lcpc_pos_left_multiply_bytes_device(const void *d_bytes, size_t n_bytes, size_t pre,
                                                 const uint64_t *left, size_t n_left, uint64_t *out);
+/* The same for n_vecs vectors in one pass over the image (batched audits of a stored file: m
+ * evaluation points, one read of the file, one set of opened columns):
+ *   out[t pre + c] = sum_r lefts[t n_left + r] M[r][c],   1 <= n_vecs <= LCPC_BATCH_MAX_TENSORS,
+ * bit for bit n_vecs calls of lcpc_pos_left_multiply_bytes.  n_left must be the file's row count;
+ * argument rules and status codes are those of the single entry, reported before any device work
+ * (a NULL pointer, n_bytes or pre of 0, n_vecs outside its range, a wrong n_left, a device image
+ * that is not 8-byte aligned: LCPC_ERR_INVALID_ARG; no device: LCPC_ERR_NO_DEVICE).
+ * The host entry takes bytes of any alignment: the image goes up once, in blocks of whole rows near
+ * 8 MiB, each block contracted as it lands and the blocks' partial sums folded at the end. */
+lcpc_status lcpc_pos_left_multiply_bytes_many(const uint8_t *bytes, size_t n_bytes, size_t pre,
+                                              const uint64_t *lefts, size_t n_vecs, size_t n_left, uint64_t *out);
+lcpc_status lcpc_pos_left_multiply_bytes_many_device(const void *d_bytes, size_t n_bytes, size_t pre,
+                                                     const uint64_t *lefts, size_t n_vecs, size_t n_left,
+                                                     uint64_t *out);
+/* The kernel the two entries above run for (pre, n_vecs), a pure function of its arguments and of
+ * LCPC_NO_MFMA (read once per process).  0: pre is no power of two >= 8 -- the image is packed to
+ * elements first, then lcpc_collapse_columns_many's kernel;  1: the VALU kernel on the bytes
+ * (pre < 64, fewer than 16 vectors, LCPC_NO_MFMA=1);  2: the int8 matrix cores on the bytes (pre >= 64
+ * and at least 16 vectors, where they measured faster).  No device needed. */
+int lcpc_pos_left_multiply_many_kernel(size_t pre, size_t n_vecs);
 /* Host-only, no device (like lcpc_pos_update_chunk_range): the rows an update touches.  The
  * reference's edit and append handlers (networking/server.rs:963-1077) each pick their "original
  * rows" differently and disagree with their clients; this is the one rule that replaces them.
@@ -1109,6 +1131,11 @@ lcpc_status lcpc_selftest_field_op(lcpc_field f, int op, int k, const uint64_t *
  * (sum_u y_u 2^(8u)) R^-1 mod p, fully reduced, for |y_u| < 2^27.  NULL y or out:
  * LCPC_ERR_INVALID_ARG. */
 lcpc_status lcpc_selftest_recombine(const int32_t *y, uint64_t *out, size_t n);
+
+/* out[i] (an Ft63 element) = recombine_redc63 (csrc/pos_eval_mfma.hpp) of the 8 digit-position
+ * accumulators y[8 i ..]: (sum_u y_u 2^(8u)) R^-1 mod p, fully reduced, for |y_u| <= 2^26.  NULL y or
+ * out: LCPC_ERR_INVALID_ARG. */
+lcpc_status lcpc_selftest_recombine63(const int32_t *y, uint64_t *out, size_t n);
 
 /* The word-expanded table entries the Ft127 encode passes multiply by (csrc/field.hpp, fe_mul_tw):
  * for each of the n Montgomery values tw[i] = w R mod p (< p), out holds 2 limbs elements,

@@ -188,6 +188,9 @@ SIGNATURES = {
     "lcpc_pos_eval_poly_bytes_device": (i32, [vp, sz, u64p, C.c_uint64, u64p]),
     "lcpc_pos_left_multiply_bytes": (i32, [vp, sz, sz, u64p, sz, u64p]),
     "lcpc_pos_left_multiply_bytes_device": (i32, [vp, sz, sz, u64p, sz, u64p]),
+    "lcpc_pos_left_multiply_bytes_many": (i32, [vp, sz, sz, u64p, sz, sz, u64p]),
+    "lcpc_pos_left_multiply_bytes_many_device": (i32, [vp, sz, sz, u64p, sz, sz, u64p]),
+    "lcpc_pos_left_multiply_many_kernel": (C.c_int, [sz, sz]),
     "lcpc_pos_update_rows": (i32, [sz, sz, sz, sz, szp, szp, szp, szp]),
     "lcpc_pos_update_evaluation": (i32, [vp, vp, sz, vp, vp, sz, u64p, u64p, sz, u64p, sz,
                                          u64p, u64p, u8p, u8p, u64p, u64p, u8p, u8p, u64p]),
@@ -282,6 +285,7 @@ SIGNATURES = {
     "lcpc_selftest_fe_dot_kmax": (i32, [i32]),
     "lcpc_selftest_field_op": (i32, [i32, i32, i32, u64p, u64p, u64p, sz]),
     "lcpc_selftest_recombine": (i32, [C.POINTER(C.c_int32), u64p, sz]),
+    "lcpc_selftest_recombine63": (i32, [C.POINTER(C.c_int32), u64p, sz]),
     "lcpc_selftest_twiddle_words": (i32, [i32, u64p, u64p, sz]),
     "lcpc_selftest_ntt_rows": (i32, [i32, i32, i32, u64p, sz, sz, u64p, sz, sz, u64p, sz, i32]),
     "lcpc_selftest_spmm": (i32, [i32, sz, sz, u32p, u32p, u64p, u64p, u64p, sz, sz, sz, i32, C.POINTER(C.c_int)]),

@@ -1758,6 +1758,75 @@ lcpc_status left_multiply_dev(Device *dev, hipStream_t s, const uint8_t *d_bytes
   return LCPC_OK;
 }
 
+// ---- many vectors, one pass over the image (batched audits of a stored file)
+static_assert(LCPC_BATCH_MAX_TENSORS == POS_LEFT_MANY_MAX_VECS, "header bound = kernel bound");
+
+lcpc_status left_multiply_many_args(const void *bytes, size_t n_bytes, size_t pre, const uint64_t *lefts, size_t n_vecs,
+                                    size_t n_left, uint64_t *out) {
+  if (!bytes || !n_bytes || !pre || !lefts || !out) return fail(LCPC_ERR_INVALID_ARG, "null or empty argument");
+  if (n_vecs == 0 || n_vecs > LCPC_BATCH_MAX_TENSORS)
+    return fail(LCPC_ERR_INVALID_ARG, "n_vecs must be in [1, LCPC_BATCH_MAX_TENSORS]");
+  const size_t len = (n_bytes + 6) / 7, n_rows = (len + pre - 1) / pre;
+  if (n_left != n_rows) return fail(LCPC_ERR_INVALID_ARG, "left vector length != the file's row count");
+  return LCPC_OK;
+}
+
+// the state of one many-vector product: the vectors and the kernel's tables on the device, then
+// piece(...) for every run of whole rows of the image, in order, then finish()
+struct LeftMany {
+  Device *dev;
+  hipStream_t s;
+  size_t n_bytes, pre, n_vecs, n_rows, piece_rows;
+  int kernel;
+  DBuf dl, prep, partials, dout;
+  size_t splits_done = 0;
+
+  // piece_rows: the rows per piece of a staged image (even), 0 = the whole image in one piece
+  lcpc_status begin(const uint64_t *lefts, size_t rows_per_piece) {
+    n_rows = ((n_bytes + 6) / 7 + pre - 1) / pre;
+    piece_rows = rows_per_piece ? rows_per_piece : n_rows;
+    kernel = pos_left_mul_many_kernel(pre, n_vecs);
+    lcpc_status st;
+    if ((st = upload(dev, dl, lefts, n_vecs * n_rows * 8))) return st;
+    HIP_TRY(dout.alloc(dev, n_vecs * pre * 8));
+    if (kernel == POS_LEFT_MANY_PACK) return LCPC_OK;
+    const size_t full = n_rows / piece_rows, rest = n_rows % piece_rows;
+    const size_t splits = full * pos_left_mul_many_splits(kernel, pre, piece_rows, n_vecs) +
+                          (rest ? pos_left_mul_many_splits(kernel, pre, rest, n_vecs) : 0);
+    HIP_TRY(partials.alloc(dev, splits * n_vecs * pre * 8));
+    HIP_TRY(prep.alloc(dev, std::max<size_t>(pos_left_mul_many_prep_bytes(kernel, n_rows, n_vecs), 8)));
+    HIP_TRY(pos_left_mul_many_prepare(kernel, dl.as<uint32_t>(), n_rows, n_vecs, prep.p, s));
+    return LCPC_OK;
+  }
+  // rows [row0, row0 + rows) of the image at d_piece (bytes: to the image's end at most)
+  lcpc_status piece(const uint8_t *d_piece, size_t bytes, size_t row0, size_t rows) {
+    HIP_TRY(pos_left_mul_many_partials(kernel, d_piece, bytes, pre, rows, row0, dl.as<uint32_t>(), n_rows, n_vecs,
+                                       prep.p, partials.as<uint32_t>() + 2 * splits_done * n_vecs * pre, s));
+    splits_done += pos_left_mul_many_splits(kernel, pre, rows, n_vecs);
+    return LCPC_OK;
+  }
+  // other widths: the element image (zero padded to whole rows), then the commitment's many-tensor collapse
+  lcpc_status pack_first(const uint8_t *d_bytes) {
+    const size_t len = (n_bytes + 6) / 7;
+    DBuf m, scratch;
+    HIP_TRY(m.alloc(dev, n_rows * pre * 8));
+    if (n_rows * pre > len) HIP_TRY(hipMemsetAsync(m.as<uint64_t>() + len, 0, (n_rows * pre - len) * 8, s));
+    HIP_TRY(pos_pack7(d_bytes, n_bytes, m.as<uint64_t>(), s));
+    HIP_TRY(scratch.alloc(dev, collapse_many_scratch_bytes(LCPC_FT63, n_rows, pre, n_vecs)));
+    HIP_TRY(collapse_rows_many(LCPC_FT63, m.as<uint32_t>(), n_rows, pre, dl.as<uint32_t>(), n_vecs, dout.as<uint32_t>(),
+                               scratch.p, s));
+    return LCPC_OK;
+  }
+  lcpc_status finish(uint64_t *out) {
+    if (kernel != POS_LEFT_MANY_PACK)
+      HIP_TRY(pos_left_mul_many_fold(kernel, partials.as<uint32_t>(), splits_done, pre, n_rows, n_vecs, prep.p,
+                                     dout.as<uint32_t>(), s));
+    HIP_TRY(hipMemcpyAsync(out, dout.p, n_vecs * pre * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return LCPC_OK;
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -1860,6 +1929,73 @@ lcpc_status lcpc_pos_left_multiply_bytes(const uint8_t *bytes, size_t n_bytes, s
                   [](size_t, size_t) { return LCPC_OK; });
   if (st) return st;
   return left_multiply_dev(dev, lease.s, image.as<uint8_t>(), n_bytes, pre, left, n_left, out);
+}
+
+int lcpc_pos_left_multiply_many_kernel(size_t pre, size_t n_vecs) { return pos_left_mul_many_kernel(pre, n_vecs); }
+
+lcpc_status lcpc_pos_left_multiply_bytes_many_device(const void *d_bytes, size_t n_bytes, size_t pre,
+                                                     const uint64_t *lefts, size_t n_vecs, size_t n_left,
+                                                     uint64_t *out) {
+  lcpc_status st = left_multiply_many_args(d_bytes, n_bytes, pre, lefts, n_vecs, n_left, out);
+  if (st) return st;
+  if ((uintptr_t)d_bytes & 7) return fail(LCPC_ERR_INVALID_ARG, "device file image must be 8-byte aligned");
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  LeftMany lm{dev, lease.s, n_bytes, pre, n_vecs};
+  if ((st = lm.begin(lefts, 0))) return st;
+  if (lm.kernel == POS_LEFT_MANY_PACK)
+    st = lm.pack_first((const uint8_t *)d_bytes);
+  else
+    st = lm.piece((const uint8_t *)d_bytes, n_bytes, 0, lm.n_rows);
+  return st ? st : lm.finish(out);
+}
+
+lcpc_status lcpc_pos_left_multiply_bytes_many(const uint8_t *bytes, size_t n_bytes, size_t pre, const uint64_t *lefts,
+                                              size_t n_vecs, size_t n_left, uint64_t *out) {
+  lcpc_status st = left_multiply_many_args(bytes, n_bytes, pre, lefts, n_vecs, n_left, out);
+  if (st) return st;
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  // The image goes up in staging blocks of whole rows (an even number of them, near 8 MiB); block
+  // b's rows are contracted as soon as they have landed, one set of partials per block, and the
+  // partials are folded at the end: field sums are exact, so the blocks do not show in the result.
+  const size_t row_b = 7 * pre;
+  const size_t block_rows = std::max<size_t>(2, (((size_t)8 << 20) / row_b) & ~(size_t)1);
+  LeftMany lm{dev, lease.s, n_bytes, pre, n_vecs};
+  DBuf image;
+  HIP_TRY(image.alloc(dev, n_bytes));
+  if ((st = lm.begin(lefts, block_rows))) return st;
+  const bool pack = lm.kernel == POS_LEFT_MANY_PACK;
+  st = h2d_blocks(dev, image.as<uint8_t>(), bytes, n_bytes, block_rows * row_b, lease.s,
+                  [&](size_t off, size_t n) -> lcpc_status {
+    if (pack) return LCPC_OK;
+    const size_t r0 = off / row_b;
+    return lm.piece(image.as<uint8_t>() + off, n, r0, std::min(block_rows, lm.n_rows - r0));
+  });
+  if (st) return st;
+  if (pack && (st = lm.pack_first(image.as<uint8_t>()))) return st;
+  return lm.finish(out);
+}
+
+lcpc_status lcpc_selftest_recombine63(const int32_t *y, uint64_t *out, size_t n) {
+  if (!y || !out) return fail(LCPC_ERR_INVALID_ARG, "null accumulators or output");
+  lcpc_status st;
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  if (!n) return LCPC_OK;
+  Lease lease(dev);
+  HIP_TRY(hipSetDevice(dev->id));
+  DBuf dy, dout;
+  if ((st = upload(dev, dy, y, n * 8 * sizeof(int32_t)))) return st;
+  HIP_TRY(dout.alloc(dev, n * 8));
+  HIP_TRY(pos_recombine63(dy.as<int>(), dout.as<uint32_t>(), n, lease.s));
+  HIP_TRY(hipMemcpyAsync(out, dout.p, n * 8, hipMemcpyDeviceToHost, lease.s));
+  HIP_TRY(hipStreamSynchronize(lease.s));
+  return LCPC_OK;
 }
 
 lcpc_status lcpc_pos_update_rows(size_t old_len, size_t offset, size_t len, size_t pre, size_t *row_lo, size_t *row_hi,

@@ -38,4 +38,29 @@ size_t pos_left_mul_bytes_scratch_bytes(size_t pre, size_t n_rows);
 hipError_t pos_left_mul_bytes(const uint8_t *bytes, size_t n_bytes, size_t pre, size_t n_rows, const uint32_t *left,
                               uint32_t *out, void *scratch, hipStream_t s);
 
+// ---- many vectors in one pass (batched audits of a stored file)
+// out[t pre + c] = sum_r lefts[t n_rows + r] * M[r][c], 1 <= n_vecs <= POS_LEFT_MANY_MAX_VECS, bit
+// for bit n_vecs calls of pos_left_mul_bytes.  The kernel is a function of (pre, n_vecs) and
+// LCPC_NO_MFMA: POS_LEFT_MANY_PACK (pre no power of two >= 8: the caller packs the image and runs
+// collapse_rows_many), _VALU (k_left_mul_bytes_many) or _MFMA (pos_eval_mfma.hpp).
+// A caller runs prepare once (the matrix-core kernel's digit table and correction, in prep), then
+// partials for every piece of whole rows of the image as it becomes available (row_base even, the
+// piece's partials after those of the pieces before it: pos_left_mul_many_splits sets each), then fold.
+constexpr int POS_LEFT_MANY_PACK = 0, POS_LEFT_MANY_VALU = 1, POS_LEFT_MANY_MFMA = 2;
+constexpr size_t POS_LEFT_MANY_MAX_VECS = 4096;  // == LCPC_BATCH_MAX_TENSORS
+// (the adoption measurement of DESIGN §5f: at the 1 GiB default dims the matrix cores win from 16 vectors on)
+constexpr size_t POS_LEFT_MANY_MFMA_MIN_VECS = 16;
+int pos_left_mul_many_kernel(size_t pre, size_t n_vecs);
+size_t pos_left_mul_many_splits(int kernel, size_t pre, size_t n_rows, size_t n_vecs);
+size_t pos_left_mul_many_prep_bytes(int kernel, size_t n_rows, size_t n_vecs);
+hipError_t pos_left_mul_many_prepare(int kernel, const uint32_t *lefts, size_t n_rows, size_t n_vecs, void *prep,
+                                     hipStream_t s);
+hipError_t pos_left_mul_many_partials(int kernel, const uint8_t *bytes, size_t n_bytes, size_t pre, size_t n_rows,
+                                      size_t row_base, const uint32_t *lefts, size_t n_rows_total, size_t n_vecs,
+                                      const void *prep, uint32_t *partials, hipStream_t s);
+hipError_t pos_left_mul_many_fold(int kernel, const uint32_t *partials, size_t n_split, size_t pre, size_t n_rows_total,
+                                  size_t n_vecs, const void *prep, uint32_t *out, hipStream_t s);
+// out[i] = recombine_redc63 of the 8 accumulators y[8 i ..] (selftest)
+hipError_t pos_recombine63(const int *y, uint32_t *out, size_t n, hipStream_t s);
+
 }  // namespace lcpc

@@ -6,6 +6,9 @@
 //                     power vector and no element image in memory.
 //   k_left_mul_bytes  left_multiply_unencoded_matrix_by_vector (file_handler.rs:614-638): u^T M
 //                     straight from the file image.
+//   k_left_mul_bytes_many / pmfma::k_left_mul_mfma   the same for many vectors in one pass over the
+//                     image (batched audits): TT accumulator sets per thread on the
+//                     VALU, or the int8 matrix cores (pos_eval_mfma.hpp).
 //
 // All arithmetic is exact field arithmetic on Montgomery words (a packed byte element is its raw
 // limb, as everywhere on the proof-of-storage path), so the order of summation does not show.
@@ -28,6 +31,7 @@
 #include "kernels.hpp"
 #include "pos.hpp"
 #include "pos_bytes.hpp"
+#include "pos_eval_mfma.hpp"
 #include "prof.hpp"
 
 namespace lcpc {
@@ -184,10 +188,154 @@ __global__ __launch_bounds__(256) void k_left_mul_bytes(const uint8_t *__restric
 
 inline size_t ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }
 
+// k_left_mul_bytes for many vectors: blockIdx.y = a chunk of TT vectors, each with its own
+// accumulators, so a run of the image is loaded once per chunk.  lefts[t left_stride + r];
+// partial[(y n_vecs + t) pre + 8g + k].  A short last chunk computes on clamped vector indices and
+// stores only the vectors that exist.
+constexpr int LEFT_MANY_TT = 4;
+
+template <class F, int TT>
+__global__ __launch_bounds__(256) void k_left_mul_bytes_many(const uint8_t *__restrict__ bytes, size_t n_bytes,
+                                                             size_t pre, size_t n_rows, size_t rows_per,
+                                                             size_t n_split, const uint32_t *__restrict__ lefts,
+                                                             size_t left_stride, size_t n_vecs,
+                                                             uint32_t *__restrict__ partials) {
+  static_assert(F::N == 2, "a file image holds WriteableFt63 elements");
+  constexpr int K = fe_dot_kmax<F>() < 2 ? fe_dot_kmax<F>() : 2;
+  const size_t n_runs = pre / 8;
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t g = t % n_runs, y = t / n_runs;
+  if (y >= n_split) return;
+  const size_t t0 = (size_t)blockIdx.y * TT;
+  const size_t r0 = y * rows_per, r1 = r0 + rows_per < n_rows ? r0 + rows_per : n_rows;
+  const size_t row_b = 7 * pre;
+  const uint32_t *lv[TT];
+#pragma unroll
+  for (int v = 0; v < TT; v++) lv[v] = lefts + 2 * (t0 + v < n_vecs ? t0 + v : n_vecs - 1) * left_stride;
+  Fe<F> acc[TT][8];
+#pragma unroll
+  for (int v = 0; v < TT; v++)
+#pragma unroll
+    for (int k = 0; k < 8; k++) acc[v][k] = fe_zero<F>();
+  size_t r = r0;
+  for (; r + K <= r1; r += K) {
+    uint64_t q[K][7];
+    Fe<F> a[TT][K];
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      pack7_load_run(bytes, n_bytes, (r + j) * row_b + 56 * g, q[j]);
+#pragma unroll
+      for (int v = 0; v < TT; v++) a[v][j] = fe_load<F>(lv[v], r + j);
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      Fe<F> b[K];
+#pragma unroll
+      for (int j = 0; j < K; j++) {
+        const uint64_t e = pack7_elem(q[j], k);
+        b[j].v[0] = (uint32_t)e;
+        b[j].v[1] = (uint32_t)(e >> 32);
+      }
+#pragma unroll
+      for (int v = 0; v < TT; v++) acc[v][k] = fe_add<F>(acc[v][k], fe_dot<F, K>(a[v], b));
+    }
+  }
+  for (; r < r1; r++) {
+    uint64_t q[7];
+    pack7_load_run(bytes, n_bytes, r * row_b + 56 * g, q);
+    Fe<F> a[TT];
+#pragma unroll
+    for (int v = 0; v < TT; v++) a[v] = fe_load<F>(lv[v], r);
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const uint64_t e = pack7_elem(q, k);
+      Fe<F> b;
+      b.v[0] = (uint32_t)e;
+      b.v[1] = (uint32_t)(e >> 32);
+#pragma unroll
+      for (int v = 0; v < TT; v++) acc[v][k] = fe_add<F>(acc[v][k], fe_mul<F>(a[v], b));
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < TT; v++)
+    if (t0 + v < n_vecs)
+#pragma unroll
+      for (int k = 0; k < 8; k++) fe_store<F>(partials, (y * n_vecs + t0 + v) * pre + 8 * g + k, acc[v][k]);
+}
+
+// corr[t] = (sum_r lefts[t left_stride + r]) * C128, the file digits' shift of the matrix-core
+// kernel (pos_eval_mfma.hpp); one block of 256 threads per vector
+template <class F>
+__global__ __launch_bounds__(256) void k_left_many_corr(const uint32_t *__restrict__ lefts, size_t left_stride,
+                                                        size_t n_rows, uint32_t *__restrict__ corr) {
+  __shared__ __align__(16) uint32_t s_w[256 * F::N];
+  const int tid = threadIdx.x;
+  const size_t t = blockIdx.x;
+  Fe<F> v = fe_zero<F>();
+  for (size_t r = tid; r < n_rows; r += 256) v = fe_add<F>(v, fe_load<F>(lefts, t * left_stride + r));
+  fe_store<F>(s_w, tid, v);
+  __syncthreads();
+  for (int o = 128; o >= 1; o >>= 1) {
+    if (tid < o) fe_store<F>(s_w, tid, fe_add<F>(fe_load<F>(s_w, tid), fe_load<F>(s_w, tid + o)));
+    __syncthreads();
+  }
+  if (tid == 0) {
+    Fe<F> c;
+    c.v[0] = (uint32_t)pmfma::C128;
+    c.v[1] = (uint32_t)(pmfma::C128 >> 32);
+    fe_store<F>(corr, t, fe_mul<F>(fe_load<F>(s_w, 0), c));
+  }
+}
+
+// out[t pre + c] = sum_y partials[(y n_vecs + t) pre + c] (+ corr[t]); blockIdx.y = t
+template <class F>
+__global__ __launch_bounds__(256) void k_left_many_fold(const uint32_t *__restrict__ partials, size_t n_split,
+                                                        size_t pre, size_t n_vecs, const uint32_t *__restrict__ corr,
+                                                        uint32_t *__restrict__ out) {
+  const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x, t = blockIdx.y;
+  if (c >= pre) return;
+  Fe<F> v = corr ? fe_load<F>(corr, t) : fe_zero<F>();
+  for (size_t y = 0; y < n_split; y++) v = fe_add<F>(v, fe_load<F>(partials, (y * n_vecs + t) * pre + c));
+  fe_store<F>(out, t * pre + c, v);
+}
+
+__global__ __launch_bounds__(256) void k_recombine63(const int *__restrict__ y, uint32_t *__restrict__ out, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int Y[8];
+#pragma unroll
+  for (int u = 0; u < 8; u++) Y[u] = y[i * 8 + u];
+  fe_store<Ft63>(out, i, pmfma::recombine_redc63<Ft63>(Y));
+}
+
+
 // the row split of k_left_mul_bytes: enough threads to fill the device, each with whole rows and
 // at least 8 of them (a few lazy reductions per partial it writes)
 inline void left_mul_split(size_t pre, size_t n_rows, size_t *rows_per, size_t *n_split) {
   const size_t n_runs = pre / 8, want = ceil_div((size_t)1 << 18, n_runs);
+  *rows_per = std::min(n_rows, std::max<size_t>(ceil_div(n_rows, want), 8));
+  *n_split = ceil_div(n_rows, *rows_per);
+}
+
+
+constexpr int MFMA_TP = 8;  // vector pairs per chunk of the matrix-core kernel: 16 vectors
+
+// the row split of the many-vector kernels over n_rows rows of one image piece
+//   VALU: left_mul_split with the chunks counted into the threads in flight;
+//   matrix cores: splits of at most MAX_SPLIT_ROWS rows, a multiple of the K step, halved while the
+//   launch has fewer than 2048 waves and a split keeps at least 128 KiB of image (below that its
+//   partials and their fold cost more than its waves add)
+inline void left_many_split(int kernel, size_t pre, size_t n_rows, size_t n_vecs, size_t *rows_per, size_t *n_split) {
+  if (kernel == POS_LEFT_MANY_MFMA) {
+    const size_t waves = pre / pmfma::COLS_PER_WAVE * ceil_div(n_vecs, 2 * MFMA_TP);
+    size_t rp = pmfma::MAX_SPLIT_ROWS;
+    while (rp > pmfma::STEP_ROWS && ceil_div(n_rows, rp) * waves < 2048 && rp / 2 * 7 * pre >= ((size_t)128 << 10))
+      rp /= 2;
+    *rows_per = rp;
+    *n_split = ceil_div(n_rows, rp);
+    return;
+  }
+  const size_t n_runs = pre / 8, want = ceil_div((size_t)1 << 18, n_runs * ceil_div(n_vecs, LEFT_MANY_TT));
   *rows_per = std::min(n_rows, std::max<size_t>(ceil_div(n_rows, want), 8));
   *n_split = ceil_div(n_rows, *rows_per);
 }
@@ -272,6 +420,86 @@ hipError_t pos_left_mul_bytes(const uint8_t *bytes, size_t n_bytes, size_t pre, 
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || n_split == 1) return e;
   return collapse_fold_rows(0, partials, n_split, pre, out, s);
+}
+
+// The matrix-core kernel from POS_LEFT_MANY_MFMA_MIN_VECS vectors on (the adoption measurement of
+// DESIGN §5f); pre below one wave's 64 columns and LCPC_NO_MFMA=1 stay on the VALU kernel.
+int pos_left_mul_many_kernel(size_t pre, size_t n_vecs) {
+  if (!pos_left_mul_bytes_ok(pre)) return POS_LEFT_MANY_PACK;
+  if (!no_mfma() && pre >= (size_t)pmfma::COLS_PER_WAVE && n_vecs >= POS_LEFT_MANY_MFMA_MIN_VECS)
+    return POS_LEFT_MANY_MFMA;
+  return POS_LEFT_MANY_VALU;
+}
+
+size_t pos_left_mul_many_splits(int kernel, size_t pre, size_t n_rows, size_t n_vecs) {
+  size_t rows_per, n_split;
+  left_many_split(kernel, pre, n_rows, n_vecs, &rows_per, &n_split);
+  return n_split;
+}
+
+size_t pos_left_mul_many_prep_bytes(int kernel, size_t n_rows, size_t n_vecs) {
+  if (kernel != POS_LEFT_MANY_MFMA) return 0;
+  return n_vecs * ((n_rows + 1) / 2) * 128 + n_vecs * 8;
+}
+
+hipError_t pos_left_mul_many_prepare(int kernel, const uint32_t *lefts, size_t n_rows, size_t n_vecs, void *prep,
+                                     hipStream_t s) {
+  if (kernel != POS_LEFT_MANY_MFMA) return hipSuccess;
+  using F = Ft63;
+  const size_t n_pairs = (n_rows + 1) / 2, nd = n_vecs * n_pairs * 16;
+  if (ceil_div(nd, 256) >= ((size_t)1 << 31)) return hipErrorInvalidValue;
+  prof::Scope ps("pos_left_mul_many_prepare", s);
+  uint8_t *hdig = static_cast<uint8_t *>(prep);
+  uint32_t *corr = reinterpret_cast<uint32_t *>(hdig + n_vecs * n_pairs * 128);
+  hipLaunchKernelGGL((pmfma::k_left_digits<F>), dim3((unsigned)ceil_div(nd, 256)), dim3(256), 0, s, lefts, n_rows,
+                     n_rows, n_pairs, n_vecs, hdig);
+  hipLaunchKernelGGL((k_left_many_corr<F>), dim3((unsigned)n_vecs), dim3(256), 0, s, lefts, n_rows, n_rows, corr);
+  return hipGetLastError();
+}
+
+hipError_t pos_left_mul_many_partials(int kernel, const uint8_t *bytes, size_t n_bytes, size_t pre, size_t n_rows,
+                                      size_t row_base, const uint32_t *lefts, size_t n_rows_total, size_t n_vecs,
+                                      const void *prep, uint32_t *partials, hipStream_t s) {
+  if (kernel == POS_LEFT_MANY_PACK || !pos_left_mul_bytes_ok(pre) || !n_rows || !n_vecs ||
+      n_vecs > POS_LEFT_MANY_MAX_VECS || row_base + n_rows > n_rows_total)
+    return hipErrorInvalidValue;
+  using F = Ft63;
+  prof::Scope ps("pos_left_mul_many", s);
+  size_t rows_per, n_split;
+  left_many_split(kernel, pre, n_rows, n_vecs, &rows_per, &n_split);
+  if (kernel == POS_LEFT_MANY_MFMA) {
+    if (pre < (size_t)pmfma::COLS_PER_WAVE || (row_base & 1) || n_split >= 65536) return hipErrorInvalidValue;
+    const size_t n_pairs = (n_rows_total + 1) / 2;
+    const uint4 *hd = static_cast<const uint4 *>(prep) + row_base / 2 * 8;
+    const dim3 grid((unsigned)ceil_div(pre, 4 * pmfma::COLS_PER_WAVE), (unsigned)n_split,
+                    (unsigned)ceil_div(n_vecs, 2 * MFMA_TP));
+    hipLaunchKernelGGL((pmfma::k_left_mul_mfma<F, MFMA_TP>), grid, dim3(256), 0, s, bytes, n_bytes, pre, n_rows, hd,
+                       n_pairs, n_vecs, partials, rows_per);
+    return hipGetLastError();
+  }
+  const size_t blocks = ceil_div(n_split * (pre / 8), 256);
+  if (blocks >= ((size_t)1 << 24)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((k_left_mul_bytes_many<F, LEFT_MANY_TT>),
+                     dim3((unsigned)blocks, (unsigned)ceil_div(n_vecs, LEFT_MANY_TT)), dim3(256), 0, s, bytes, n_bytes,
+                     pre, n_rows, rows_per, n_split, lefts + 2 * row_base, n_rows_total, n_vecs, partials);
+  return hipGetLastError();
+}
+
+hipError_t pos_left_mul_many_fold(int kernel, const uint32_t *partials, size_t n_split, size_t pre, size_t n_rows_total,
+                                  size_t n_vecs, const void *prep, uint32_t *out, hipStream_t s) {
+  prof::Scope ps("pos_left_mul_many_fold", s);
+  const uint32_t *corr = nullptr;
+  if (kernel == POS_LEFT_MANY_MFMA)
+    corr = reinterpret_cast<const uint32_t *>(static_cast<const uint8_t *>(prep) + n_vecs * ((n_rows_total + 1) / 2) * 128);
+  hipLaunchKernelGGL((k_left_many_fold<Ft63>), dim3((unsigned)ceil_div(pre, 256), (unsigned)n_vecs), dim3(256), 0, s,
+                     partials, n_split, pre, n_vecs, corr, out);
+  return hipGetLastError();
+}
+
+hipError_t pos_recombine63(const int *y, uint32_t *out, size_t n, hipStream_t s) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(k_recombine63, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, y, out, n);
+  return hipGetLastError();
 }
 
 }  // namespace lcpc

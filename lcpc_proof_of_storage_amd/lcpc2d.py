@@ -200,6 +200,15 @@ def selftest_recombine(y) -> np.ndarray:
     return out
 
 
+def selftest_recombine63(y) -> np.ndarray:
+    """recombine_redc63 of pos_eval_mfma.hpp per GPU thread (lcpc_selftest_recombine63): y is int32
+    of shape (n, 8), the digit-position accumulators; returns the n Ft63 words."""
+    y = np.ascontiguousarray(y, dtype=np.int32).reshape(-1, 8)
+    out = np.zeros(len(y), np.uint64)
+    _raise(N.load().lcpc_selftest_recombine63(y.ctypes.data_as(C.POINTER(C.c_int32)), _p64(out), len(y)))
+    return out
+
+
 def selftest_twiddle_words(field: int, tw) -> np.ndarray:
     """The word-expanded table entries of the Montgomery values tw (lcpc_selftest_twiddle_words,
     Ft127): for n values the (n, 2 limbs, limbs) words of w 2^(32 (j + 2)) mod p, j < 2 limbs."""

@@ -39,7 +39,7 @@ import numpy as np
 
 from . import _native as N
 from .lcpc2d import (FT63, VERIFIER, DeviceError, LcColumn, LcCommit, LigeroEncoding, ProverError, VerifierError,
-                     _p64, _raise, collapse_columns, digest_name, limbs, verify_column_path)
+                     _p64, _raise, collapse_columns, collapse_columns_many, digest_name, limbs, verify_column_path)
 
 WRITTEN_BYTES_WIDTH = 8   # size_of::<WriteableFt63>() (data_field.rs:24)
 DATA_BYTE_CAPACITY = 7    # CAPACITY / 8 (data_field.rs:22)
@@ -1048,3 +1048,83 @@ def client_verify_read(root: bytes, file_len: int, pre: int, enc: int, byte_star
     rows that disagree with the openings raise VerifierError(ReadMismatch)."""
     return _verify_read(LigeroEncoding.new_from_dims(FT63, pre, enc), root, file_len, byte_start, byte_end, data,
                         columns, opening, seed)
+
+
+# ---------------------------------------------------------------- batched audits of a stored file
+# m evaluation points, one pass over the raw file, one set of opened columns (DESIGN.md §5f).  No
+# counterpart in the reference, whose server answers one point per request.
+LEFT_MANY_PACK, LEFT_MANY_VALU, LEFT_MANY_MFMA = 0, 1, 2
+
+
+def left_multiply_many_kernel(pre_encoded_size: int, n_vecs: int) -> int:
+    """The kernel left_multiply_unencoded_matrix_by_vectors runs for this shape: LEFT_MANY_PACK (the
+    image is packed to elements first), LEFT_MANY_VALU or LEFT_MANY_MFMA (the int8 matrix cores).
+    A pure function of its arguments and LCPC_NO_MFMA; needs no device."""
+    return int(N.load().lcpc_pos_left_multiply_many_kernel(pre_encoded_size, n_vecs))
+
+
+def left_multiply_unencoded_matrix_by_vectors(data, pre_encoded_size: int, lefts) -> np.ndarray:
+    """left_multiply_unencoded_matrix_by_vector for m left vectors in one pass over the bytes
+    (lcpc_pos_left_multiply_bytes_many): lefts is (m, n_rows) Montgomery words, the result (m,
+    pre_encoded_size), row j bit for bit the single call's vector for lefts[j]."""
+    a = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.asarray(data, np.uint8)
+    n_rows = _file_rows(a.size, pre_encoded_size)
+    lv = np.ascontiguousarray(np.asarray(lefts, dtype=np.uint64))
+    lv = lv.reshape(lv.shape[0], -1) if lv.ndim > 1 else lv.reshape(1, -1)
+    if lv.shape[1] != n_rows:
+        raise ValueError(f"left vectors of incorrect size, expected {n_rows} and received {lv.shape[1]}")
+    out = np.zeros((lv.shape[0], pre_encoded_size), np.uint64)
+    _raise(N.load().lcpc_pos_left_multiply_bytes_many(a.ctypes.data, a.size, pre_encoded_size, _p64(lv.reshape(-1)),
+                                                      lv.shape[0], n_rows, _p64(out.reshape(-1))))
+    return out
+
+
+def client_verify_batch_evaluation(root: bytes, file_len: int, pre: int, enc: int, points, vectors, column_indices,
+                                   columns: Sequence[LcColumn]) -> np.ndarray:
+    """One audit of a stored file at m points: `vectors` (m, pre) are the server's unencoded vectors
+    v_j = left_j^T M (FileHandler.batch_evaluation_vectors), `columns` the opened columns with their
+    paths for `column_indices` (Montgomery limbs, as a commitment opens them).  Checks, as
+    _checked_file_evaluation does for one point: the indices are strictly increasing (ValueError),
+    every column has the file's row count, every path leads to root, every word of `vectors` is
+    below p, and Enc(v_j)[idx_k] == <left_j, col_k> for every (j, k) -- one encode of the m rows and
+    one many-tensor combination of the k columns.  Returns the m evaluations <v_j, right_j>, (m, 1);
+    raises VerifierError(ColumnEval) otherwise.
+
+    ORDER IS A SOUNDNESS CONDITION: the client must hold all m vectors before it reveals
+    column_indices.  A server that knows the k < pre columns it will be checked on can fit a false
+    vector to exactly those positions; fixed before the draw, a false v_j differs from the true one
+    in at least enc - pre + 1 positions of its encoding and survives the k openings with the
+    probability it has in a single audit.  The batch is no weaker than the weakest of its m single
+    audits (the stored-file form of lcpc_prove_batch absorbing every p_eval_j before the columns)."""
+    cols = [int(c) for c in column_indices]
+    if any(b <= a for a, b in zip(cols, cols[1:])):
+        raise ValueError("requested columns must be strictly increasing")
+    n_rows = _file_rows(file_len, pre)
+    if len(columns) != len(cols) or any(np.asarray(c.col).size != n_rows for c in columns):
+        raise _verifier_error("ColumnEval", "opened columns do not have the file's row count")
+    if any(not 0 <= c < enc for c in cols):
+        raise _verifier_error("ColumnEval", "column index outside the encoded row")
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.uint64)).reshape(-1)
+    m = pts.size
+    v = np.asarray(vectors, dtype=np.uint64)
+    if m == 0 or v.size != m * pre:
+        raise _verifier_error("ColumnEval", "vectors are not one unencoded row per point")
+    v = np.ascontiguousarray(v.reshape(m, pre))
+    if (v >= np.uint64(FT63_MODULUS)).any():
+        raise _verifier_error("ColumnEval", "vector word not below the modulus")
+    client_online_verify_column_paths(root, cols, columns)
+    sides = [form_side_vectors_for_polynomial_evaluation_from_point(pts[j:j + 1], n_rows, pre) for j in range(m)]
+    lefts = np.stack([l.reshape(-1) for l, _ in sides])
+    rights = np.stack([r.reshape(-1) for _, r in sides])
+    rows = np.zeros((m, enc, 1), np.uint64)
+    rows[:, :pre, 0] = v
+    encoded = LigeroEncoding.new_from_dims(FT63, pre, enc).encode_rows(rows).reshape(m, enc)
+    if cols:
+        opened = np.ascontiguousarray(np.stack([np.asarray(c.col, dtype=np.uint64).reshape(-1) for c in columns], axis=1))
+        dots = collapse_columns_many(FT63, opened, lefts, n_rows, len(cols)).reshape(m, len(cols))
+        if not np.array_equal(dots, encoded[:, cols]):
+            raise _verifier_error("ColumnEval", "column value mismatch")
+    # <v_j, right_j>: the diagonal of one many-tensor combination of the vectors against the rights
+    vals = collapse_columns_many(FT63, np.ascontiguousarray(v.T), rights, pre, m).reshape(m, m)
+    return np.ascontiguousarray(np.diagonal(vals)).reshape(m, 1)
+

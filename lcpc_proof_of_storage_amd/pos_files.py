@@ -1190,6 +1190,32 @@ class FileHandler:
                 for c in self.read_full_columns(columns)]
         return result, cols
 
+    # -- batched audits (pos.client_verify_batch_evaluation)
+    def batch_evaluation_vectors(self, points) -> np.ndarray:
+        """The first message of an audit at m points: the m unencoded vectors v_j = left_j^T M,
+        left_j = [1, x_j^pre, ...], as (m, pre) Montgomery words.  The raw file is read once and
+        contracted in one pass (lcpc_pos_left_multiply_bytes_many).  It is sent BEFORE the client
+        names any column: the order is what makes the batch sound (pos.client_verify_batch_evaluation).
+        With one point the vector is left_multiply_unencoded_matrix_by_vector's, and its encode is
+        polynomial_evaluation_response's result."""
+        from .pos import (form_side_vectors_for_polynomial_evaluation_from_point,
+                          left_multiply_unencoded_matrix_by_vectors)
+        pts = np.ascontiguousarray(np.asarray(points, dtype=np.uint64)).reshape(-1)
+        lefts = np.stack([form_side_vectors_for_polynomial_evaluation_from_point(
+            pts[j:j + 1], self.rows_written, self.pre_encoded_size)[0].reshape(-1) for j in range(pts.size)])
+        with open(self.unencoded_file_handle, "rb") as f:
+            data = f.read(self.total_data_bytes)
+        return left_multiply_unencoded_matrix_by_vectors(data, self.pre_encoded_size, lefts)
+
+    def batch_evaluation_columns(self, columns):
+        """The second message: read_full_columns(columns) with the values as a commitment opens them
+        (Montgomery limbs; the `.porenc` holds canonical ones), one set for all m points."""
+        from .lcpc2d import LcColumn
+        from .pos import FT63_MODULUS
+        return [LcColumn(np.array([(int(v) << 64) % FT63_MODULUS for v in np.asarray(c.col).reshape(-1)],
+                                  np.uint64).reshape(-1, 1), c.path)
+                for c in self.read_full_columns(columns)]
+
     # -- checkable reads (pos.client_verify_read; DESIGN.md §5e)
     def _read_plan(self, byte_start: int, byte_end: int):
         from .pos import read_plan
