@@ -17,7 +17,19 @@
  *   - handles may be used from several threads: each call leases a HIP stream from a
  *     per-device pool (commits / encodes, prove, and the latency-side calls each have their own
  *     pool; all streams run at one priority unless LCPC_PRIORITY_STREAMS=1), so independent
- *     calls, e.g. commitments of different objects, overlap on the device.
+ *     calls, e.g. commitments of different objects, overlap on the device.  That holds for the
+ *     handles a call only reads -- lcpc_encoding (the reference's rayon workers encode rows of
+ *     one encoding at once), lcpc_commit (prove, open_column) and the proof handles (verify) --
+ *     and for the stateless entry points.  tests/test_gpu_threads.py holds it up: 16 host threads
+ *     in one process on one encoding, one commitment and one proof handle and on the stored-file
+ *     entry points, every result compared with the CPU oracle, under the default stream mode and
+ *     LCPC_STREAM_MODE=serial; tests/cpp/test_pool_threads.cpp runs the device block cache's
+ *     ordering logic from 8 threads under ThreadSanitizer.
+ *     Handles that carry the state of a call in progress are NOT for concurrent use of one
+ *     instance (distinct instances are independent): lcpc_transcript (the sponge, or the caller's
+ *     callbacks), lcpc_column_digests and lcpc_pos_writer (rows and chaining values accumulated
+ *     between update / push calls), lcpc_pos_chunk_cache (its update entry points rewrite the
+ *     cached values in place), and lcpc_sharded_commit / lcpc_comm (one collective call at a time).
  * No torch / HIP types appear in the signatures; `void *stream` is an optional hipStream_t.
  */
 #ifndef LCPC_MI_H
@@ -297,8 +309,10 @@ void lcpc_transcript_challenge_bytes(lcpc_transcript *t, const uint8_t *label, s
  *   challenge_bytes(ctx, label, dest, n)     = Transcript::challenge_bytes
  * Labels are always one of "$l//DT", "$l//PR", "$l//PE", "$l//CO" (macros.rs:29-36), so a Rust
  * shim can map them back to its &'static [u8] constants.  Callbacks run on the calling thread,
- * inside the prove / verify call; 0 = success, anything else makes the call return
- * LCPC_ERR_TRANSCRIPT (a sharded prove still completes its exchanges first).  The handle holds no
+ * inside the prove / verify call, and the callbacks of one call are never concurrent -- also in
+ * lcpc_sharded_commit_prove_many, whose worker pool runs only the library's own transcripts
+ * (tests/test_gpu_transcript_ops.py records the thread of every callback); 0 = success,
+ * anything else makes the call return LCPC_ERR_TRANSCRIPT (a sharded prove still completes its exchanges first).  The handle holds no
  * transcript state of its own: lcpc_transcript_clone refuses it (NULL). */
 typedef struct lcpc_transcript_ops {
   void *ctx;

@@ -1626,8 +1626,9 @@ lcpc_status lcpc_sharded_commit_prove_many(const lcpc_encoding *e, const void *c
     for (auto &f : pending)
       if (f.valid()) f.wait();
     for (auto &f : finals) f.second.wait();  // (their tasks reset cs[k])
-    for (auto &c : cs)
-      if (c && c->next.valid()) c->next.wait();
+    for (auto &c : cs)  // (a deferred absorb of a caller-owned transcript is dropped, not run)
+      if (c && c->next.valid() && c->next.wait_for(std::chrono::seconds(0)) != std::future_status::deferred)
+        c->next.wait();
     {
       std::lock_guard<std::mutex> l2(err_mu);
       if (!err_msg.empty()) msg = err_msg;
@@ -1755,7 +1756,14 @@ lcpc_status lcpc_sharded_commit_prove_many(const lcpc_encoding *e, const void *c
           if ((s - S_R0) % 2 == 0) return stage_collapse(c, r);
           const lcpc_status s2 = stage_fold(c, r);
           if (s2) return s2;
-          if (c->me == c->root_rank) c->next = pool.submit([c, r] { return host_absorb(c, r); });
+          if (c->me != c->root_rank) return LCPC_OK;
+          // a caller-owned transcript's callbacks run on the thread that made this call, one at a
+          // time (lcpc_mi.h, lcpc_transcript_ops): deferred, the absorb runs inside the driver's
+          // c->next.get().  The library's own transcript keeps the worker pool.
+          if (c->tr->external)
+            c->next = std::async(std::launch::deferred, [c, r] { return host_absorb(c, r); });
+          else
+            c->next = pool.submit([c, r] { return host_absorb(c, r); });
           return LCPC_OK;
         }));
         if (s == S_COLS) to_finalize.push_back(k);

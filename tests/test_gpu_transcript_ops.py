@@ -9,6 +9,8 @@ the library's own transcript AND to the oracle's of_prove, and the caller's tran
 the state both of those reach (the challenge_bytes(b"after") check).
 """
 import ctypes as C
+import threading
+import time
 
 import numpy as np
 import pytest
@@ -247,6 +249,223 @@ def test_pipelined_driver_over_caller_transcripts(gpu, oracle, hipmem):
             o_tr = oracle.standard_transcript(nco, o.root())
             _same_proof(proofs[i], o.prove(o_enc, outer, o_tr), oracle)
             assert made[i].challenge_bytes(b"after", 32) == o_tr.challenge_bytes(b"after", 32)
+    finally:
+        for d in ds:
+            hipmem.free(d)
+
+
+# ---- the callbacks of a caller-owned transcript run on the calling thread, one at a time
+# (include/lcpc_mi.h, lcpc_transcript_ops).  A Rust shim holds a `&mut merlin::Transcript` behind
+# the ops: a callback on another thread, or two at once, is a data race there.  ctypes hides both
+# under the GIL, so the transcripts below record where and how deep they were called.
+class _CallbackProbe:
+    """what the transcripts of ONE native call saw: the thread of every callback and the largest
+    number of callbacks that were inside their bodies at one time"""
+
+    def __init__(self):
+        self.lock = threading.Lock()
+        self.idents = []
+        self.depth = 0
+        self.max_depth = 0
+
+    def enter(self):
+        with self.lock:
+            self.idents.append(threading.get_ident())
+            self.depth += 1
+            self.max_depth = max(self.max_depth, self.depth)
+
+    def leave(self):
+        with self.lock:
+            self.depth -= 1
+
+    def check(self, caller_ident, at_least):
+        assert len(self.idents) >= at_least, len(self.idents)
+        foreign = sorted({i for i in self.idents if i != caller_ident})
+        assert not foreign, f"{sum(i != caller_ident for i in self.idents)} of {len(self.idents)} callbacks ran on " \
+                            f"threads {foreign}, the call was made on {caller_ident}"
+        assert self.max_depth == 1 and self.depth == 0, (self.max_depth, self.depth)
+
+
+class ThreadRecordingTranscript(CountingOracleTranscript):
+    """CountingOracleTranscript that reports every callback to a _CallbackProbe.  The body yields
+    the GIL once (time.sleep(0)) so that a second callback running at the same time on another
+    thread gets the chance to be seen inside it."""
+
+    def __init__(self, oracle, probe, **kw):
+        super().__init__(oracle, **kw)
+        self.probe = probe
+        self.armed = False  # (the test's own _prefix / "after" calls are not the library's callbacks)
+
+    def _probed(self, fn, *a):
+        if not self.armed:
+            return fn(*a)
+        self.probe.enter()
+        try:
+            time.sleep(0)
+            return fn(*a)
+        finally:
+            self.probe.leave()
+
+    def append_message(self, label, msg):
+        return self._probed(super().append_message, label, msg)
+
+    def _append_messages(self, label, msgs, msg_len):
+        return self._probed(super()._append_messages, label, msgs, msg_len)
+
+    def challenge_bytes(self, label, n):
+        return self._probed(super().challenge_bytes, label, n)
+
+
+def _armed(oracle, probe, root, nco):
+    tr = _prefix(ThreadRecordingTranscript(oracle, probe), root, nco)
+    tr.armed = True
+    return tr
+
+
+def _after(tr):
+    tr.armed = False
+    return tr.challenge_bytes(b"after", 32)
+
+
+@pytest.fixture(scope="module")
+def thread_case(gpu, oracle):
+    """one small commitment (Ft127 256 -> 512, 12 rows, 2 degree tests) and the oracle's proof"""
+    fid, n_per_row, n_cols, nco, ndt = 1, 256, 512, 24, 2
+    enc = gpu.RsEncoding.new(fid, n_per_row, n_cols, nco, ndt)
+    o_enc = oracle.Encoding.ligero(fid, n_per_row, n_cols, nco, ndt)
+    coeffs = rand_elems(oracle, fid, 12 * n_per_row, 41)
+    g = gpu.LcCommit.commit(coeffs, enc)
+    o = oracle.Commit(o_enc, coeffs)
+    root = g.get_root()
+    assert root == o.root()
+    tensors = [oracle.eval_tensors(fid, rand_elems(oracle, fid, 1, 42 + j), n_per_row, g.get_n_rows())
+               for j in range(3)]
+    inners, outers = [t[0] for t in tensors], [t[1] for t in tensors]
+    o_tr = oracle.standard_transcript(nco, root)
+    op = o.prove(o_enc, outers[0], o_tr)
+    return dict(fid=fid, enc=enc, o_enc=o_enc, g=g, root=root, nco=nco, ndt=ndt, n_per_row=n_per_row,
+                inners=inners, outers=outers, op=op, o_after=o_tr.challenge_bytes(b"after", 32))
+
+
+def test_prove_ops_verify_ops_callbacks_on_the_calling_thread(gpu, oracle, thread_case):
+    """lcpc_prove_ops / lcpc_verify_ops (the per-call ops entry points)"""
+    from lcpc_proof_of_storage_amd import _native as N
+    lib = N.load()
+    t = thread_case
+    p64, el = gpu.lcpc2d._p64, gpu.lcpc2d._elems
+    o, i = el(t["outers"][0], t["fid"]), el(t["inners"][0], t["fid"])
+    probe = _CallbackProbe()
+    tr = _armed(oracle, probe, t["root"], t["nco"])
+    ct = gpu.CallerTranscript(tr)
+    h = C.c_void_p()
+    me = threading.get_ident()
+    assert lib.lcpc_prove_ops(t["g"]._h, p64(o), o.shape[0], t["enc"]._h, C.byref(ct._ops), C.byref(h)) == 0
+    pf = gpu.LcEvalProof(h.value)
+    probe.check(me, t["ndt"] + 1)
+    _same_proof(pf, t["op"], oracle)
+    assert _after(tr) == t["o_after"]
+
+    probe = _CallbackProbe()
+    tr = _armed(oracle, probe, t["root"], t["nco"])
+    ct = gpu.CallerTranscript(tr)
+    ev = np.zeros(gpu.limbs(t["fid"]), np.uint64)
+    rp = (C.c_uint8 * 32).from_buffer_copy(t["root"])
+    assert lib.lcpc_verify_ops(rp, p64(o), o.shape[0], p64(i), i.shape[0], pf._h, t["enc"]._h, C.byref(ct._ops),
+                               p64(ev)) == 0
+    probe.check(me, t["ndt"] + 1)
+    v_o = oracle.standard_transcript(t["nco"], t["root"])
+    rc, o_ev = t["op"].verify(t["root"], t["outers"][0], t["inners"][0], t["o_enc"], v_o)
+    assert rc == 0 and np.array_equal(ev, o_ev)
+    assert _after(tr) == v_o.challenge_bytes(b"after", 32)
+
+
+def test_prove_batch_ops_verify_batch_ops_callbacks_on_the_calling_thread(gpu, oracle, thread_case):
+    """lcpc_prove_batch_ops / lcpc_verify_batch_ops, three points: the same batch proof, evaluations
+    and end state as lcpc_prove_batch / lcpc_verify_batch over the library's transcript"""
+    from lcpc_proof_of_storage_amd import _native as N
+    lib = N.load()
+    t = thread_case
+    p64 = gpu.lcpc2d._p64
+    o = gpu.lcpc2d._stack_tensors(t["outers"], t["fid"])
+    i = gpu.lcpc2d._stack_tensors(t["inners"], t["fid"])
+    m = o.shape[0]
+    own = _prefix(gpu.Transcript(b"test transcript"), t["root"], t["nco"])
+    want = t["g"].prove_batch(t["outers"], t["enc"], own)
+    probe = _CallbackProbe()
+    tr = _armed(oracle, probe, t["root"], t["nco"])
+    ct = gpu.CallerTranscript(tr)
+    h = C.c_void_p()
+    me = threading.get_ident()
+    assert lib.lcpc_prove_batch_ops(t["g"]._h, p64(o.reshape(-1)), m, o.shape[1], t["enc"]._h, C.byref(ct._ops),
+                                    C.byref(h)) == 0
+    pf = gpu.LcBatchEvalProof(h.value)
+    probe.check(me, t["ndt"] + 1)
+    assert pf.to_bytes() == want.to_bytes()
+    assert _after(tr) == own.challenge_bytes(b"after", 32)
+
+    v_own = _prefix(gpu.Transcript(b"test transcript"), t["root"], t["nco"])
+    want_ev = want.verify(t["root"], t["outers"], t["inners"], t["enc"], v_own)
+    probe = _CallbackProbe()
+    tr = _armed(oracle, probe, t["root"], t["nco"])
+    ct = gpu.CallerTranscript(tr)
+    ev = np.zeros((m, gpu.limbs(t["fid"])), np.uint64)
+    rp = (C.c_uint8 * 32).from_buffer_copy(t["root"])
+    assert lib.lcpc_verify_batch_ops(rp, p64(o.reshape(-1)), m, o.shape[1], p64(i.reshape(-1)), i.shape[1], pf._h,
+                                     t["enc"]._h, C.byref(ct._ops), p64(ev)) == 0
+    probe.check(me, t["ndt"] + 1)
+    assert np.array_equal(ev, np.stack(want_ev))
+    assert _after(tr) == v_own.challenge_bytes(b"after", 32)
+
+
+def test_sharded_prove_callbacks_on_the_calling_thread(gpu, oracle, hipmem, thread_case):
+    """ShardedCommit.prove (lcpc_sharded_prove, one rank) over a caller transcript"""
+    from lcpc_proof_of_storage_amd import shard
+    t = thread_case
+    coeffs = rand_elems(oracle, t["fid"], 12 * t["n_per_row"], 41)  # thread_case's polynomial
+    d = hipmem.to_device(coeffs)
+    try:
+        sc = shard.ShardedCommit(t["enc"], shard.NativeComm.single(), d, 12)
+        assert sc.get_root() == t["root"]
+        probe = _CallbackProbe()
+        tr = _armed(oracle, probe, t["root"], t["nco"])
+        me = threading.get_ident()
+        pf = sc.prove(t["outers"][0], tr, root=0)
+        probe.check(me, t["ndt"] + 1)
+        _same_proof(pf, t["op"], oracle)
+        assert _after(tr) == t["o_after"]
+        del sc
+    finally:
+        hipmem.free(d)
+
+
+def test_pipelined_driver_callbacks_on_the_calling_thread(gpu, oracle, hipmem):
+    """lcpc_sharded_commit_prove_many (one rank) with three caller transcripts: every callback of
+    the three on the thread that made the call, never two at once (the driver's worker pool runs
+    only the library's own transcripts), and the proofs and end states still the oracle's."""
+    from lcpc_proof_of_storage_amd import shard
+    fid, n_per_row, n_cols, nco, ndt = 1, 256, 512, 24, 2
+    enc = gpu.RsEncoding.new(fid, n_per_row, n_cols, nco, ndt)
+    o_enc = oracle.Encoding.ligero(fid, n_per_row, n_cols, nco, ndt)
+    n_rows = 16
+    polys = [rand_elems(oracle, fid, n_rows * n_per_row, 31 + k) for k in range(3)]
+    outer = rand_elems(oracle, fid, n_rows, 32)
+    ds = [hipmem.to_device(p) for p in polys]
+    made = {}
+    probe = _CallbackProbe()
+    try:
+        def make_tr(i, root):
+            made[i] = _armed(oracle, probe, root, nco)
+            return made[i]
+
+        me = threading.get_ident()
+        roots, proofs = shard.sharded_commit_prove_many(enc, shard.NativeComm.single(), ds, n_rows, outer, make_tr)
+        probe.check(me, 3 * (ndt + 1))
+        for i, p in enumerate(polys):
+            o = oracle.Commit(o_enc, p)
+            assert roots[i] == o.root()
+            o_tr = oracle.standard_transcript(nco, o.root())
+            _same_proof(proofs[i], o.prove(o_enc, outer, o_tr), oracle)
+            assert _after(made[i]) == o_tr.challenge_bytes(b"after", 32)
     finally:
         for d in ds:
             hipmem.free(d)

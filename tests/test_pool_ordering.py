@@ -23,6 +23,24 @@ def test_pool_ordering_on_simulated_streams(tmp_path):
     assert "pool ordering: ok" in r.stdout
 
 
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_pool_ordering_from_many_threads(tmp_path):
+    """The same property with 8 host threads on one pool (take / put / order_after under its mutex,
+    the backend called outside it) while a simulated device thread retires the streams' operations
+    in random order: tests/cpp/test_pool_threads.cpp, built with ThreadSanitizer.  No block may be
+    owned twice, no earlier owner's write may complete after a later owner's first read, and the
+    pool's own state must be free of data races."""
+    exe = tmp_path / "test_pool_threads"
+    src = os.path.join(ROOT, "tests", "cpp", "test_pool_threads.cpp")
+    subprocess.run(["g++", "-std=c++20", "-O1", "-g", "-fsanitize=thread", "-Wall", "-o", str(exe), src],
+                   check=True, timeout=300)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    print(r.stdout[-500:])
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "pool threads: ok" in r.stdout
+    assert "ThreadSanitizer" not in r.stderr, r.stderr[-4000:]
+
+
 @pytest.mark.gpu
 def test_pool_ordering_on_device():
     """The same fences on the MI355X (lcpc_selftest_pool_ordering): a block released while a
