@@ -52,7 +52,8 @@ extern "C" {
  * lcpc_pos_update_evaluation).  So are the diagnostics added since (lcpc_selftest_field_op,
  * lcpc_selftest_recombine, lcpc_selftest_twiddle_words, lcpc_selftest_ntt_rows, lcpc_selftest_spmm, lcpc_selftest_reed_solomon).
  * So is the batched stored-file audit (lcpc_pos_left_multiply_bytes_many*, lcpc_pos_left_multiply_many_kernel,
- * lcpc_selftest_recombine63). */
+ * lcpc_selftest_recombine63).  So are the grouped stored-file audits (lcpc_pos_left_multiply_bytes_grouped*,
+ * lcpc_pos_group_plan, lcpc_field_to_montgomery). */
 #define LCPC_ABI_VERSION 3
 
 typedef enum lcpc_status {
@@ -583,6 +584,58 @@ lcpc_status lcpc_pos_left_multiply_bytes_many_device(const void *d_bytes, size_t
  * (pre < 64, fewer than 16 vectors, LCPC_NO_MFMA=1);  2: the int8 matrix cores on the bytes (pre >= 64
  * and at least 16 vectors, where they measured faster).  No device needed. */
 int lcpc_pos_left_multiply_many_kernel(size_t pre, size_t n_vecs);
+/* Grouped audits: lcpc_pos_left_multiply_bytes for n_jobs files in one call (a server's queue of
+ * audits over different files, most of them small).  Job j is the image bytes[j] of n_bytes[j] bytes
+ * with rows of pre[j] elements; its left vector is the next n_rows_j = ceil(ceil(n_bytes[j] / 7) / pre[j])
+ * words of lefts, its result the next pre[j] words of out:
+ *   out_j[c] = sum_r left_j[r] M_j[r][c].
+ * BIT-IDENTITY: out_j is word for word what lcpc_pos_left_multiply_bytes(bytes[j], n_bytes[j], pre[j],
+ * left_j, n_rows_j, .) returns, for every job that call accepts (field sums are exact: neither the
+ * grouping nor a job's row split shows).
+ * PADDING is per image: job j is read through (bytes[j], n_bytes[j]) alone and zero padded past its
+ * own end; the bytes that follow an image in an arena belong to the next file and never enter.
+ * Host images may have any alignment.  Consecutive jobs are staged at 8-byte aligned offsets of a
+ * device arena in staging groups of at most LCPC_POS_GROUP_STAGE_BYTES image bytes (and bounded job,
+ * row and column counts), one upload and one contraction launch (plus one fold launch for the jobs
+ * split in rows) per group, each group contracted as it lands: the launches are O(groups), never
+ * O(n_jobs), and the device memory in use is the arena plus the largest single file.  A job larger
+ * than a staging group, or with pre no power of two >= 8, goes through lcpc_pos_left_multiply_bytes'
+ * own path inside the same call (it ends the group before it).
+ * Errors, before any device work: a NULL pointer, n_jobs = 0, a job with n_bytes or pre of 0, n_left_total
+ * != sum n_rows_j, n_out_total != sum pre[j]: LCPC_ERR_INVALID_ARG; no device: LCPC_ERR_NO_DEVICE.
+ * Threading as every entry: a stream of its own per call. */
+#define LCPC_POS_GROUP_STAGE_BYTES ((size_t)32 << 20)
+lcpc_status lcpc_pos_left_multiply_bytes_grouped(const uint8_t *const *bytes, const size_t *n_bytes, const size_t *pre,
+                                                 size_t n_jobs, const uint64_t *lefts, size_t n_left_total,
+                                                 uint64_t *out, size_t n_out_total);
+/* The same over one device arena the caller owns: job j is the n_bytes[j] bytes at d_arena +
+ * offsets[j], offsets[j] a multiple of 8 (else LCPC_ERR_INVALID_ARG; d_arena itself 8-byte aligned).
+ * No byte outside [offsets[j], offsets[j] + n_bytes[j]) enters job j's value, whatever the arena holds
+ * there.  Nothing is staged but the launches' tables; the groups are those of the host entry. */
+lcpc_status lcpc_pos_left_multiply_bytes_grouped_device(const void *d_arena, const size_t *offsets,
+                                                        const size_t *n_bytes, const size_t *pre, size_t n_jobs,
+                                                        const uint64_t *lefts, size_t n_left_total, uint64_t *out,
+                                                        size_t n_out_total);
+/* Host-only, no device (like lcpc_pos_read_plan): the work list of the launches the two entries above
+ * make for these jobs, a pure function of its arguments (and of LCPC_POS_GROUP_BYTES, a test seam read
+ * at every call that can only lower the staging group's size).  A tile is rows [row_lo, row_hi) x
+ * 56-byte runs [run_lo, run_hi) of one job, a lane per run; `launch` counts the grouped launches from
+ * 0 and `wave` the waves of a launch (4 per workgroup): the tiles of one wave share a row count and a
+ * width.  A job routed to the single-file path has one record with launch = LCPC_POS_GROUP_SINGLE,
+ * wave = 0, over all its rows and its ceil(pre / 8) runs.  Every (job, row, run) is in exactly one
+ * record.  Writes at most cap records to tiles (may be NULL with cap 0), the count needed to *n_tiles
+ * and the number of grouped launches to *n_launches (either may be NULL). */
+typedef struct lcpc_pos_group_tile {
+  uint64_t job, row_lo, row_hi, run_lo, run_hi;
+  uint32_t launch, wave;
+} lcpc_pos_group_tile;
+#define LCPC_POS_GROUP_SINGLE 0xffffffffu
+lcpc_status lcpc_pos_group_plan(const size_t *n_bytes, const size_t *pre, size_t n_jobs, lcpc_pos_group_tile *tiles,
+                                size_t cap, size_t *n_tiles, size_t *n_launches);
+/* Host-only: out[i] = (in[i] R) mod p, the Montgomery word of any 64-bit value in[i] (canonical or
+ * not), R = 2^64; f must be LCPC_FT63 (else LCPC_ERR_UNSUPPORTED).  in == out is allowed.  What a
+ * server does to the canonical column values of a `.porenc` before it sends them. */
+lcpc_status lcpc_field_to_montgomery(lcpc_field f, const uint64_t *in, uint64_t *out, size_t n);
 /* Host-only, no device (like lcpc_pos_update_chunk_range): the rows an update touches.  The
  * reference's edit and append handlers (networking/server.rs:963-1077) each pick their "original
  * rows" differently and disagree with their clients; this is the one rule that replaces them.

@@ -16,3 +16,6 @@ from .lcpc2d import (  # noqa: F401
     SELFTEST_OPS, selftest_fe_dot_kmax, selftest_field_op, selftest_recombine, selftest_recombine63, selftest_twiddle_words, selftest_ntt_rows,
     selftest_spmm, selftest_reed_solomon,
 )
+# grouped audits of many stored files
+from .pos import left_multiply_unencoded_matrices_by_vectors  # noqa: F401,E402
+from .pos_files import answer_evaluation_requests  # noqa: F401,E402

@@ -51,6 +51,12 @@ class TranscriptOps(C.Structure):
                 ("challenge_bytes", TR_CHALLENGE_FN)]
 
 
+class PosGroupTile(C.Structure):
+    """lcpc_pos_group_tile (include/lcpc_mi.h)"""
+    _fields_ = [("job", C.c_uint64), ("row_lo", C.c_uint64), ("row_hi", C.c_uint64), ("run_lo", C.c_uint64),
+                ("run_hi", C.c_uint64), ("launch", C.c_uint32), ("wave", C.c_uint32)]
+
+
 class CommOps(C.Structure):
     _fields_ = [("user", vp), ("all_gather", ALL_GATHER_FN), ("all_to_all_v", ALL_TO_ALL_V_FN),
                 ("broadcast", BROADCAST_FN)]
@@ -191,6 +197,10 @@ SIGNATURES = {
     "lcpc_pos_left_multiply_bytes_many": (i32, [vp, sz, sz, u64p, sz, sz, u64p]),
     "lcpc_pos_left_multiply_bytes_many_device": (i32, [vp, sz, sz, u64p, sz, sz, u64p]),
     "lcpc_pos_left_multiply_many_kernel": (C.c_int, [sz, sz]),
+    "lcpc_pos_left_multiply_bytes_grouped": (i32, [C.POINTER(vp), szp, szp, sz, u64p, sz, u64p, sz]),
+    "lcpc_pos_left_multiply_bytes_grouped_device": (i32, [vp, szp, szp, szp, sz, u64p, sz, u64p, sz]),
+    "lcpc_pos_group_plan": (i32, [szp, szp, sz, C.POINTER(PosGroupTile), sz, szp, szp]),
+    "lcpc_field_to_montgomery": (i32, [i32, u64p, u64p, sz]),
     "lcpc_pos_update_rows": (i32, [sz, sz, sz, sz, szp, szp, szp, szp]),
     "lcpc_pos_update_evaluation": (i32, [vp, vp, sz, vp, vp, sz, u64p, u64p, sz, u64p, sz,
                                          u64p, u64p, u8p, u8p, u64p, u64p, u8p, u8p, u64p]),

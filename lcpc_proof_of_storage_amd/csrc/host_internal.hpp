@@ -1,7 +1,7 @@
 // host_internal.hpp -- shared host-side machinery of liblcpc_mi.so (per-device stream pools and
 // caching allocator, pinned staging, handle layouts, Fiat-Shamir helpers).  Internal: included by
 // every host unit (lcpc_host.cpp, shard_host.cpp, shard_native.cpp, batch_host.cpp and, through
-// pos_internal.hpp, pos_files_host.cpp and pos_repair_host.cpp); one definition of every pool /
+// pos_internal.hpp, pos_files_host.cpp, pos_repair_host.cpp and pos_group_host.cpp); one definition of every pool /
 // thread-local across them.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -825,6 +825,93 @@ inline void challenge_columns(lcpc_transcript &tr, size_t n_cols, size_t nco, st
   ChaCha20Rng rng(key);
   idx.resize(nco);
   for (size_t i = 0; i < nco; i++) idx[i] = uniform_usize(rng, 0, n_cols);
+}
+
+// Host -> device upload of `bytes` bytes in blocks of `block` bytes on a copy stream of its own,
+// each block handed to on_block(off, n) -- which queues the block's compute on `s` -- as soon as s
+// has been ordered after the block's copy: the DMA of block k + 1 overlaps the kernels of block k.
+// A page-locked source (hipHostMalloc / registered) is read by the DMA engine directly; a pageable
+// one (lcpc_commit_new's source is the caller's &[F], lcpc-2d/src/lib.rs:651: normally pageable)
+// goes through the runtime's own pageable path, block by block (measured against staging it
+// through two page-locked slots of this thread: 40.5 / 40.8 against 38.9 / 40.2 GB/s at cfg3,
+// profiles/r06_h2d_pageable_ab.json).  Returns with the copies queued; s is ordered after all of
+// them.
+struct UploadStats {
+  bool pinned = false;
+  size_t blocks = 0;
+};
+inline thread_local UploadStats t_last_upload;
+// this thread's upload events (one "block landed" event per block in flight, and the
+// destination's "taken" record on the consuming stream), per current device
+struct UploadEvents {
+  hipEvent_t e[3] = {};
+  int dev = -1;
+  ~UploadEvents() { reset(); }
+  void reset() {
+    for (hipEvent_t &x : e) {
+      if (x) (void)hipEventDestroy(x);
+      x = nullptr;
+    }
+  }
+  bool ready() {
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess) return false;
+    if (cur != dev) {
+      reset();
+      dev = cur;
+    }
+    for (hipEvent_t &x : e)
+      if (!x && hipEventCreateWithFlags(&x, hipEventDisableTiming) != hipSuccess) {
+        x = nullptr;
+        return false;
+      }
+    return true;
+  }
+};
+inline thread_local UploadEvents t_upload_ev;
+
+template <class OnBlock>
+lcpc_status h2d_blocks(Device *dev, uint8_t *d_dst, const uint8_t *h_src, size_t bytes, size_t block,
+                       hipStream_t s, OnBlock &&on_block) {
+  t_last_upload = {};
+  if (!bytes) return LCPC_OK;
+  block = std::max<size_t>(block, 4096);
+  t_last_upload.pinned = host_dev_ptr(h_src) != nullptr;
+  if (!t_upload_ev.ready()) return fail(LCPC_ERR_DEVICE, "hipEventCreate");
+  hipStream_t cs = dev->acquire_stream(POOL_BULK);
+  if (!cs) return fail(LCPC_ERR_DEVICE, "no HIP stream");
+  // (the copies stay queued on cs, and s waits on them: the stream goes back to the pool at once,
+  // work still queued on it ordered like any pooled stream's; the events are this thread's,
+  // reused only after its caller drains s)
+  struct Release {
+    Device *dev;
+    hipStream_t cs;
+    bool ordered = false;  // s waits on every copy queued so far
+    ~Release() {
+      // an early return may leave a copy that s never waited on: it writes a buffer the caller
+      // releases with a fence on s alone, so drain it here
+      if (!ordered) (void)hipStreamSynchronize(cs);
+      dev->release_stream(cs, POOL_BULK);
+    }
+  } rel{dev, cs};
+  // d_dst was taken from the pool on s (a reused block's fence wait is queued there): the copy
+  // stream writes it only after s has passed that point
+  HIP_TRY(hipEventRecord(t_upload_ev.e[2], s));
+  HIP_TRY(hipStreamWaitEvent(cs, t_upload_ev.e[2], 0));
+  size_t k = 0;
+  for (size_t off = 0; off < bytes; off += block, k++) {
+    const size_t n = std::min(block, bytes - off);
+    hipEvent_t landed = t_upload_ev.e[k & 1];
+    rel.ordered = false;
+    HIP_TRY(hipMemcpyAsync(d_dst + off, h_src + off, n, hipMemcpyHostToDevice, cs));
+    HIP_TRY(hipEventRecord(landed, cs));
+    HIP_TRY(hipStreamWaitEvent(s, landed, 0));
+    rel.ordered = true;
+    lcpc_status st = on_block(off, n);
+    if (st) return st;
+  }
+  t_last_upload.blocks = k;
+  return LCPC_OK;
 }
 
 inline Device *current_device(lcpc_status *st) { return get_device(g_device, st); }

@@ -63,4 +63,36 @@ hipError_t pos_left_mul_many_fold(int kernel, const uint32_t *partials, size_t n
 // out[i] = recombine_redc63 of the 8 accumulators y[8 i ..] (selftest)
 hipError_t pos_recombine63(const int *y, uint32_t *out, size_t n, hipStream_t s);
 
+// ---- pos_group.hip: u^T M of many files in one launch (grouped audits)
+// The host builds the tables of a launch (pos_group_host.cpp); all offsets are in elements of the
+// named buffer unless they say bytes.
+//   job    an image of n_bytes bytes at byte offset base of the launch's arena (a multiple of 8), rows
+//          of pre elements (a power of two >= 8), its left vector at element left_off of the lefts
+//   tile   rows [row_lo, row_lo + the wave's n_rows) x 56-byte runs [run_lo, run_lo + 2^log_w) of one
+//          job, one lane per run; the row vector it accumulates into starts at element dst of res (the
+//          job's output when the job has one row split, else one of its partials)
+//   wave   n_tiles tiles from tile0 on, all 2^log_w lanes wide (2^log_w = min(pre / 8, 64)) and n_rows
+//          rows deep, so the row loop is uniform over the wave: lane l works on tile l >> log_w
+//   fold   columns [col0, col0 + n_cols) (at most 64, one lane each) of a job split in rows:
+//          res[out + c] = sum_{y < n_split} res[part + y pre + c]
+struct PosGroupJob {
+  uint64_t base, n_bytes, left_off, pre;
+};
+struct PosGroupTile {
+  uint32_t job, row_lo, run_lo, pad;
+  uint64_t dst;
+};
+struct PosGroupWave {
+  uint32_t tile0, n_tiles, log_w, n_rows;
+};
+struct PosGroupFold {
+  uint64_t out, part;
+  uint32_t n_split, pre, col0, n_cols;
+};
+// one launch over n_waves waves (4 per workgroup), then with n_folds != 0 one fold launch (a wave per
+// fold); n_waves / 4 and n_folds / 4 stay below 2^24 workgroups as in pos_left_mul_bytes
+hipError_t pos_group_left_mul(const uint8_t *arena, const PosGroupJob *jobs, const PosGroupTile *tiles,
+                              const PosGroupWave *waves, size_t n_waves, const PosGroupFold *folds, size_t n_folds,
+                              const uint32_t *lefts, uint32_t *res, hipStream_t s);
+
 }  // namespace lcpc

@@ -1079,6 +1079,109 @@ def left_multiply_unencoded_matrix_by_vectors(data, pre_encoded_size: int, lefts
     return out
 
 
+# ---------------------------------------------------------------- grouped audits of many stored files
+# A server's queue of audits over different files, most of them small, answered with launches that
+# do not grow with the number of files.  No counterpart in the reference.
+GROUP_STAGE_BYTES = 32 << 20        # LCPC_POS_GROUP_STAGE_BYTES
+GROUP_SINGLE = 0xFFFFFFFF           # LCPC_POS_GROUP_SINGLE: a job routed to the single-file path
+
+
+def _as_image(data) -> np.ndarray:
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        return np.frombuffer(data, np.uint8)
+    return np.ascontiguousarray(np.asarray(data, np.uint8).reshape(-1))
+
+
+def _sizes(values) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(list(values), dtype=np.uint64)).astype(C.c_size_t)
+
+
+def _group_lefts(sizes, pres, lefts):
+    """the jobs' left vectors one after another, checked against the files' row counts"""
+    flat = []
+    for j, (n, pre, lv) in enumerate(zip(sizes, pres, lefts)):
+        v = np.asarray(lv, dtype=np.uint64).reshape(-1)
+        if v.size != _file_rows(int(n), int(pre)):
+            raise ValueError(f"job {j}: left_vector incorrect size, expected {_file_rows(int(n), int(pre))} "
+                             f"and received {v.size}")
+        flat.append(v)
+    return np.ascontiguousarray(np.concatenate(flat)) if flat else np.zeros(0, np.uint64)
+
+
+def _split_outputs(out: np.ndarray, pres) -> List[np.ndarray]:
+    ends = np.cumsum(np.asarray(pres, dtype=np.int64))
+    return [out[e - int(p):e].reshape(-1, 1) for e, p in zip(ends, pres)]
+
+
+def left_multiply_unencoded_matrices_by_vectors(datas, pres, lefts) -> List[np.ndarray]:
+    """left_multiply_unencoded_matrix_by_vector for many files in one call
+    (lcpc_pos_left_multiply_bytes_grouped): job j is the file datas[j] with rows of pres[j] elements
+    and the left vector lefts[j].  Returns the list of (pres[j], 1) arrays, array j word for word what
+    left_multiply_unencoded_matrix_by_vector(datas[j], pres[j], lefts[j]) returns; the launches are
+    per staging group of files, not per file."""
+    images = [_as_image(d) for d in datas]
+    pres = [int(p) for p in pres]
+    if not (len(images) == len(pres) == len(lefts)):
+        raise ValueError("datas, pres and lefts must have one entry per job")
+    if not images:
+        return []
+    if any(a.size == 0 for a in images) or any(p < 1 for p in pres):
+        raise ValueError("every job needs a non-empty file and pre_encoded_size >= 1")
+    sizes = [a.size for a in images]
+    lv = _group_lefts(sizes, pres, lefts)
+    out = np.zeros(sum(pres), np.uint64)
+    ptrs = (C.c_void_p * len(images))(*[a.ctypes.data for a in images])
+    nb, pr = _sizes(sizes), _sizes(pres)
+    _raise(N.load().lcpc_pos_left_multiply_bytes_grouped(ptrs, nb.ctypes.data_as(N.szp), pr.ctypes.data_as(N.szp),
+                                                         len(images), _p64(lv), lv.size, _p64(out), out.size))
+    return _split_outputs(out, pres)
+
+
+def left_multiply_device_arena_by_vectors(arena_ptr: int, offsets, sizes, pres, lefts) -> List[np.ndarray]:
+    """The same over a device arena the caller owns (lcpc_pos_left_multiply_bytes_grouped_device): job j
+    is the sizes[j] bytes at arena_ptr + offsets[j], offsets[j] a multiple of 8.  Nothing outside a
+    job's own bytes enters its value."""
+    sizes, pres = [int(n) for n in sizes], [int(p) for p in pres]
+    lv = _group_lefts(sizes, pres, lefts)
+    out = np.zeros(sum(pres), np.uint64)
+    of, nb, pr = _sizes(offsets), _sizes(sizes), _sizes(pres)
+    _raise(N.load().lcpc_pos_left_multiply_bytes_grouped_device(
+        arena_ptr, of.ctypes.data_as(N.szp), nb.ctypes.data_as(N.szp), pr.ctypes.data_as(N.szp), len(sizes), _p64(lv),
+        lv.size, _p64(out), out.size))
+    return _split_outputs(out, pres)
+
+
+def left_multiply_group_plan(sizes, pres):
+    """lcpc_pos_group_plan: (tiles, n_launches) for files of sizes[j] bytes with rows of pres[j]
+    elements.  tiles is a structured array with the fields job, row_lo, row_hi, run_lo, run_hi, launch
+    and wave: the work list of the grouped launches the calls above make, a job routed to the
+    single-file path as one record with launch == GROUP_SINGLE.  Host only, a pure function."""
+    nb, pr = _sizes(sizes), _sizes(pres)
+    if nb.size != pr.size:
+        raise ValueError("sizes and pres must have one entry per job")
+    n, launches = C.c_size_t(), C.c_size_t()
+    L = N.load()
+    _raise(L.lcpc_pos_group_plan(nb.ctypes.data_as(N.szp), pr.ctypes.data_as(N.szp), nb.size, None, 0, C.byref(n),
+                                 C.byref(launches)))
+    dt = np.dtype([("job", "<u8"), ("row_lo", "<u8"), ("row_hi", "<u8"), ("run_lo", "<u8"), ("run_hi", "<u8"),
+                   ("launch", "<u4"), ("wave", "<u4")])
+    assert dt.itemsize == C.sizeof(N.PosGroupTile)
+    tiles = np.zeros(n.value, dt)
+    _raise(L.lcpc_pos_group_plan(nb.ctypes.data_as(N.szp), pr.ctypes.data_as(N.szp), nb.size,
+                                 tiles.ctypes.data_as(C.POINTER(N.PosGroupTile)), tiles.size, C.byref(n),
+                                 C.byref(launches)))
+    return tiles, launches.value
+
+
+def field_to_montgomery(values, field: int = FT63) -> np.ndarray:
+    """lcpc_field_to_montgomery: (v R) mod p per 64-bit word, R = 2^64 (Ft63 only): canonical values,
+    as a `.porenc` holds them, to the Montgomery words a commitment opens.  Same shape as `values`."""
+    a = np.ascontiguousarray(np.asarray(values, dtype=np.uint64))
+    out = np.empty_like(a)
+    _raise(N.load().lcpc_field_to_montgomery(field, _p64(a.reshape(-1)), _p64(out.reshape(-1)), a.size))
+    return out
+
+
 def client_verify_batch_evaluation(root: bytes, file_len: int, pre: int, enc: int, points, vectors, column_indices,
                                    columns: Sequence[LcColumn]) -> np.ndarray:
     """One audit of a stored file at m points: `vectors` (m, pre) are the server's unencoded vectors

@@ -1669,3 +1669,50 @@ class FileHandler:
         d = os.path.dirname(self.unencoded_file_handle)
         if not os.listdir(d):
             os.rmdir(d)
+
+
+# -- grouped audits
+def answer_evaluation_requests(requests):
+    """A server's queue of evaluation requests over different stored files, answered together:
+    `requests` is a sequence of (FileHandler, point, columns), the result the list of (result_vector,
+    columns_with_paths), entry i bit-identical to requests[i][0].polynomial_evaluation_response(point,
+    columns).  The same handler may appear in several requests (its raw file is read once).
+
+    The raw files go through one grouped contraction (lcpc_pos_left_multiply_bytes_grouped: launches
+    per staging group, not per file), the vectors through one encode_rows per distinct (pre, enc), and
+    the opened columns from canonical to Montgomery words in the library (lcpc_field_to_montgomery),
+    not in a Python loop over elements."""
+    from .lcpc2d import FT63, LcColumn, LigeroEncoding
+    from .pos import (field_to_montgomery, form_side_vectors_for_polynomial_evaluation_from_point,
+                      left_multiply_unencoded_matrices_by_vectors)
+    reqs = [(fh, point, list(columns)) for fh, point, columns in requests]
+    if not reqs:
+        return []
+    raw = {}
+    for fh, _, _ in reqs:
+        if id(fh) not in raw:
+            with open(fh.unencoded_file_handle, "rb") as f:
+                raw[id(fh)] = f.read(fh.total_data_bytes)
+    lefts = [form_side_vectors_for_polynomial_evaluation_from_point(point, fh.rows_written, fh.pre_encoded_size)[0]
+             for fh, point, _ in reqs]
+    vectors = left_multiply_unencoded_matrices_by_vectors([raw[id(fh)] for fh, _, _ in reqs],
+                                                          [fh.pre_encoded_size for fh, _, _ in reqs], lefts)
+    by_dims = {}
+    for i, (fh, _, _) in enumerate(reqs):
+        by_dims.setdefault((fh.pre_encoded_size, fh.encoded_size), []).append(i)
+    results = [None] * len(reqs)
+    for (pre, enc), members in by_dims.items():
+        rows = np.zeros((len(members), enc), np.uint64)
+        for k, i in enumerate(members):
+            rows[k, :pre] = vectors[i].reshape(-1)
+        coded = LigeroEncoding.new_from_dims(FT63, pre, enc).encode_rows(rows)
+        for k, i in enumerate(members):
+            results[i] = coded[k].reshape(enc, 1).copy()
+    out = []
+    for i, (fh, _, columns) in enumerate(reqs):
+        opened = fh.read_full_columns(columns)
+        if opened:  # one conversion per request: its columns all have the file's row count
+            mont = field_to_montgomery(np.stack([np.asarray(c.col).reshape(-1) for c in opened]))
+            opened = [LcColumn(mont[k].reshape(-1, 1), c.path) for k, c in enumerate(opened)]
+        out.append((results[i], opened))
+    return out
