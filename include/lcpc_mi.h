@@ -53,7 +53,9 @@ extern "C" {
  * lcpc_selftest_recombine, lcpc_selftest_twiddle_words, lcpc_selftest_ntt_rows, lcpc_selftest_spmm, lcpc_selftest_reed_solomon).
  * So is the batched stored-file audit (lcpc_pos_left_multiply_bytes_many*, lcpc_pos_left_multiply_many_kernel,
  * lcpc_selftest_recombine63).  So are the grouped stored-file audits (lcpc_pos_left_multiply_bytes_grouped*,
- * lcpc_pos_group_plan, lcpc_field_to_montgomery). */
+ * lcpc_pos_group_plan, lcpc_field_to_montgomery).  So is the grouped check of stored-file audit
+ * responses (lcpc_pos_audit_job, lcpc_pos_verify_evaluations_grouped, lcpc_pos_verify_tile,
+ * lcpc_pos_verify_group_plan). */
 #define LCPC_ABI_VERSION 3
 
 typedef enum lcpc_status {
@@ -636,6 +638,63 @@ lcpc_status lcpc_pos_group_plan(const size_t *n_bytes, const size_t *pre, size_t
  * not), R = 2^64; f must be LCPC_FT63 (else LCPC_ERR_UNSUPPORTED).  in == out is allowed.  What a
  * server does to the canonical column values of a `.porenc` before it sends them. */
 lcpc_status lcpc_field_to_montgomery(lcpc_field f, const uint64_t *in, uint64_t *out, size_t n);
+
+/* ---- PoS grouped check of audit responses (the client side of the grouped audits) ----
+ * NO COUNTERPART IN THE REFERENCE.  Additive within LCPC_ABI_VERSION 3.  An auditor that holds the
+ * roots of many stored files checks a queue of plain audit responses -- per file the server's result
+ * vector and the opened columns with their Merkle paths -- together.  Job j passes (verdict[j] = 0)
+ * iff every opened column hashes, through its path, to root and the result vector, decoded (ifft_oi),
+ * cut to pre coefficients, zero padded and re-encoded, equals sum_r left[r] col_k[r] at every idx[k],
+ * left = [1, x^pre, x^(2 pre), ...] for x = point; values[j] = <dec[:pre], [1, x, x^2, ...]>, the file
+ * polynomial's value at the point.  A Merkle path that does not lead to root is verdict 1; paths that
+ * pass and a column value that disagrees is verdict 2 (paths first, then values).  values[j] is
+ * written for every job and means something only where verdict[j] == 0.  A bad response is a verdict,
+ * never an error status, and never changes another job's verdict or value.
+ * EQUALITY: verdict and value are what the single sequence (lcpc_hash_field_columns,
+ * lcpc_verify_leaf_paths, lcpc_pos_side_vectors, lcpc_ifft_oi_rows, the dot, lcpc_encode,
+ * lcpc_verify_column_values) gives for that response, the value word for word.  cols and result are
+ * untrusted 64-bit words and are not range checked, as there; point is a field element in Montgomery
+ * form.  Ft63 and BLAKE3 only; the entry takes no encoding, so no other digest can reach it.
+ * Consecutive jobs fill staging groups of at most LCPC_POS_GROUP_STAGE_BYTES bytes of columns (and
+ * at most 2^16 jobs and 2^16 columns, which bounds the paths); a group's columns (each at a 16-byte aligned stride),
+ * paths, roots, indices, left vectors and tables go up in one copy from one of two page-locked blocks
+ * and are checked in two launches, the next group gathered meanwhile.  The result vectors take one
+ * decode per distinct enc and one encode per distinct (pre, enc) for the whole call.  The launches
+ * never grow with n_jobs.  A job whose columns exceed a group (or number more than 2^16) ends the group
+ * before it and goes through the single sequence inside the same call.
+ * Errors, before any device work: a NULL pointer (idx, cols and paths may be NULL where n_cols == 0),
+ * n_jobs = 0, pre, enc or file_len of 0, enc no power of two or enc <= pre (the dims every stored file
+ * has: EncodedFileWriter's, e.g. 24 / 32), an idx that is not strictly
+ * increasing or not below enc: LCPC_ERR_INVALID_ARG; enc beyond the field's two-adicity:
+ * LCPC_FFT_TOO_BIG; no device: LCPC_ERR_NO_DEVICE.  Threading as every entry: a stream of its own per call. */
+typedef struct lcpc_pos_audit_job {
+  const uint8_t *root;    /* 32 B, the root the client holds */
+  size_t file_len, pre, enc;
+  uint64_t point;         /* the evaluation point, the word lcpc_pos_side_vectors takes */
+  const uint64_t *idx;    /* n_cols opened column indices, strictly increasing, < enc */
+  size_t n_cols;
+  const uint64_t *cols;   /* [n_cols][n_rows] Montgomery words, n_rows = rows of file_len at pre */
+  const uint8_t *paths;   /* n_cols x log2(enc) x 32 B */
+  const uint64_t *result; /* enc words: the server's result vector */
+} lcpc_pos_audit_job;
+lcpc_status lcpc_pos_verify_evaluations_grouped(const lcpc_pos_audit_job *jobs, size_t n_jobs, uint8_t *verdict,
+                                                uint64_t *values);
+/* Host-only, no device (like lcpc_pos_group_plan): the work list of the first launch of each staging
+ * group the entry above makes for jobs of these file lengths, pre and opened-column counts, a pure function
+ * of its arguments (and of LCPC_POS_GROUP_BYTES, the test seam that can only lower the group's size).
+ * A record is columns [col_lo, col_hi) (at most 64, a lane each) of one job and one 1-KiB chunk of their
+ * leaf messages: one wave; `launch` counts the groups that launch from 0, `wave` the waves of a launch
+ * (4 per workgroup).  A job routed to the single sequence has one record per chunk over all its columns
+ * with launch = LCPC_POS_GROUP_SINGLE, wave = 0.  Every (job, column, chunk) is in exactly one record;
+ * a job with n_cols = 0 has none.  Writes at most cap records to tiles (may be NULL with cap 0), the
+ * count needed to *n_tiles and the number of launching groups to *n_launches (either may be NULL).
+ * Errors: a NULL array, n_jobs = 0, a file_len or pre of 0: LCPC_ERR_INVALID_ARG. */
+typedef struct lcpc_pos_verify_tile {
+  uint64_t job, col_lo, col_hi, chunk;
+  uint32_t launch, wave;
+} lcpc_pos_verify_tile;
+lcpc_status lcpc_pos_verify_group_plan(const size_t *file_len, const size_t *pre, const size_t *n_cols, size_t n_jobs,
+                                       lcpc_pos_verify_tile *tiles, size_t cap, size_t *n_tiles, size_t *n_launches);
 /* Host-only, no device (like lcpc_pos_update_chunk_range): the rows an update touches.  The
  * reference's edit and append handlers (networking/server.rs:963-1077) each pick their "original
  * rows" differently and disagree with their clients; this is the one rule that replaces them.

@@ -19,3 +19,5 @@ from .lcpc2d import (  # noqa: F401
 # grouped audits of many stored files
 from .pos import left_multiply_unencoded_matrices_by_vectors  # noqa: F401,E402
 from .pos_files import answer_evaluation_requests  # noqa: F401,E402
+# the client's check of those responses, one at a time or grouped
+from .pos import client_verify_evaluation, client_verify_evaluations_grouped, verify_group_plan  # noqa: F401,E402

@@ -57,6 +57,19 @@ class PosGroupTile(C.Structure):
                 ("run_hi", C.c_uint64), ("launch", C.c_uint32), ("wave", C.c_uint32)]
 
 
+class PosAuditJob(C.Structure):
+    """lcpc_pos_audit_job (include/lcpc_mi.h)"""
+    _fields_ = [("root", vp), ("file_len", C.c_size_t), ("pre", C.c_size_t), ("enc", C.c_size_t),
+                ("point", C.c_uint64), ("idx", vp), ("n_cols", C.c_size_t), ("cols", vp), ("paths", vp),
+                ("result", vp)]
+
+
+class PosVerifyTile(C.Structure):
+    """lcpc_pos_verify_tile (include/lcpc_mi.h)"""
+    _fields_ = [("job", C.c_uint64), ("col_lo", C.c_uint64), ("col_hi", C.c_uint64), ("chunk", C.c_uint64),
+                ("launch", C.c_uint32), ("wave", C.c_uint32)]
+
+
 class CommOps(C.Structure):
     _fields_ = [("user", vp), ("all_gather", ALL_GATHER_FN), ("all_to_all_v", ALL_TO_ALL_V_FN),
                 ("broadcast", BROADCAST_FN)]
@@ -201,6 +214,8 @@ SIGNATURES = {
     "lcpc_pos_left_multiply_bytes_grouped_device": (i32, [vp, szp, szp, szp, sz, u64p, sz, u64p, sz]),
     "lcpc_pos_group_plan": (i32, [szp, szp, sz, C.POINTER(PosGroupTile), sz, szp, szp]),
     "lcpc_field_to_montgomery": (i32, [i32, u64p, u64p, sz]),
+    "lcpc_pos_verify_evaluations_grouped": (i32, [C.POINTER(PosAuditJob), sz, u8p, u64p]),
+    "lcpc_pos_verify_group_plan": (i32, [szp, szp, szp, sz, C.POINTER(PosVerifyTile), sz, szp, szp]),
     "lcpc_pos_update_rows": (i32, [sz, sz, sz, sz, szp, szp, szp, szp]),
     "lcpc_pos_update_evaluation": (i32, [vp, vp, sz, vp, vp, sz, u64p, u64p, sz, u64p, sz,
                                          u64p, u64p, u8p, u8p, u64p, u64p, u8p, u8p, u64p]),

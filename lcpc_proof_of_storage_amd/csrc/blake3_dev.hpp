@@ -129,24 +129,25 @@ struct CmEval {
   size_t row0 = 0;
 };
 
-template <class F, bool CANON, bool SLICE, bool EVAL = false>
-__device__ __forceinline__ void leaf_chunks_cm_body(const uint32_t *__restrict__ m, size_t n_rows, size_t n_cols,
-                                                    uint32_t *__restrict__ cvs, uint8_t *__restrict__ leaves,
-                                                    int n_chunks, int fuse2, const CmSlice &sl,
-                                                    const CmEval &ev = CmEval{}) {
+// One chunk of one wave's 64 columns [col0, col0 + 64) of m (column c at m + c * col_words words, its
+// word 0 being message word w_base): the chunk's blocks staged through the wave's LDS rows `stage`,
+// the next block's loads in flight while this one compresses; cv = the chunk's chaining value (ROOT
+// when n_chunks == 1).  TAIL: the message may end inside a 4-word unit (n_rows odd), the words past it
+// are zeroed.  CHECK: noncanon |= an element is not < p.  EVAL: acc += sum over the chunk's rows r of
+// weights[r - row0] * element r (the element as loaded; the row is the same in every lane, so a
+// wave-uniform weights pointer makes the weight loads scalar).  Every caller passes wave-uniform
+// arguments but for the lane's own cv / acc / noncanon.
+template <class F, bool CANON, bool TAIL, bool CHECK, bool EVAL>
+__device__ __forceinline__ void cm_chunk_cv(uint4 (*__restrict__ stage)[5], const uint32_t *__restrict__ m,
+                                            size_t n_rows, size_t n_cols, size_t col0, size_t col_words,
+                                            size_t w_base, int chunk, int n_chunks,
+                                            const uint32_t *__restrict__ weights, size_t row0, uint32_t cv[8],
+                                            Fe<F> &acc, bool &noncanon) {
   constexpr int N = F::N;
-  static_assert(16 % N == 0 && 8 % N == 0, "element must tile a BLAKE3 block");
-  static_assert(!EVAL || SLICE, "the weighted sums ride on slice launches");
   constexpr int EPB = 16 / N;
-  __shared__ uint4 stage[4][64][5];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const size_t col0 = ((size_t)blockIdx.x * 4 + wave) * 64, col = col0 + lane;
-  if (col0 >= n_cols) return;  // whole waves
+  const int lane = threadIdx.x & 63;
   const size_t msg_words = 8 + n_rows * N;  // the column's message, in words
-  const size_t col_words = SLICE ? sl.col_words : n_rows * N, w_base = SLICE ? sl.w_base : 8;
   const int unit = lane & 3, csub = lane >> 2;
-  bool noncanon = false;
-  Fe<F> acc = fe_zero<F>();
   // block b (of the chunk starting at message word w0): this lane's 4 loads, unit `unit` (words
   // 4 unit .. +3) of column col0 + csub + 16 i
   auto gload = [&](size_t w0, int b, uint4 r[4]) {
@@ -157,7 +158,7 @@ __device__ __forceinline__ void leaf_chunks_cm_body(const uint32_t *__restrict__
       const size_t c = col0 + csub + 16 * i;
       r[i] = in && c < n_cols ? reinterpret_cast<const uint4 *>(m + c * col_words + (w - w_base))[0]
                               : make_uint4(0, 0, 0, 0);
-      if constexpr (SLICE) {  // the message ends inside this unit (msg_words is even)
+      if constexpr (TAIL) {  // the message ends inside this unit (msg_words is even)
         if (w + 2 == msg_words) r[i].z = r[i].w = 0;
       }
     }
@@ -169,61 +170,79 @@ __device__ __forceinline__ void leaf_chunks_cm_body(const uint32_t *__restrict__
   };
   auto lput = [&](const uint4 r[4]) {
 #pragma unroll
-    for (int i = 0; i < 4; i++) stage[wave][csub + 16 * i][unit] = r[i];
+    for (int i = 0; i < 4; i++) stage[csub + 16 * i][unit] = r[i];
     wave_sync();
   };
-  // one chunk's chaining value (its blocks staged through LDS, the next block's loads in flight
-  // while this one compresses)
-  auto chunk_cv = [&](int chunk, uint32_t cv[8]) {
-    const size_t w0 = (size_t)chunk * 256;
-    const size_t cw = msg_words - w0 < 256 ? msg_words - w0 : 256;
-    const int nb = (int)((cw + 15) / 16);
-    iv(cv);
-    uint4 r[4];
-    gload(w0, 0, r);
-    lput(r);
-    for (int b = 0; b < nb; b++) {
-      const bool more = b + 1 < nb;
-      if (more) gload(w0, b + 1, r);
-      uint32_t msg[16];
-      {
-        const uint4 *row = stage[wave][lane];
+  const size_t w0 = (size_t)chunk * 256;
+  const size_t cw = msg_words - w0 < 256 ? msg_words - w0 : 256;
+  const int nb = (int)((cw + 15) / 16);
+  iv(cv);
+  uint4 r[4];
+  gload(w0, 0, r);
+  lput(r);
+  for (int b = 0; b < nb; b++) {
+    const bool more = b + 1 < nb;
+    if (more) gload(w0, b + 1, r);
+    uint32_t msg[16];
+    {
+      const uint4 *row = stage[lane];
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-          const uint4 q = row[k];
-          msg[4 * k] = q.x; msg[4 * k + 1] = q.y; msg[4 * k + 2] = q.z; msg[4 * k + 3] = q.w;
-        }
+      for (int k = 0; k < 4; k++) {
+        const uint4 q = row[k];
+        msg[4 * k] = q.x; msg[4 * k + 1] = q.y; msg[4 * k + 2] = q.z; msg[4 * k + 3] = q.w;
       }
-      wave_sync();  // every lane has read block b before block b + 1 overwrites the stage
-      // element words -> repr words (Montgomery -> canonical unless CANON); the zero prefix and
-      // words past the message stay zero either way (from_mont(0) = 0, and they load as zero)
-#pragma unroll
-      for (int k = 0; k < EPB; k++) {
-        Fe<F> e;
-#pragma unroll
-        for (int i = 0; i < N; i++) e.v[i] = msg[k * N + i];
-        if constexpr (SLICE) noncanon |= !fe_is_canonical<F>(e);  // (prefix and tail words are zero)
-        if constexpr (EVAL) {
-          // the element's message word and row (the same in every lane); the prefix and the pad
-          // past an odd row count hold no element
-          const size_t ew = w0 + 16 * (size_t)b + (size_t)k * N;
-          if (ew >= 8 && ew < msg_words) acc = fe_add<F>(acc, fe_mul<F>(fe_load<F>(ev.weights, (ew - 8) / N - ev.row0), e));
-        }
-        uint32_t w[N];
-        if constexpr (CANON)
-          fe_canon_repr_words<F>(e, w);
-        else
-          fe_repr_words<F>(e, w);
-#pragma unroll
-        for (int i = 0; i < N; i++) msg[k * N + i] = w[i];
-      }
-      const size_t left = cw - 16 * (size_t)b;
-      const uint32_t blen = left >= 16 ? 64u : (uint32_t)(4 * left);
-      uint32_t flags = b == 0 ? CHUNK_START : 0u;
-      if (b == nb - 1) flags |= CHUNK_END | (n_chunks == 1 ? ROOT : 0u);
-      compress(cv, msg, (uint64_t)chunk, blen, flags);
-      if (more) lput(r);
     }
+    wave_sync();  // every lane has read block b before block b + 1 overwrites the stage
+    // element words -> repr words (Montgomery -> canonical unless CANON); the zero prefix and
+    // words past the message stay zero either way (from_mont(0) = 0, and they load as zero)
+#pragma unroll
+    for (int k = 0; k < EPB; k++) {
+      Fe<F> e;
+#pragma unroll
+      for (int i = 0; i < N; i++) e.v[i] = msg[k * N + i];
+      if constexpr (CHECK) noncanon |= !fe_is_canonical<F>(e);  // (prefix and tail words are zero)
+      if constexpr (EVAL) {
+        // the element's message word and row (the same in every lane); the prefix and the pad
+        // past an odd row count hold no element
+        const size_t ew = w0 + 16 * (size_t)b + (size_t)k * N;
+        if (ew >= 8 && ew < msg_words) acc = fe_add<F>(acc, fe_mul<F>(fe_load<F>(weights, (ew - 8) / N - row0), e));
+      }
+      uint32_t w[N];
+      if constexpr (CANON)
+        fe_canon_repr_words<F>(e, w);
+      else
+        fe_repr_words<F>(e, w);
+#pragma unroll
+      for (int i = 0; i < N; i++) msg[k * N + i] = w[i];
+    }
+    const size_t left = cw - 16 * (size_t)b;
+    const uint32_t blen = left >= 16 ? 64u : (uint32_t)(4 * left);
+    uint32_t flags = b == 0 ? CHUNK_START : 0u;
+    if (b == nb - 1) flags |= CHUNK_END | (n_chunks == 1 ? ROOT : 0u);
+    compress(cv, msg, (uint64_t)chunk, blen, flags);
+    if (more) lput(r);
+  }
+}
+
+template <class F, bool CANON, bool SLICE, bool EVAL = false>
+__device__ __forceinline__ void leaf_chunks_cm_body(const uint32_t *__restrict__ m, size_t n_rows, size_t n_cols,
+                                                    uint32_t *__restrict__ cvs, uint8_t *__restrict__ leaves,
+                                                    int n_chunks, int fuse2, const CmSlice &sl,
+                                                    const CmEval &ev = CmEval{}) {
+  constexpr int N = F::N;
+  static_assert(16 % N == 0 && 8 % N == 0, "element must tile a BLAKE3 block");
+  static_assert(!EVAL || SLICE, "the weighted sums ride on slice launches");
+  __shared__ uint4 stage[4][64][5];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const size_t col0 = ((size_t)blockIdx.x * 4 + wave) * 64, col = col0 + lane;
+  if (col0 >= n_cols) return;  // whole waves
+  const size_t col_words = SLICE ? sl.col_words : n_rows * N, w_base = SLICE ? sl.w_base : 8;
+  bool noncanon = false;
+  Fe<F> acc = fe_zero<F>();
+  // one chunk's chaining value (cm_chunk_cv)
+  auto chunk_cv = [&](int chunk, uint32_t cv[8]) {
+    cm_chunk_cv<F, CANON, SLICE, SLICE, EVAL>(stage[wave], m, n_rows, n_cols, col0, col_words, w_base, chunk, n_chunks,
+                                              ev.weights, ev.row0, cv, acc, noncanon);
   };
   uint32_t cv[8];
   if (fuse2) {

@@ -95,4 +95,32 @@ hipError_t pos_group_left_mul(const uint8_t *arena, const PosGroupJob *jobs, con
                               const PosGroupWave *waves, size_t n_waves, const PosGroupFold *folds, size_t n_folds,
                               const uint32_t *lefts, uint32_t *res, hipStream_t s);
 
+// ---- pos_verify_group.hip: many stored-file audit responses checked in one pass
+// The host builds the tables of a launch (pos_verify_group_host.cpp).
+//   job    n_cols opened columns of n_rows Montgomery elements, staged at byte offset cols of the
+//          launch's arena (a multiple of 16), column k at cols + k * col_words * 4 (col_words = 2 n_rows
+//          rounded up to 4 words, the pad zero); their Merkle paths (n_cols x path_len x 32 B) at byte
+//          offset paths; the left vector at element left of the lefts; the job's columns are
+//          [col0, col0 + n_cols) of the launch's per-column arrays (idx, want, bits) and the chaining
+//          value and partial sum of (chunk, column k) are slot cv0 + chunk * n_cols + k of cvs / partials
+//   wave   columns [col_lo, min(col_lo + 64, n_cols)) of one job, a lane each, and one 1-KiB chunk of
+//          their leaf messages (k_group_leaf_dot); the finish launch has one wave per 64 columns of a job
+struct PosVerifyJob {
+  uint64_t cols, paths, left, col0, cv0;
+  uint32_t n_rows, n_cols, n_chunks, path_len, col_words, pad;
+};
+struct PosVerifyWave {
+  uint32_t job, col_lo, chunk, pad;
+};
+constexpr size_t POS_VERIFY_MAX_CHUNKS = (size_t)1 << 16;  // chunks of one column's leaf (the fold's stack)
+// The two launches of a staging group: k_group_leaf_dot over n_waves waves (4 per workgroup) leaves
+// every (chunk, column)'s chaining value and its share of sum_r left[r] col[r]; k_group_leaf_finish
+// over n_fwaves waves folds each column's leaf, walks its path to its job's root (roots: 32 B per
+// job) and compares its sum with want: bits[col] = (path leads to the root) | (sum == want) << 1.
+// max_chunks: the largest n_chunks of the launch's jobs (<= POS_VERIFY_MAX_CHUNKS).
+hipError_t pos_group_verify(const uint8_t *arena, const PosVerifyJob *jobs, const PosVerifyWave *waves, size_t n_waves,
+                            const PosVerifyWave *fwaves, size_t n_fwaves, size_t max_chunks, const uint32_t *lefts,
+                            const uint8_t *roots, const uint64_t *idx, const uint32_t *want, uint32_t *cvs,
+                            uint32_t *partials, uint32_t *bits, hipStream_t s);
+
 }  // namespace lcpc

@@ -24,15 +24,7 @@ constexpr size_t GROUP_MAX_JOBS = (size_t)1 << 16, GROUP_MAX_OUT_WORDS = (size_t
 inline size_t ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
 
-// Image bytes per staging group.  LCPC_POS_GROUP_BYTES (a test seam, read at every call) can only
-// lower it; zero or an unparsable value is ignored.
-size_t group_bytes() {
-  if (const char *env = std::getenv("LCPC_POS_GROUP_BYTES")) {
-    const unsigned long long v = std::strtoull(env, nullptr, 10);
-    if (v) return std::min<size_t>(LCPC_POS_GROUP_STAGE_BYTES, (size_t)v);
-  }
-  return LCPC_POS_GROUP_STAGE_BYTES;
-}
+size_t group_bytes() { return pos_group_bytes(); }
 
 inline size_t job_rows(size_t n_bytes, size_t pre) { return ceil_div(ceil_div(n_bytes, POS_DB), pre); }
 

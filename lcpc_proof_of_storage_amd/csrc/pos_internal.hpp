@@ -1,5 +1,5 @@
 // pos_internal.hpp -- what the proof-of-storage host units share (lcpc_host.cpp, pos_files_host.cpp,
-// pos_repair_host.cpp, pos_group_host.cpp): constants, page-locked staging, argument checks and the device-side steps
+// pos_repair_host.cpp, pos_group_host.cpp, pos_verify_group_host.cpp): constants, page-locked staging, argument checks and the device-side steps
 // that more than one entry point runs.  The image's host side is pos_image.hpp.  Stateless, inline.
 #pragma once
 #include "host_internal.hpp"
@@ -22,6 +22,17 @@ inline size_t pos_stage_bytes() {
     if (v) return std::min<size_t>(budget, (size_t)v);
   }
   return budget;
+}
+
+// Bytes per staging group of the grouped stored-file entries (pos_group_host.cpp: image bytes;
+// pos_verify_group_host.cpp: column bytes).  LCPC_POS_GROUP_BYTES (a test seam, read at every call)
+// can only lower it; zero or an unparsable value is ignored.
+inline size_t pos_group_bytes() {
+  if (const char *env = std::getenv("LCPC_POS_GROUP_BYTES")) {
+    const unsigned long long v = std::strtoull(env, nullptr, 10);
+    if (v) return std::min<size_t>(LCPC_POS_GROUP_STAGE_BYTES, (size_t)v);
+  }
+  return LCPC_POS_GROUP_STAGE_BYTES;
 }
 
 // a page-locked block from the device's pool, returned at scope exit

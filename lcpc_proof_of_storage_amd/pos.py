@@ -31,6 +31,7 @@ checkable read, read_plan / ReadOpening / client_verify_read (§5e).
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 import math
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
@@ -772,10 +773,13 @@ def _file_rows(n_bytes: int, pre: int) -> int:
     return -(-(-(-n_bytes // DATA_BYTE_CAPACITY)) // pre)
 
 
-def _checked_file_evaluation(root: bytes, n_bytes: int, pre: int, enc: int, point, cols, result_vector,
+def client_verify_evaluation(root: bytes, n_bytes: int, pre: int, enc: int, point, cols, result_vector,
                              columns: Sequence[LcColumn]) -> np.ndarray:
-    """Checks 1 and 2 for one version: the opened columns hash up to root, and the decoded result
-    vector, re-encoded, agrees with them; returns the file polynomial's value at the point."""
+    """The client's check of one plain audit response (FileHandler.polynomial_evaluation_response):
+    the opened columns hash up to root, and the decoded result vector, re-encoded, agrees with them
+    (checks 1 and 2 of the update audits, for one version); returns the file polynomial's value at
+    the point.  Raises VerifierError (ColumnEval); non-increasing columns raise ValueError.  Many
+    responses at once: client_verify_evaluations_grouped."""
     cols = [int(c) for c in cols]
     if any(b <= a for a, b in zip(cols, cols[1:])):
         raise ValueError("requested columns must be strictly increasing")
@@ -789,6 +793,9 @@ def _checked_file_evaluation(root: bytes, n_bytes: int, pre: int, enc: int, poin
     # side vectors over (n_rows, pre): the left stride is pre, so the value is the file polynomial's
     left, right = form_side_vectors_for_polynomial_evaluation_from_point(point, n_rows, pre)
     return verifiable_full_polynomial_evaluation(left, right, decode_row(res), cols, columns, pre, enc)
+
+
+_checked_file_evaluation = client_verify_evaluation   # the name the update audits know it by
 
 
 def client_verify_reshape_evaluation(old_root: bytes, new_root: bytes, file_len: int, old_dims, new_dims, point,
@@ -1171,6 +1178,100 @@ def left_multiply_group_plan(sizes, pres):
                                  tiles.ctypes.data_as(C.POINTER(N.PosGroupTile)), tiles.size, C.byref(n),
                                  C.byref(launches)))
     return tiles, launches.value
+
+
+def verify_group_plan(file_lens, pres, n_cols):
+    """lcpc_pos_verify_group_plan: (tiles, n_launches) for audit responses over files of file_lens[j]
+    bytes with rows of pres[j] elements and n_cols[j] opened columns.  tiles is a structured array with
+    the fields job, col_lo, col_hi, chunk, launch and wave: the work list of the first launch of every
+    staging group client_verify_evaluations_grouped makes, a job routed to the single sequence as one
+    record per chunk with launch == GROUP_SINGLE.  Host only, a pure function."""
+    nb, pr, nc = _sizes(file_lens), _sizes(pres), _sizes(n_cols)
+    if not (nb.size == pr.size == nc.size):
+        raise ValueError("file_lens, pres and n_cols must have one entry per job")
+    n, launches = C.c_size_t(), C.c_size_t()
+    L = N.load()
+    args = (nb.ctypes.data_as(N.szp), pr.ctypes.data_as(N.szp), nc.ctypes.data_as(N.szp), nb.size)
+    _raise(L.lcpc_pos_verify_group_plan(*args, None, 0, C.byref(n), C.byref(launches)))
+    dt = np.dtype([("job", "<u8"), ("col_lo", "<u8"), ("col_hi", "<u8"), ("chunk", "<u8"), ("launch", "<u4"),
+                   ("wave", "<u4")])
+    assert dt.itemsize == C.sizeof(N.PosVerifyTile)
+    tiles = np.zeros(n.value, dt)
+    _raise(L.lcpc_pos_verify_group_plan(*args, tiles.ctypes.data_as(C.POINTER(N.PosVerifyTile)), tiles.size,
+                                        C.byref(n), C.byref(launches)))
+    return tiles, launches.value
+
+
+def client_verify_evaluations_grouped(audits) -> list:
+    """client_verify_evaluation for a queue of responses in one call
+    (lcpc_pos_verify_evaluations_grouped): audits is a sequence of its argument tuples (root, file_len,
+    pre, enc, point, cols, result_vector, columns).  Returns a list: entry i is the evaluation array
+    client_verify_evaluation returns for audit i, word for word, or the VerifierError (ColumnEval) it
+    would raise, as an instance that is not raised; its message names paths or values.  The launches are
+    per staging group of responses, not per response.  The caller's own mistakes raise ValueError before
+    any device work: non-increasing or out-of-range columns, dims the audits cannot have.  What the
+    single check rejects from shapes alone (a wrong column count, a column that is not the file's row
+    count long, a result vector that is not enc words, a digest that is not 32 bytes, paths of the
+    wrong length) is that entry's VerifierError, and the job never reaches the library."""
+    audits = list(audits)
+    out: list = [None] * len(audits)
+    jobs, keep, live = [], [], []
+    for i, (root, file_len, pre, enc, point, cols, result_vector, columns) in enumerate(audits):
+        file_len, pre, enc = int(file_len), int(pre), int(enc)
+        idx = np.ascontiguousarray(np.asarray(list(cols), dtype=np.int64).reshape(-1))
+        if idx.size > 1 and not (np.diff(idx) > 0).all():
+            raise ValueError(f"audit {i}: requested columns must be strictly increasing")
+        if file_len < 1 or pre < 1 or enc <= pre or enc & (enc - 1):
+            raise ValueError(f"audit {i}: needs a non-empty file and enc a power of two > pre")
+        if idx.size and (idx[0] < 0 or idx[-1] >= enc):
+            raise ValueError(f"audit {i}: requested columns must be below enc")
+        n_rows, plen = _file_rows(file_len, pre), enc.bit_length() - 1
+        columns = list(columns)
+        arrs = [np.asarray(c.col, dtype=np.uint64) for c in columns]
+        if len(columns) != idx.size or {a.size for a in arrs} - {n_rows}:
+            out[i] = _verifier_error("ColumnEval", "opened columns do not have the file's row count")
+            continue
+        res = np.ascontiguousarray(np.asarray(result_vector, dtype=np.uint64).reshape(-1))
+        if res.size != enc:
+            out[i] = _verifier_error("ColumnEval", "result vector is not one encoded row")
+            continue
+        if set(map(len, (c.path for c in columns))) - {plen}:
+            out[i] = _verifier_error("ColumnEval", "Merkle paths of the wrong length")
+            continue
+        digests = list(itertools.chain.from_iterable(c.path for c in columns))
+        rt = bytes(root)
+        if len(rt) != 32 or set(map(len, digests)) - {32}:
+            out[i] = _verifier_error("ColumnEval", "a path digest is not 32 bytes")
+            continue
+        paths = b"".join(digests)
+        try:     # columns of one shape, (n_rows, 1) as a commitment opens them: one copy
+            cm = np.concatenate(arrs) if arrs else np.zeros(0, np.uint64)
+        except ValueError:
+            cm = np.concatenate(arrs, axis=None)
+        pb = np.frombuffer(paths, np.uint8) if paths else np.zeros(0, np.uint8)
+        rb = np.frombuffer(rt, np.uint8)
+        iu = idx.astype(np.uint64)
+        x = int(np.asarray(point, dtype=np.uint64).reshape(-1)[0])
+        keep.append((cm, pb, rb, iu, res))
+        jobs.append(N.PosAuditJob(rb.ctypes.data, file_len, pre, enc, x, iu.ctypes.data if iu.size else None,
+                                  iu.size, cm.ctypes.data if iu.size else None, pb.ctypes.data if iu.size else None,
+                                  res.ctypes.data))
+        live.append(i)
+    if not jobs:
+        return out
+    arr = (N.PosAuditJob * len(jobs))(*jobs)
+    verdict = np.zeros(len(jobs), np.uint8)
+    values = np.zeros(len(jobs), np.uint64)
+    _raise(N.load().lcpc_pos_verify_evaluations_grouped(arr, len(jobs), verdict.ctypes.data_as(N.u8p), _p64(values)))
+    del keep
+    for k, i in enumerate(live):
+        if verdict[k] == 0:
+            out[i] = values[k:k + 1].reshape(1, 1).copy()
+        elif verdict[k] == 1:
+            out[i] = _verifier_error("ColumnEval", "Merkle path mismatch (paths)")
+        else:
+            out[i] = _verifier_error("ColumnEval", "column value mismatch (values)")
+    return out
 
 
 def field_to_montgomery(values, field: int = FT63) -> np.ndarray:
