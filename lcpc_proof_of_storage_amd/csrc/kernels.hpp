@@ -47,6 +47,14 @@ struct NttPlan {
   // measured choice: the one-pass kernel for file images, the four-step pair for element rows),
   // _FOURSTEP or _ONEPASS (lcpc_encoding_set_row_kernel)
   int row_kernel = 0;
+  // the persistent passes' grid (ntt_v2.hpp, LCPC_NTT_PERSIST): the blocks the device holds at
+  // once, blocks per CU at the kernels' LDS / VGPR footprint times the CU count, taken once at
+  // plan init; 0 where the plan's passes have no persistent form (they launch one workgroup per
+  // tile).  LCPC_NTT_PERSIST_GRID=<n> in the environment at plan init gives the grid instead
+  // (persist_grid_forced: taken as it stands, not rounded to the column groups); any grid is
+  // correct, the tests walk small ones.
+  size_t persist_grid = 0;
+  bool persist_grid_forced = false;
 };
 // the longest sub-FFT whose block stages word-expanded twiddles: 2^(L-1) entries of 64 bytes beside
 // the tile (16 KiB at L = 9; at L = 12 the table alone would be 128 KiB of a CU's 160)

@@ -2,6 +2,8 @@
 #include "kernels.hpp"
 #include "field.hpp"
 
+#include <cstdlib>
+
 namespace lcpc {
 
 #define DECL(n)                                                                                   \
@@ -16,6 +18,9 @@ DECL(ft253)
 #undef DECL
 hipError_t ntt_tw4_table_ft127(const uint32_t *, size_t, size_t, uint32_t *, hipStream_t);
 bool ntt_tw4_enabled();  // ntt_ft127.hip: the build's LCPC_NTT_TW4
+// ntt_ft127.hip: blocks per CU of the plan's persistent passes (the smaller of the two), 0 if the
+// build (LCPC_NTT_PERSIST) or the plan's shape has none; the plan's tables are not read
+int ntt_persist_blocks_per_cu_ft127(const NttPlan &p);
 
 namespace {
 // out[(t << l2) + c] = tw[c * bitrev_l1(t)]: an element copy of `words` u32 words
@@ -88,14 +93,35 @@ hipError_t ntt_plan_init(NttPlan &p, int fid, int log_n, bool inverse, hipStream
       if ((e = ntt_tw4_table(fid, p.d_tw, (size_t)1 << p.l1, nb, p.d_tw4 + na * 16, s)) != hipSuccess) return e;
     }
   }
-  if (inverse) return hipSuccess;
-  // canonical words of w^e = Montgomery words of w^e R^-1 (canon_out encodes)
-  e = hipMalloc(&p.d_tw_canon, n * field_bytes(fid));
-  if (e != hipSuccess) return e;
-  if ((e = convert(fid, p.d_tw, p.d_tw_canon, n, false, s)) != hipSuccess) return e;
-  if (log_n > 12) {
-    if ((e = hipMalloc(&p.d_tw2_canon, n * field_bytes(fid))) != hipSuccess) return e;
-    if ((e = ntt_tw2_table(fid, p.d_tw_canon, log_n, p.l1, p.d_tw2_canon, s)) != hipSuccess) return e;
+  if (!inverse) {
+    // canonical words of w^e = Montgomery words of w^e R^-1 (canon_out encodes)
+    e = hipMalloc(&p.d_tw_canon, n * field_bytes(fid));
+    if (e != hipSuccess) return e;
+    if ((e = convert(fid, p.d_tw, p.d_tw_canon, n, false, s)) != hipSuccess) return e;
+    if (log_n > 12) {
+      if ((e = hipMalloc(&p.d_tw2_canon, n * field_bytes(fid))) != hipSuccess) return e;
+      if ((e = ntt_tw2_table(fid, p.d_tw_canon, log_n, p.l1, p.d_tw2_canon, s)) != hipSuccess) return e;
+    }
+  }
+  p.persist_grid = 0;
+  p.persist_grid_forced = false;
+  if (fid == 1 && log_n > 12) {
+    // the persistent passes' grid (kernels.hpp, NttPlan::persist_grid); the override is read here,
+    // per plan, so one process can hold encodings with different grids
+    const int bpc = ntt_persist_blocks_per_cu_ft127(p);
+    if (bpc > 0) {
+      int dev = 0, cus = 0;
+      if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
+      if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
+      p.persist_grid = (size_t)bpc * (size_t)(cus > 0 ? cus : 1);
+      if (const char *g = std::getenv("LCPC_NTT_PERSIST_GRID")) {
+        const long v = std::atol(g);
+        if (v > 0) {
+          p.persist_grid = (size_t)v;
+          p.persist_grid_forced = true;
+        }
+      }
+    }
   }
   return hipSuccess;
 }

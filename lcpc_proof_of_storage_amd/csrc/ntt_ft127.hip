@@ -18,4 +18,11 @@ hipError_t ntt_tw4_table_ft127(const uint32_t *tw, size_t stride, size_t count, 
   return hipGetLastError();
 }
 bool ntt_tw4_enabled() { return LCPC_NTT_TW4 != 0; }
+int ntt_persist_blocks_per_cu_ft127(const NttPlan &p) {
+  // the rate-1/2 commit's instantiations (HALFZ, canonical output on forward plans)
+  int bpc = 1 << 30;
+  const hipError_t e = ntt_detail::ntt_rows_t<Ft127>(p, nullptr, 0, ((size_t)1 << p.log_n) / 2, nullptr, 0, 1, nullptr,
+                                                     nullptr, 0, !p.inverse, &bpc);
+  return e == hipSuccess && bpc != (1 << 30) ? bpc : 0;
+}
 }  // namespace lcpc

@@ -150,8 +150,11 @@ __global__ void k_from_mont_rows(uint32_t *__restrict__ m, size_t stride, size_t
 
 template <class F>
 hipError_t ntt_rows_t(const NttPlan &p, const uint32_t *src, size_t ss, size_t nv, uint32_t *dst,
-                      size_t ds, size_t n_rows, hipStream_t s, uint32_t *cp, size_t cs, bool canon) {
-  if (n_rows == 0) return hipSuccess;
+                      size_t ds, size_t n_rows, hipStream_t s, uint32_t *cp, size_t cs, bool canon,
+                      int *query = nullptr) {
+  // query (ntt_plan_init, log_n > 12): nothing runs; *query is lowered to the blocks per CU of the
+  // persistent kernels these arguments would launch (untouched where the shape has none)
+  if (n_rows == 0 && !query) return hipSuccess;
   if (canon && !p.d_tw_canon) return hipErrorInvalidValue;
   if (p.log_n > 12 && !(canon ? p.d_tw2_canon : p.d_tw2)) return hipErrorInvalidValue;
   if (p.log_n == 0) {  // length-1 transform is the identity (fffft returns early)
@@ -188,12 +191,42 @@ hipError_t ntt_rows_t(const NttPlan &p, const uint32_t *src, size_t ss, size_t n
   // multiply by the word-expanded twiddles of d_tw4, everything else by the flat table's elements.
   if (LCPC_NTT_TW4 && F::ID == 1 && ntt_tw4_entries(p.l1) + ntt_tw4_entries(p.l2) && !p.d_tw4)
     return hipErrorInvalidValue;
+  // The persistent form (ntt_v2.hpp, LCPC_NTT_PERSIST): Ft127 at the default tile shape, passes
+  // that stage their twiddles beside a tile of at most 2^NTT_TW4_MAX_L points.  The grid is the
+  // plan's resident blocks, for pass A rounded down to a multiple of the groups per row so that a
+  // workgroup keeps its column group (an overridden grid is taken as given); a plan without the
+  // count (made by hand) takes the one-tile kernels.
+  auto persist_grid = [&](int log_groups) {
+    size_t g = p.persist_grid;
+    const size_t groups = (size_t)1 << log_groups;
+    if (!p.persist_grid_forced && g > groups) g -= g % groups;
+    return g;
+  };
   auto pass_a = [&]<int L, int CW, int T = L + CW - R>() {
     constexpr bool TW4 = LCPC_NTT_TW4 && LCPC_NTT_TW4_A && F::ID == 1 && L <= NTT_TW4_MAX_L;
     using TW = std::conditional_t<TW4, ntt_v2::TwWords<F>, ntt_v2::TwLib<F>>;
     const uint32_t *tw = TW4 ? p.d_tw4 : p.d_tw;
     // the inter-pass twiddles in [t][c] layout (canonical words for canon_out)
     const uint32_t *t2 = canon ? p.d_tw2_canon : p.d_tw2;
+    if constexpr (LCPC_NTT_PERSIST && F::ID == 1 && L <= NTT_TW4_MAX_L && L + CW == E && R < L) {
+      if (query || p.persist_grid > 0) {
+        const size_t g = persist_grid(p.log_n - L - CW);
+        // Register budget (three blocks per CU: 168 VGPRs, no scratch): rate-1/2 rows prefetch 16
+        // VGPRs and keep their 2^R inter-pass twiddles resident (32), except the 64-point columns
+        // of 2^13-point rows, which reload them per tile (12 bytes of scratch per lane with
+        // both); full-length rows would prefetch 32 VGPRs and spill with the resident twiddles
+        // (84-120 bytes per lane) and at 2^8 points without them (48), so they only loop
+        constexpr bool W2 = L >= 8;
+        if (halfz && canon)
+          return ntt_v2::launch_a_loop<F, L, CW, T, true, true, TW, true, W2>(src, ss, nv, dst, ds, tw, p.log_n, n_rows, s, cp, cs, t2, g, query);
+        if (halfz)
+          return ntt_v2::launch_a_loop<F, L, CW, T, true, false, TW, true, W2>(src, ss, nv, dst, ds, tw, p.log_n, n_rows, s, cp, cs, t2, g, query);
+        if (canon)
+          return ntt_v2::launch_a_loop<F, L, CW, T, false, true, TW, false, false>(src, ss, nv, dst, ds, tw, p.log_n, n_rows, s, cp, cs, t2, g, query);
+        return ntt_v2::launch_a_loop<F, L, CW, T, false, false, TW, false, false>(src, ss, nv, dst, ds, tw, p.log_n, n_rows, s, cp, cs, t2, g, query);
+      }
+    }
+    if (query) return hipSuccess;
     if (halfz && canon)
       return ntt_v2::launch_a<F, L, CW, T, true, true, TW>(src, ss, nv, dst, ds, tw, p.log_n, n_rows, s, cp, cs, t2);
     if (halfz)
@@ -205,6 +238,12 @@ hipError_t ntt_rows_t(const NttPlan &p, const uint32_t *src, size_t ss, size_t n
   auto pass_b = [&]<int L, int CW, int T = L + CW - R>() {
     constexpr bool TW4 = LCPC_NTT_TW4 && F::ID == 1 && L <= NTT_TW4_MAX_L;
     using TW = std::conditional_t<TW4, ntt_v2::TwWords<F>, ntt_v2::TwLib<F>>;
+    if constexpr (LCPC_NTT_PERSIST && LCPC_NTT_PERSIST_B && F::ID == 1 && L <= NTT_TW4_MAX_L && L + CW == E && R < L) {
+      if (query || p.persist_grid > 0)
+        return ntt_v2::launch_b_loop<F, L, CW, T, TW>(dst, ds, TW4 ? ntt_tw4_b(p) : p.d_tw, p.log_n, n_rows, s,
+                                                      p.persist_grid, query);
+    }
+    if (query) return hipSuccess;
     return ntt_v2::launch_b<F, L, CW, T, TW>(dst, ds, TW4 ? ntt_tw4_b(p) : p.d_tw, p.log_n, n_rows, s);
   };
   hipError_t e;

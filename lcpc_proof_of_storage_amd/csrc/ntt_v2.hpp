@@ -40,6 +40,22 @@
 #define LCPC_NTT_TW4_A 1
 #endif
 
+// LCPC_NTT_PERSIST (default 1): Ft127's pass A of at most 2^NTT_TW4_MAX_L points at the default
+// tile shape runs as a persistent tile loop (k_pass_a_loop; pass B: LCPC_NTT_PERSIST_B) on a grid
+// of the resident blocks.  0 builds the one-tile-per-workgroup kernels everywhere (tools/ab_lib.py
+// runs one build against the other).
+#ifndef LCPC_NTT_PERSIST
+#define LCPC_NTT_PERSIST 1
+#endif
+// LCPC_NTT_PERSIST_B (default 0; an A/B switch under LCPC_NTT_PERSIST, as LCPC_NTT_TW4_A is under
+// LCPC_NTT_TW4): 0 pass B stays on the one-tile kernel while pass A loops, 1 it loops and
+// prefetches too (k_pass_b_loop).  Measured: the looping pass B is 14 % slower
+// alone (0.344 against 0.302 ms) and about 1 % faster inside the pipelined bench, which is within
+// twice the parent's run-to-run spread.
+#ifndef LCPC_NTT_PERSIST_B
+#define LCPC_NTT_PERSIST_B 0
+#endif
+
 namespace lcpc {
 namespace ntt_v2 {
 
@@ -302,6 +318,272 @@ __global__ __launch_bounds__(1 << LOG_T) void k_pass_b(uint32_t *__restrict__ da
     fe_store<F>(io, idx, tile[t * LD + v]);
 #endif
   }
+}
+
+// ---- persistent passes (LCPC_NTT_PERSIST): a workgroup walks tiles blockIdx.x, + gridDim.x, ...
+// Same arithmetic per element as k_pass_a / k_pass_b; what a one-tile workgroup paid per tile is
+// paid once per workgroup or overlapped:
+//   * the sub-FFT twiddles are staged before the loop;
+//   * PF: tile i+1's round-0 loads are issued into a second register set before tile i's last
+//     round (same pos < n_valid predicate; none when there is no next tile), and pass A's fused
+//     coefficient-copy stores go out from those registers at the top of the next iteration;
+//   * TW2R (pass A): when gridDim.x is a multiple of the groups per row a workgroup's tiles differ
+//     only in the row, so a thread's 2^R inter-pass twiddles are loaded once, before the loop;
+//     for any other grid the launcher takes the instantiation that loads them per tile as
+//     k_pass_a does.
+// Tiles are independent and no workgroup waits for another, so any grid size is correct; the
+// launcher sizes it to the resident blocks (NttPlan::persist_grid).
+// The second launch bound keeps three 256-thread blocks per CU (168 VGPRs).
+// A use of r's registers that costs no instruction: the compiler's wait for the loads that fill
+// them lands here.  The loops put it before a tile's last stores: left to the first real use (the
+// next tile's round 0), the wait would also count those younger stores -- s_waitcnt vmcnt(0) at
+// the top of every tile, a store round trip per tile that a one-tile workgroup never waits for.
+template <class F, int K>
+__device__ __forceinline__ void land_loads(Fe<F> (&r)[K]) {
+#pragma unroll
+  for (int j = 0; j < K; j++)
+#pragma unroll
+    for (int i = 0; i < F::N; i++) asm volatile("" : "+v"(r[j].v[i])::"memory");
+}
+
+// TW2R needs gridDim.x to be a multiple of the groups per row (launch_a_loop sees to it).
+template <class F, int LOG_S, int LOG_CW, int LOG_T, bool HALFZ, bool CANON, class TW, bool PF, bool TW2R>
+__global__ __launch_bounds__(1 << LOG_T, 3) void k_pass_a_loop(const uint32_t *__restrict__ src,
+                                                               size_t src_stride, size_t n_valid,
+                                                               uint32_t *__restrict__ dst, size_t dst_stride,
+                                                               const uint32_t *__restrict__ twn,
+                                                               const uint32_t *__restrict__ tw2, int log_n,
+                                                               uint32_t *__restrict__ copy, size_t copy_stride,
+                                                               size_t n_tiles) {
+  constexpr int S = 1 << LOG_S, CW = 1 << LOG_CW, LD = CW > 1 ? CW + 1 : 1, T = 1 << LOG_T;
+  constexpr int R = LOG_S + LOG_CW - LOG_T;
+  static_assert(R >= 1 && R < LOG_S, "tile / thread shape (more than one round)");
+  constexpr int LS0 = last_s0<LOG_S, R>();
+  constexpr int RR0 = rr_of<LOG_S, R, 0>(), K0 = 1 << RR0, GL0 = 1 << (LOG_S - RR0);
+  constexpr int KL = HALFZ ? K0 / 2 : K0;  // what round 0 loads
+  // last round: NIT items of KE elements per thread (NIT * KE = 2^R)
+  constexpr int RRE = LOG_S - LS0, KE = 1 << RRE, NIT = 1 << (R - RRE);
+  __shared__ __align__(16) uint32_t smem[(S * LD + S / 2 * TW::ELEMS) * F::N];
+  Fe<F> *tw = reinterpret_cast<Fe<F> *>(smem);
+  Fe<F> *tile = tw + S / 2 * TW::ELEMS;
+  const int tid = threadIdx.x;
+  const int log_m = log_n - LOG_S, log_g = log_m - LOG_CW;
+  const size_t gmask = ((size_t)1 << log_g) - 1;
+  const size_t G = gridDim.x;
+  TW::template stage<S / 2>(tw, twn, log_m, tid, T);
+
+  const int v0 = tid & (CW - 1), q0 = tid >> LOG_CW;  // round 0's item (q0 < GL0)
+  auto load0 = [&](size_t tl, Fe<F> *r) {
+    const uint32_t *in = src + (tl >> log_g) * src_stride * F::N;
+    const size_t c = ((tl & gmask) << LOG_CW) + v0;
+#pragma unroll
+    for (int j = 0; j < KL; j++) {
+      const size_t pos = c + ((size_t)(q0 + j * GL0) << log_m);
+      r[j] = pos < n_valid ? fe_load<F>(in, pos) : fe_zero<F>();
+    }
+  };
+  Fe<F> w2[TW2R ? K0 : 1];
+  auto load_w2 = [&](size_t c0) {
+#pragma unroll
+    for (int i = 0; i < NIT; i++) {
+      const int item = tid + i * T;
+      const size_t c = c0 + (item & (CW - 1));
+#pragma unroll
+      for (int j = 0; j < KE; j++) {
+        const int t = ((item >> LOG_CW) << RRE) + j;
+        if (CANON || (c && t))
+          w2[TW2R ? i * KE + j : 0] = fe_load<F>(tw2, c + ((size_t)t << log_m));
+        else
+          w2[TW2R ? i * KE + j : 0] = fe_zero<F>();  // (never multiplied by: w^0 = 1)
+      }
+    }
+    land_loads<F>(w2);  // (or every tile's last round would wait as if they were still in flight)
+  };
+  Fe<F> nx[PF ? KL : 1];
+  size_t tl = blockIdx.x;
+  if constexpr (PF) {
+    if (tl < n_tiles) load0(tl, nx);
+  }
+  if constexpr (TW2R) load_w2((tl & gmask) << LOG_CW);  // (the same columns in every tile of this workgroup)
+  for (; tl < n_tiles; tl += G) {
+    const size_t row = tl >> log_g, c0 = (tl & gmask) << LOG_CW;
+    uint32_t *out = dst + row * dst_stride * F::N;
+    // ---- round 0 from the registers the previous iteration filled (exactly one item per thread)
+    Fe<F> x[K0];
+    if constexpr (PF) {
+#pragma unroll
+      for (int j = 0; j < KL; j++) x[j] = nx[j];
+    } else {
+      load0(tl, x);
+    }
+#pragma unroll
+    for (int j = KL; j < K0; j++) x[j] = fe_zero<F>();
+    if (copy) {
+      uint32_t *cp = copy + row * copy_stride * F::N;
+#pragma unroll
+      for (int j = 0; j < KL; j++) {
+        const size_t pos = c0 + v0 + ((size_t)(q0 + j * GL0) << log_m);
+        if (pos < n_valid) fe_store<F>(cp, pos, x[j]);  // coalesced: lanes = adjacent columns
+      }
+    }
+    __syncthreads();  // twiddle table (first tile); the previous tile's last-round reads of `tile`
+    dif_regs<F, LOG_S, 0, RR0, HALFZ, TW>(x, q0, tw);
+#pragma unroll
+    for (int j = 0; j < K0; j++) tile[(q0 + j * GL0) * LD + v0] = x[j];
+    __syncthreads();
+    mid_rounds<F, LOG_S, LOG_CW, LOG_T, R, RR0, LS0, TW>(tile, tw, tid);
+    if constexpr (PF) {
+      if (tl + G < n_tiles) load0(tl + G, nx);
+    }
+    // ---- last round: LDS -> registers -> twiddle -> HBM
+#pragma unroll
+    for (int i = 0; i < NIT; i++) {
+      const int item = tid + i * T;
+      const int v = item & (CW - 1), b = (item >> LOG_CW) << RRE;  // GL == 1
+      Fe<F> y[KE];
+#pragma unroll
+      for (int j = 0; j < KE; j++) y[j] = tile[(b + j) * LD + v];
+      dif_regs<F, LOG_S, LS0, RRE, false, TW>(y, 0, tw);
+      const size_t c = c0 + v;
+#pragma unroll
+      for (int j = 0; j < KE; j++) {
+        const int t = b + j;
+        if (CANON || (c && t)) {  // (w^0 = 1 otherwise; at is also the [t][c] twiddle's index)
+          if constexpr (TW2R)
+            y[j] = NTT_MUL<F>(y[j], w2[i * KE + j]);
+          else
+            y[j] = NTT_MUL<F>(y[j], fe_load<F>(tw2, c + ((size_t)t << log_m)));
+        }
+      }
+      if constexpr (PF) {
+        if (i == NIT - 1) land_loads<F>(nx);
+      }
+#pragma unroll
+      for (int j = 0; j < KE; j++) fe_store<F>(out, c + ((size_t)(b + j) << log_m), y[j]);
+    }
+  }
+}
+
+template <class F, int LOG_S, int LOG_CW, int LOG_T, class TW, bool PF>
+__global__ __launch_bounds__(1 << LOG_T, 3) void k_pass_b_loop(uint32_t *__restrict__ data, size_t stride,
+                                                               const uint32_t *__restrict__ twn, int log_n,
+                                                               size_t n_tiles) {
+  constexpr int S = 1 << LOG_S, CW = 1 << LOG_CW, LD = CW > 1 ? CW + 1 : 1, T = 1 << LOG_T;
+  constexpr int R = LOG_S + LOG_CW - LOG_T;
+  static_assert(R >= 1 && R < LOG_S, "tile / thread shape (more than one round)");
+  constexpr int LS0 = last_s0<LOG_S, R>();
+  constexpr int RR0 = rr_of<LOG_S, R, 0>(), K0 = 1 << RR0, LOG_GL0 = LOG_S - RR0, GL0 = 1 << LOG_GL0;
+  __shared__ __align__(16) uint32_t smem[(S * LD + S / 2 * TW::ELEMS) * F::N];
+  Fe<F> *tw = reinterpret_cast<Fe<F> *>(smem);
+  Fe<F> *tile = tw + S / 2 * TW::ELEMS;
+  const int tid = threadIdx.x;
+  const int log_blocks = log_n - LOG_S, log_g = log_blocks - LOG_CW;
+  const size_t gmask = ((size_t)1 << log_g) - 1;
+  const size_t G = gridDim.x;
+  TW::template stage<S / 2>(tw, twn, log_blocks, tid, T);
+  const int q0 = tid & (GL0 - 1), v0 = tid >> LOG_GL0;  // round 0: lanes = adjacent positions of one block
+  auto tile_io = [&](size_t tl) { return data + ((tl >> log_g) * stride + (((tl & gmask) << LOG_CW) << LOG_S)) * F::N; };
+  auto load0 = [&](size_t tl, Fe<F> *r) {
+    const uint32_t *io = tile_io(tl);
+#pragma unroll
+    for (int j = 0; j < K0; j++) r[j] = fe_load<F>(io, (size_t)v0 * S + q0 + j * GL0);
+  };
+  Fe<F> nx[PF ? K0 : 1];
+  size_t tl = blockIdx.x;
+  if constexpr (PF) {
+    if (tl < n_tiles) load0(tl, nx);
+  }
+  for (; tl < n_tiles; tl += G) {
+    uint32_t *io = tile_io(tl);
+    {
+      Fe<F> x[K0];
+      if constexpr (PF) {
+#pragma unroll
+        for (int j = 0; j < K0; j++) x[j] = nx[j];
+      } else {
+        load0(tl, x);
+      }
+      __syncthreads();  // twiddle table (first tile); the previous tile's final reads of `tile`
+      dif_regs<F, LOG_S, 0, RR0, false, TW>(x, q0, tw);
+#pragma unroll
+      for (int j = 0; j < K0; j++) tile[(q0 + j * GL0) * LD + v0] = x[j];
+    }
+    __syncthreads();
+    mid_rounds<F, LOG_S, LOG_CW, LOG_T, R, RR0, LS0, TW>(tile, tw, tid);
+    if constexpr (PF) {
+      if (tl + G < n_tiles) load0(tl + G, nx);
+    }
+    mid_rounds<F, LOG_S, LOG_CW, LOG_T, R, LS0, LOG_S, TW>(tile, tw, tid);  // the last round
+    if constexpr (PF) land_loads<F>(nx);
+    for (int idx = tid; idx < S * CW; idx += T) {
+      const int v = idx >> LOG_S, t = idx & (S - 1);
+#if LCPC_NTT_LAZY
+      fe_store<F>(io, idx, fe_reduce_2p<F>(tile[t * LD + v]));
+#else
+      fe_store<F>(io, idx, tile[t * LD + v]);
+#endif
+    }
+  }
+}
+
+// Blocks of `threads` threads of kernel `k` that one CU holds, from the kernel's own LDS and
+// register footprint (160 KiB of LDS, 512 VGPRs per lane in granules of 8, 8 waves per SIMD).
+template <class K>
+int blocks_per_cu(K k, int threads) {
+  hipFuncAttributes at;
+  if (hipFuncGetAttributes(&at, reinterpret_cast<const void *>(k)) != hipSuccess) {
+    (void)hipGetLastError();
+    return 1;
+  }
+  const int waves = (threads + 63) / 64;
+  const int regs = at.numRegs > 0 ? (at.numRegs + 7) / 8 * 8 : 8;
+  int per_simd = 512 / regs;
+  if (per_simd > 8) per_simd = 8;
+  int n = per_simd * 4 / waves;
+  if (at.sharedSizeBytes > 0 && (int)(160 * 1024 / at.sharedSizeBytes) < n) n = (int)(160 * 1024 / at.sharedSizeBytes);
+  return n < 1 ? 1 : n;
+}
+
+// grid: the workgroups to launch (at most the tiles).  query: only lower *query to this
+// kernel's blocks per CU (ntt_plan_init sizes NttPlan::persist_grid with it); nothing is launched.
+template <class F, int LOG_S, int LOG_CW, int LOG_T, bool HALFZ, bool CANON, class TW, bool PF = true,
+          bool TW2R = true>
+hipError_t launch_a_loop(const uint32_t *src, size_t ss, size_t nv, uint32_t *dst, size_t ds, const uint32_t *tw,
+                         int log_n, size_t n_rows, hipStream_t s, uint32_t *cp, size_t cs, const uint32_t *tw2,
+                         size_t grid, int *query = nullptr) {
+  auto k = k_pass_a_loop<F, LOG_S, LOG_CW, LOG_T, HALFZ, CANON, TW, PF, TW2R>;
+  if (query) {
+    const int b = blocks_per_cu(k, 1 << LOG_T);
+    if (b < *query) *query = b;
+    return hipSuccess;
+  }
+  const size_t tiles = n_rows << (log_n - LOG_S - LOG_CW);
+  if (grid > tiles) grid = tiles;
+  if constexpr (TW2R) {  // a workgroup keeps its column group only on a multiple of the groups
+    if (grid & (((size_t)1 << (log_n - LOG_S - LOG_CW)) - 1))
+      return launch_a_loop<F, LOG_S, LOG_CW, LOG_T, HALFZ, CANON, TW, PF, false>(src, ss, nv, dst, ds, tw, log_n, n_rows,
+                                                                                s, cp, cs, tw2, grid);
+  }
+  prof::Scope ps("ntt_pass_a", s);
+  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(1 << LOG_T), 0, s, src, ss, nv, dst, ds, tw, tw2, log_n, cp, cs,
+                     tiles);
+  return hipGetLastError();
+}
+
+template <class F, int LOG_S, int LOG_CW, int LOG_T, class TW, bool PF = true>
+hipError_t launch_b_loop(uint32_t *dst, size_t ds, const uint32_t *tw, int log_n, size_t n_rows, hipStream_t s,
+                         size_t grid, int *query = nullptr) {
+  auto k = k_pass_b_loop<F, LOG_S, LOG_CW, LOG_T, TW, PF>;
+  if (query) {
+    const int b = blocks_per_cu(k, 1 << LOG_T);
+    if (b < *query) *query = b;
+    return hipSuccess;
+  }
+  const size_t tiles = n_rows << (log_n - LOG_S - LOG_CW);
+  if (grid > tiles) grid = tiles;
+  prof::Scope ps("ntt_pass_b", s);
+  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(1 << LOG_T), 0, s, dst, ds, tw, log_n, tiles);
+  return hipGetLastError();
 }
 
 template <class F, int LOG_S, int LOG_CW, int LOG_T, bool HALFZ, bool CANON, class TW>

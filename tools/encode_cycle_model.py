@@ -11,7 +11,10 @@ Inputs (all measured on MI355X, committed under profiles/):
   * the passes' dynamic VALU count per wave (SQ_INSTS_VALU / SQ_WAVES, tools/pmc_ntt.sh);
   * the passes' isolated durations (rocprofv3 kernel trace, fastest launch = a serial one).
 
-Model: time = (waves / 1024 SIMDs) x sum_class(static count x cost) x (dynamic / static VALU).
+Model: time = (waves / 1024 SIMDs) x sum_class(static count x cost) x (dynamic / static VALU), waves
+and the dynamic count per launch from the counters (65536 waves for a one-tile pass, the resident
+blocks' waves for a persistent one: the product is the launch's VALU instructions at the stream's
+mean price either way).  A k_pass_a_loop entry in the attribution replaces k_pass_a's.
 
     python tools/encode_cycle_model.py ISSUE_COST.json PMC_DIR TRACE_STATS.csv [OUT.txt [OUT.json [ATTRIBUTION.txt]]]
 
@@ -60,7 +63,7 @@ def issue_costs(path, k=4):
 def attribution(path=os.path.join(ROOT, "profiles", "r06_encode_isa_attribution.txt")):
     passes, cur = {}, None
     for line in open(path):
-        m = re.match(r"^(k_pass_[ab])<.*VALU (\d+), s_nop (\d+)", line)
+        m = re.match(r"^(k_pass_[ab])(?:_loop)?<.*VALU (\d+), s_nop (\d+)", line)
         if m:
             cur = m.group(1)
             passes[cur] = {"valu": int(m.group(2)), "s_nop": int(m.group(3)), "classes": {}}
@@ -73,11 +76,16 @@ def attribution(path=os.path.join(ROOT, "profiles", "r06_encode_isa_attribution.
 
 def pmc(pmc_dir):
     agg = collections.defaultdict(lambda: collections.defaultdict(float))
+    launches = collections.defaultdict(set)
     for f in glob.glob(os.path.join(pmc_dir, "p*", "*counter_collection.csv")):
         for r in csv.DictReader(open(f)):
             k = "k_pass_a" if "k_pass_a" in r["Kernel_Name"] else "k_pass_b" if "k_pass_b" in r["Kernel_Name"] else None
             if k:
                 agg[k][r["Counter_Name"]] += float(r["Counter_Value"])
+                if r["Counter_Name"] == "SQ_WAVES":
+                    launches[k].add(r["Dispatch_Id"])
+    for k in agg:
+        agg[k]["launches"] = len(launches[k])
     return agg
 
 
@@ -110,11 +118,12 @@ def main():
         waves = c["SQ_WAVES"]
         dyn = c["SQ_INSTS_VALU"] / waves if waves else a["valu"]
         scale = dyn / a["valu"]
-        model_ms = (65536 / 1024) * per_wave * scale * 1e-6
-        clock = (c["GRBM_GUI_ACTIVE"] / 8 / (waves / 65536)) / (dur[k] * 1e-3) / 1e9 if dur.get(k) else None
+        per_launch = waves / c["launches"] if c.get("launches") else 65536
+        model_ms = (per_launch / 1024) * per_wave * scale * 1e-6
+        clock = (c["GRBM_GUI_ACTIVE"] / 8 / (waves / per_launch)) / (dur[k] * 1e-3) / 1e9 if dur.get(k) else None
         res[k] = model_ms
         print(f"{k}: static VALU {a['valu']}/wave, dynamic {dyn:.0f}/wave (x{scale:.3f}); issue time per wave "
-              f"{per_wave * scale:.0f} ns -> {model_ms:.3f} ms for 64 waves/SIMD; measured {dur.get(k, float('nan')):.3f} ms "
+              f"{per_wave * scale:.0f} ns -> {model_ms:.3f} ms for {per_launch / 1024:.0f} waves/SIMD; measured {dur.get(k, float('nan')):.3f} ms "
               f"(fastest launch) -> model / measured = {model_ms / dur[k]:.2f}", file=out)
         wc = c["SQ_WAVE_CYCLES"]
         print(f"    wave cycles: issuing {c['SQ_ACTIVE_INST_ANY'] / wc:.2f}, issue-stalled {c['SQ_WAIT_INST_ANY'] / wc:.2f}, "

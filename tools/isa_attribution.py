@@ -76,11 +76,23 @@ def main():
         ks = IC.kernels(ns)
         dem = dict(zip(ks, IC.demangle(list(ks))))
         print("\n# cfg3 passes, static VALU instructions per thread (one tile item per thread)", file=out)
+        # the persistent pass A (LCPC_NTT_PERSIST) comes last: prologue + one loop body per thread,
+        # only its class mix is meaningful (tools/encode_cycle_model.py prices it per instruction)
         for want, key in (("k_pass_a<lcpc::Ft127, 8, 3, 8, true, true", "k_pass_a"),
-                          ("k_pass_b<lcpc::Ft127, 8, 3, 8", "k_pass_b")):
-            mk = next(k for k in ks if want in dem[k])
+                          ("k_pass_b<lcpc::Ft127, 8, 3, 8", "k_pass_b"),
+                          ("k_pass_a_loop<lcpc::Ft127, 8, 3, 8, true, true, lcpc::ntt_v2::TwWords<lcpc::Ft127>, true, true",
+                           "k_pass_a_loop")):
+            mk = next((k for k in ks if want in dem[k]), None)
+            if mk is None:
+                continue
             c = valu_classes(ks[mk])
             tot = sum(c.values())
+            if key == "k_pass_a_loop":
+                name = dem[mk].split('(')[0]
+                print(f"{name[name.find('k_pass'):]}: VALU {tot}, s_nop {IC.classify(ks[mk]).get('s_nop', 0)}", file=out)
+                for n, v in sorted(c.items(), key=lambda kv: -kv[1]):
+                    print(f"   {n:28s} {v:6d}  ({100.0 * v / tot:4.1f} %)", file=out)
+                continue
             sh = dict(SHAPES[key])
             mads = c.get("mad_u64_u32", 0)
             if "TwWords" in dem[mk]:

@@ -39,7 +39,7 @@ struct Variant {
 };
 
 template <class F>
-void bench(const char *fname, int log_n, size_t rows, bool with_copy = false) {
+void bench(const char *fname, int log_n, size_t rows, bool with_copy = false, bool persist_steps = false) {
   const size_t n = (size_t)1 << log_n, np = n / 2;
   const size_t W = F::N;
   uint32_t *coeffs, *ref, *out, *tw;
@@ -122,7 +122,42 @@ void bench(const char *fname, int log_n, size_t rows, bool with_copy = false) {
                       CK((ntt_v2::launch_b<F, LB, CWB, TB, ntt_v2::TwWords<F>>(o, n, tw4_for(LB), log_n, rows, st))); \
                     }});                                                                       \
   }
-  if constexpr (F::ID == 1) {
+  // The persistent passes (ntt_v2.hpp) step by step beside the one-tile pair at the same shape:
+  // the tile loop alone, with the next tile's prefetch, with pass A's resident inter-pass twiddles.
+  // The grid is the product's: blocks per CU of the two kernels x CUs, a multiple of the groups.
+#define PV(NAME, L, CW, T, PF, W2)                                                             \
+  if constexpr (F::ID == 1) {                                                                  \
+    int bpc = 1 << 30;                                                                         \
+    CK((ntt_v2::launch_a_loop<F, L, CW, T, true, false, ntt_v2::TwWords<F>, PF, W2>(           \
+        nullptr, 0, 0, nullptr, 0, nullptr, log_n, 1, s, nullptr, 0, nullptr, 0, &bpc)));      \
+    CK((ntt_v2::launch_b_loop<F, L, CW, T, ntt_v2::TwWords<F>, PF>(nullptr, 0, nullptr, log_n, 1, s, 0, &bpc))); \
+    int cus = 0;                                                                               \
+    CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0));                 \
+    size_t g = (size_t)bpc * cus;                                                              \
+    const size_t groups = (size_t)1 << (log_n - L - CW);                                       \
+    if (g > groups) g -= g % groups;                                                           \
+    vs.push_back({std::string(NAME) + " grid " + std::to_string(g),                            \
+                  [&, g](const uint32_t *c, uint32_t *o, hipStream_t st) {                     \
+                    CK((ntt_v2::launch_a_loop<F, L, CW, T, true, false, ntt_v2::TwWords<F>, PF, W2>( \
+                        c, np, np, o, n, tw4_for(L), log_n, rows, st, cpy, np, tw2_for(L), g))); \
+                    CK((ntt_v2::launch_b_loop<F, L, CW, T, ntt_v2::TwWords<F>, PF>(o, n, tw4_for(L), log_n, rows, st, g))); \
+                  }});                                                                         \
+  }
+  if (persist_steps) {
+    if constexpr (F::ID == 1) {
+      if (log_n == 16) {
+        V2(8, 3, 8, 8, 3, 8)
+        PV("loop A,B(S=2^8,CW=2^3,T=2^8)", 8, 3, 8, false, false)
+        PV("loop+prefetch", 8, 3, 8, true, false)
+        PV("loop+prefetch+resident tw2", 8, 3, 8, true, true)
+      } else if (log_n == 14) {
+        V2(7, 5, 10, 7, 5, 10)
+        PV("loop A,B(S=2^7,CW=2^4,T=2^8)", 7, 4, 8, false, false)
+        PV("loop+prefetch", 7, 4, 8, true, false)
+        PV("loop+prefetch+resident tw2", 7, 4, 8, true, true)
+      }
+    }
+  } else if constexpr (F::ID == 1) {
     if (log_n == 16) {
       V2(8, 3, 8, 8, 3, 8)
       V2(8, 2, 7, 8, 2, 7)
@@ -222,8 +257,8 @@ void bench(const char *fname, int log_n, size_t rows, bool with_copy = false) {
   for (size_t i = 0; i < vs.size(); i++) {
     auto t = times[i];
     std::sort(t.begin(), t.end());
-    printf("%-52s %s  median %.3f ms  min %.3f ms  (%.0f GB/s algorithmic)\n", vs[i].name.c_str(),
-           ok[i] ? "OK " : "BAD", t[t.size() / 2], t[0], bytes / (t[t.size() / 2] * 1e-3) / 1e9);
+    printf("%-52s %s  median %.3f ms  min %.3f ms  max %.3f ms  (%.0f GB/s algorithmic)\n", vs[i].name.c_str(),
+           ok[i] ? "OK " : "BAD", t[t.size() / 2], t[0], t.back(), bytes / (t[t.size() / 2] * 1e-3) / 1e9);
   }
 }
 
@@ -235,5 +270,10 @@ int main(int argc, char **argv) {
   if (which == 5) bench<Ft63>("Ft63 PoS 1 GiB (copy)", 15, 9363, true);
   if (which == 7) bench<Ft63>("Ft63 PoS bench dims (copy)", 17, 2341, true);
   if (which == 3) bench<Ft255>("Ft255", 17, 256);
+  // the persistent passes' steps beside the one-tile pair: the flagship shape with the copy, cfg2
+  if (which == 8) {
+    bench<Ft127>("Ft127 persistent steps (copy)", 16, 512, true, true);
+    bench<Ft127>("Ft127 cfg2 persistent steps (copy)", 14, 128, true, true);
+  }
   return 0;
 }
