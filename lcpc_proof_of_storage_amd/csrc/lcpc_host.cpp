@@ -1279,7 +1279,9 @@ lcpc_status lcpc_verify_leaf_paths(const uint8_t *leaves, const uint8_t *paths, 
   Lease lease(dev);
   HIP_TRY(hipSetDevice(dev->id));
   DBuf dl, dp, di, dr, dfl;
-  if ((st = upload(dev, dl, leaves, n * 32)) || (st = upload(dev, dp, paths, n * path_len * 32 + 32)) ||
+  // exactly the caller's n * path_len digests (none when path_len is 0: an empty upload still
+  // allocates a block, and k_path_checks then reads no path word)
+  if ((st = upload(dev, dl, leaves, n * 32)) || (st = upload(dev, dp, paths, n * path_len * 32)) ||
       (st = upload(dev, di, idx, n * 8)) || (st = upload(dev, dr, root, 32)))
     return st;
   HIP_TRY(dfl.alloc(dev, n * 4));

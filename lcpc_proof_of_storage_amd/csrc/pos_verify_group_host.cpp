@@ -272,10 +272,7 @@ lcpc_status verify_single(const lcpc_pos_audit_job &a, const uint64_t *enc_row, 
   std::vector<uint8_t> leaves(32 * n), ok(n);
   lcpc_status st;
   if ((st = lcpc_hash_field_columns((lcpc_field)POS_FID, a.cols, nr, n, leaves.data()))) return st;
-  // (lcpc_verify_leaf_paths uploads one digest past the paths)
-  std::vector<uint8_t> paths(n * pl * 32 + 32);
-  std::memcpy(paths.data(), a.paths, n * pl * 32);
-  if ((st = lcpc_verify_leaf_paths(leaves.data(), paths.data(), n, pl, a.idx, a.root, ok.data()))) return st;
+  if ((st = lcpc_verify_leaf_paths(leaves.data(), a.paths, n, pl, a.idx, a.root, ok.data()))) return st;
   if (!std::all_of(ok.begin(), ok.end(), [](uint8_t v) { return v != 0; })) {
     *verdict = 1;
     return LCPC_OK;

@@ -84,7 +84,7 @@ def upload_bytes(n_rows, pre, enc, n_cols):
     paths = n_cols * plen * 32
     grouped = stride + paths + 32 + 16 * n_cols + 8 * n_rows + 64 + 2 * enc * 8
     singles = (cols                                            # lcpc_hash_field_columns
-               + 32 * n_cols + paths + 32 + 8 * n_cols + 32    # lcpc_verify_leaf_paths
+               + 32 * n_cols + paths + 8 * n_cols + 32         # lcpc_verify_leaf_paths
                + 8                                             # lcpc_pos_side_vectors
                + enc * 8                                       # lcpc_ifft_oi_rows
                + 2 * pre * 8                                   # the dot
