@@ -191,6 +191,13 @@ size_t lcpc_encoding_n_cols(const lcpc_encoding *e);
 #define LCPC_ROW_KERNEL_FOURSTEP 1
 #define LCPC_ROW_KERNEL_ONEPASS 2
 lcpc_status lcpc_encoding_set_row_kernel(lcpc_encoding *e, int kernel);
+/* 1 if lcpc_commit_new_device under e hashes the column leaves inside the encode's second pass
+ * instead of in a pass of its own over the codeword (whole rows, BLAKE3, device-resident
+ * coefficients; Ft127 encodings whose second pass is 2^8 points long, that is n_cols 2^15 .. 2^16),
+ * else 0.  Fixed when the encoding is made: a build with -DLCPC_NTT_LEAF_FUSE=0 has no such pass,
+ * and LCPC_NTT_LEAF_FUSE=0 in the environment at creation keeps that encoding on the separate
+ * pass.  Commitments are bit-identical either way.  Host only; no reference counterpart. */
+int lcpc_encoding_leaf_fuse(const lcpc_encoding *e);
 /* "BLAKE3", "SHA-256", "SHA3-256", "Keccak-256"; NULL for an unknown value.  Host only. */
 const char *lcpc_digest_name(lcpc_digest d);
 /* The digest D of everything made or checked under e: with D substituted, merkleize (lcpc-2d/src/

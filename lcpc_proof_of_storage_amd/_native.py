@@ -110,6 +110,7 @@ SIGNATURES = {
     "lcpc_encoding_n_per_row": (sz, [vp]),
     "lcpc_encoding_n_cols": (sz, [vp]),
     "lcpc_encoding_set_row_kernel": (i32, [vp, i32]),
+    "lcpc_encoding_leaf_fuse": (i32, [vp]),
     "lcpc_digest_name": (C.c_char_p, [i32]),
     "lcpc_encoding_set_digest": (i32, [vp, i32]),
     "lcpc_encoding_digest": (i32, [vp]),

@@ -55,6 +55,11 @@ struct NttPlan {
   // correct, the tests walk small ones.
   size_t persist_grid = 0;
   bool persist_grid_forced = false;
+  // whether a whole commitment's encode may end in the pass B that also hashes the column leaves
+  // (ntt_rows_leaf_cvs): forward Ft127 plans whose pass B has the fused kernel's length, in a build
+  // that has the kernel (LCPC_NTT_LEAF_FUSE, ntt_v2.hpp); LCPC_NTT_LEAF_FUSE=0 in the environment
+  // at plan init clears it for that plan
+  bool leaf_fuse = false;
 };
 // the longest sub-FFT whose block stages word-expanded twiddles: 2^(L-1) entries of 64 bytes beside
 // the tile (16 KiB at L = 9; at L = 12 the table alone would be 128 KiB of a CU's 160)
@@ -89,6 +94,17 @@ void ntt_plan_free(NttPlan &p);
 hipError_t ntt_rows(const NttPlan &p, const uint32_t *src, size_t src_stride, size_t n_valid,
                     uint32_t *dst, size_t dst_stride, size_t n_rows, hipStream_t s,
                     uint32_t *copy = nullptr, size_t copy_stride = 0, bool canon_out = false);
+// ntt_rows with canon_out for ALL n_rows rows of a row-major commitment at once, whose second pass
+// also leaves the BLAKE3 chunk chaining values of the column leaves (leaf_hashes' messages over
+// the canonical codeword) in cvs[chunk][col], leaf_n_chunks(fid, n_rows) x 2^log_n values of 8
+// words, the layout leaf_chunk_cvs writes with blk = 0: leaves_from_cvs turns them into the leaves
+// (a one-chunk message's value is already the leaf), and no kernel reads the codeword back.
+// Only where ntt_rows_leaf_ok says so (the plan's leaf_fuse, canonical output, rows n_cols apart);
+// hipErrorInvalidValue otherwise.
+bool ntt_rows_leaf_ok(const NttPlan &p, size_t dst_stride, bool canon_out);
+hipError_t ntt_rows_leaf_cvs(const NttPlan &p, const uint32_t *src, size_t src_stride, size_t n_valid,
+                             uint32_t *dst, size_t dst_stride, size_t n_rows, hipStream_t s, uint32_t *copy,
+                             size_t copy_stride, uint32_t *cvs);
 // m[r][j] <-> m[r][bitrev_log_n(j)] in place, rows r < n_rows of stride `stride` elements
 hipError_t bitrev_rows_inplace(int fid, uint32_t *m, size_t stride, int log_n, size_t n_rows, hipStream_t s);
 // The proof-of-storage file image encoded straight into a commitment (ntt_row1.hpp BYTES): row r

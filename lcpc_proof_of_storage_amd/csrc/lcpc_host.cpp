@@ -163,6 +163,9 @@ lcpc_status commit_device(const lcpc_encoding *e, const void *d_src, bool src_is
   uint8_t *cf = c->coeffs.as<uint8_t>();
   uint8_t *cm = c->comm.as<uint8_t>();
   DBuf tmp;  // (SDIG scratch; at function scope, so that no block exit drains the stream)
+  DBuf scratch;  // the leaf hashing's chunk chaining values
+  const bool eval = eval_left && eval_out;
+  int fused_chunks = 0;  // > 0: the encode's second pass left the leaf chunks' chaining values in scratch
   if (e->kind == KIND_SDIG) {
     // element-major codeword [n_cols][n_rows]: the message part is the coefficient matrix
     // transposed, the SDIG levels fill the rest, and each leaf is a contiguous column.  The
@@ -227,8 +230,17 @@ lcpc_status commit_device(const lcpc_encoding *e, const void *d_src, bool src_is
     // commitment's own coefficient copy as it reads them (no separate D2D copy)
     c->canon = true;
     const size_t full = len / np, tail = len - full * np;
-    HIP_TRY(ntt_rows(e->plan, (const uint32_t *)d_src, np, np, (uint32_t *)cm, nc, full, s,
-                     (uint32_t *)cf, np, true));
+    if (!tail && !eval && c->digest == DIGEST_BLAKE3 && ntt_rows_leaf_ok(e->plan, nc, true)) {
+      // whole rows, BLAKE3 leaves, no u^T Enc(M): pass B hashes the columns as it stores them, and
+      // no leaf pass reads the codeword back (ntt_rows_leaf_cvs)
+      fused_chunks = (int)leaf_n_chunks(fid, n_rows);
+      HIP_TRY(scratch.alloc(dev, (size_t)fused_chunks * nc * 32));
+      HIP_TRY(ntt_rows_leaf_cvs(e->plan, (const uint32_t *)d_src, np, np, (uint32_t *)cm, nc, n_rows, s, (uint32_t *)cf,
+                                np, scratch.as<uint32_t>()));
+    } else {
+      HIP_TRY(ntt_rows(e->plan, (const uint32_t *)d_src, np, np, (uint32_t *)cm, nc, full, s,
+                       (uint32_t *)cf, np, true));
+    }
     if (tail) {
       uint8_t *last = cf + full * np * wb;
       HIP_TRY(hipMemcpyAsync(last, (const uint8_t *)d_src + full * np * wb, tail * wb,
@@ -241,9 +253,8 @@ lcpc_status commit_device(const lcpc_encoding *e, const void *d_src, bool src_is
   // Merkle tree (:685-697, merkleize :720-734); leaves past n_cols stay zero digests
   HIP_TRY(c->hashes.alloc(dev, c->n_hashes * 32));
   if (np2 > nc) HIP_TRY(hipMemsetAsync(c->hashes.as<uint8_t>() + nc * 32, 0, (np2 - nc) * 32, s));
-  DBuf scratch, dleft, partials, dsum;
-  HIP_TRY(scratch.alloc(dev, leaf_hash_scratch_bytes(fid, n_rows, nc)));
-  const bool eval = eval_left && eval_out;
+  DBuf dleft, partials, dsum;
+  if (!fused_chunks) HIP_TRY(scratch.alloc(dev, leaf_hash_scratch_bytes(fid, n_rows, nc)));
   const bool fused = eval && !c->col_major && c->canon && leaf_eval_fusable(fid);
   if (eval) {
     if (c->col_major) return fail(LCPC_ERR_UNSUPPORTED, "u^T Enc(M): row-major (Ligero) commitments only");
@@ -251,7 +262,9 @@ lcpc_status commit_device(const lcpc_encoding *e, const void *d_src, bool src_is
     if (st) return st;
     HIP_TRY(dsum.alloc(dev, nc * wb));
   }
-  if (c->digest != DIGEST_BLAKE3) {
+  if (fused_chunks) {
+    HIP_TRY(leaves_from_cvs(scratch.as<uint32_t>(), nc, fused_chunks, c->hashes.as<uint8_t>(), s));
+  } else if (c->digest != DIGEST_BLAKE3) {
     // D = SHA-256 / SHA3-256 / Keccak-256 (digest.hip); (eval is BLAKE3-only: refused above)
     if (c->col_major)
       HIP_TRY(leaf_hashes_cols_d(c->digest, fid, c->comm.as<uint32_t>(), n_rows, nc, c->hashes.as<uint8_t>(), nullptr, s,
@@ -472,6 +485,10 @@ lcpc_status lcpc_encoding_set_row_kernel(lcpc_encoding *e, int kernel) {
     return fail(LCPC_ERR_INVALID_ARG, "row kernel");
   e->plan.row_kernel = kernel;
   return LCPC_OK;
+}
+
+int lcpc_encoding_leaf_fuse(const lcpc_encoding *e) {
+  return e && e->kind != KIND_SDIG && ntt_rows_leaf_ok(e->plan, e->n_cols, true) ? 1 : 0;
 }
 
 const char *lcpc_digest_name(lcpc_digest d) { return digest_name((int)d); }

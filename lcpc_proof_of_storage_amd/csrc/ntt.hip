@@ -21,6 +21,9 @@ bool ntt_tw4_enabled();  // ntt_ft127.hip: the build's LCPC_NTT_TW4
 // ntt_ft127.hip: blocks per CU of the plan's persistent passes (the smaller of the two), 0 if the
 // build (LCPC_NTT_PERSIST) or the plan's shape has none; the plan's tables are not read
 int ntt_persist_blocks_per_cu_ft127(const NttPlan &p);
+int ntt_leaf_fuse_l2_ft127();  // ntt_ft127.hip: the pass B length of the fused leaf pass, 0 if not built
+hipError_t ntt_rows_leaf_cvs_ft127(const NttPlan &, const uint32_t *, size_t, size_t, uint32_t *, size_t, size_t,
+                                   hipStream_t, uint32_t *, size_t, uint32_t *);
 
 namespace {
 // out[(t << l2) + c] = tw[c * bitrev_l1(t)]: an element copy of `words` u32 words
@@ -123,6 +126,12 @@ hipError_t ntt_plan_init(NttPlan &p, int fid, int log_n, bool inverse, hipStream
       }
     }
   }
+  // the fused leaf pass (kernels.hpp, NttPlan::leaf_fuse); the switch is read here, per plan, so one
+  // process can make both kinds of encoding
+  p.leaf_fuse = fid == 1 && !inverse && log_n > 12 && ntt_leaf_fuse_l2_ft127() > 0 && p.l2 == ntt_leaf_fuse_l2_ft127();
+  if (const char *f = std::getenv("LCPC_NTT_LEAF_FUSE")) {
+    if (std::atol(f) == 0) p.leaf_fuse = false;
+  }
   return hipSuccess;
 }
 
@@ -155,6 +164,19 @@ hipError_t ntt_rows(const NttPlan &p, const uint32_t *src, size_t src_stride, si
   if (e == hipSuccess && !p.inverse) e = bitrev_rows_inplace(p.fid, dst, dst_stride, p.log_n, n_rows, s);
 #endif
   return e;
+}
+
+bool ntt_rows_leaf_ok(const NttPlan &p, size_t dst_stride, bool canon) {
+  // (a natural-order build reorders the rows after pass B: the hash would see the wrong columns)
+  return LCPC_FFT_OUTPUT_BITREV && p.leaf_fuse && p.fid == 1 && !p.inverse && canon && p.d_tw_canon && p.d_tw2_canon &&
+         dst_stride == ((size_t)1 << p.log_n);
+}
+
+hipError_t ntt_rows_leaf_cvs(const NttPlan &p, const uint32_t *src, size_t src_stride, size_t n_valid, uint32_t *dst,
+                             size_t dst_stride, size_t n_rows, hipStream_t s, uint32_t *copy, size_t copy_stride,
+                             uint32_t *cvs) {
+  if (!ntt_rows_leaf_ok(p, dst_stride, true)) return hipErrorInvalidValue;
+  return ntt_rows_leaf_cvs_ft127(p, src, src_stride, n_valid, dst, dst_stride, n_rows, s, copy, copy_stride, cvs);
 }
 
 }  // namespace lcpc

@@ -127,6 +127,13 @@ struct Shape<Ft191> {
   static constexpr int R = 2, E = 10;
 };
 
+// the pass B length whose tile the fused leaf pass takes (ntt_v2.hpp, k_pass_b_leaf: as many
+// threads as points, so CW = 2^R rows per tile)
+template <class F>
+constexpr int leaf_fuse_l2() {
+  return Shape<F>::E - Shape<F>::R;
+}
+
 template <int LOG_S, int E>
 constexpr int log_cw() {
   return E > LOG_S ? E - LOG_S : 0;
@@ -151,7 +158,11 @@ __global__ void k_from_mont_rows(uint32_t *__restrict__ m, size_t stride, size_t
 template <class F>
 hipError_t ntt_rows_t(const NttPlan &p, const uint32_t *src, size_t ss, size_t nv, uint32_t *dst,
                       size_t ds, size_t n_rows, hipStream_t s, uint32_t *cp, size_t cs, bool canon,
-                      int *query = nullptr) {
+                      int *query = nullptr, uint32_t *leaf_cvs = nullptr) {
+  // leaf_cvs (ntt_rows_leaf_cvs; the caller has checked ntt_rows_leaf_ok): the rows are a whole
+  // commitment and pass B is the kernel that also hashes the column leaves' chunks into leaf_cvs
+  if (leaf_cvs && (F::ID != 1 || !canon || p.log_n <= 12 || p.l2 != leaf_fuse_l2<F>() || ds != ((size_t)1 << p.log_n)))
+    return hipErrorInvalidValue;
   // query (ntt_plan_init, log_n > 12): nothing runs; *query is lowered to the blocks per CU of the
   // persistent kernels these arguments would launch (untouched where the shape has none)
   if (n_rows == 0 && !query) return hipSuccess;
@@ -238,6 +249,14 @@ hipError_t ntt_rows_t(const NttPlan &p, const uint32_t *src, size_t ss, size_t n
   auto pass_b = [&]<int L, int CW, int T = L + CW - R>() {
     constexpr bool TW4 = LCPC_NTT_TW4 && F::ID == 1 && L <= NTT_TW4_MAX_L;
     using TW = std::conditional_t<TW4, ntt_v2::TwWords<F>, ntt_v2::TwLib<F>>;
+#if LCPC_NTT_LEAF_FUSE
+    if constexpr (F::ID == 1 && L == leaf_fuse_l2<F>() && L + CW == E && T == L) {
+      if (leaf_cvs)
+        return ntt_v2::launch_b_leaf<F, L, CW, T, TW>(dst, ds, TW4 ? ntt_tw4_b(p) : p.d_tw, p.log_n, n_rows,
+                                                      leaf_n_chunks(F::ID, n_rows), leaf_cvs, s);
+    }
+#endif
+    if (leaf_cvs) return hipErrorInvalidValue;
     if constexpr (LCPC_NTT_PERSIST && LCPC_NTT_PERSIST_B && F::ID == 1 && L <= NTT_TW4_MAX_L && L + CW == E && R < L) {
       if (query || p.persist_grid > 0)
         return ntt_v2::launch_b_loop<F, L, CW, T, TW>(dst, ds, TW4 ? ntt_tw4_b(p) : p.d_tw, p.log_n, n_rows, s,

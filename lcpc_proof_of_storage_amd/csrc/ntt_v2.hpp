@@ -56,6 +56,24 @@
 #define LCPC_NTT_PERSIST_B 0
 #endif
 
+// LCPC_NTT_LEAF_FUSE (default 1): a whole Ft127 commitment's canonical encode can end in
+// k_pass_b_leaf, pass B that also hashes the column leaves' BLAKE3 chunks (ntt_rows_leaf_cvs,
+// kernels.hpp).  0 builds the tree without the kernel: every commitment keeps the separate leaf
+// pass (tools/ab_lib.py runs one build against the other).  LCPC_NTT_LEAF_FUSE=0 in the environment
+// when a plan is made does the same for that plan (NttPlan::leaf_fuse).
+#ifndef LCPC_NTT_LEAF_FUSE
+#define LCPC_NTT_LEAF_FUSE 1
+#endif
+// LCPC_NTT_LEAF_FUSE_PF (default 0): the fused pass prefetches the next tile's round-0 loads before
+// its last round and the hash (an A/B switch, as LCPC_NTT_PERSIST_B).
+#ifndef LCPC_NTT_LEAF_FUSE_PF
+#define LCPC_NTT_LEAF_FUSE_PF 0
+#endif
+
+#if LCPC_NTT_LEAF_FUSE
+#include "blake3_dev.hpp"
+#endif
+
 namespace lcpc {
 namespace ntt_v2 {
 
@@ -526,6 +544,114 @@ __global__ __launch_bounds__(1 << LOG_T, 3) void k_pass_b_loop(uint32_t *__restr
   }
 }
 
+#if LCPC_NTT_LEAF_FUSE
+// ---- pass B that also hashes the column leaves (LCPC_NTT_LEAF_FUSE): the commitment's last pass
+// over the codeword leaves the BLAKE3 chunk chaining values of every column, so no leaf kernel
+// reads the codeword back.  16-byte elements (a "row" of a leaf message is 16 bytes: chunk k of the
+// message 32 zero bytes || row 0 || row 1 ... covers rows 64k - 2 .. 64k + 61, the rows below 0
+// standing for the zero prefix), T == S threads.
+// A workgroup is one (chunk, block of S columns) and walks the chunk in tiles of CW rows of that
+// one block from row 64k - 2 on: tile slot v of tile i is row 64k - 2 + CW i + v, so a tile is CW/4
+// whole 64-byte blocks of each column's message.  Slots outside [0, n_rows) load zeros and store
+// nothing; the transform of a zero row is zero words (fe_add_2p, fe_sub_2p and the twiddle
+// products all map 0 to 0), which is what the prefix and the pad past the message hash as.  After
+// the last round thread t holds column b S + t of the tile's CW rows, reduced to canonical words:
+// it stores them (lanes = adjacent columns, as k_pass_b's final stores) and compresses them into
+// the chunk's chaining value, kept in registers across the tiles.  cvs[chunk][col] (8 words) is
+// k_leaf_chunks' layout; a one-chunk message's value carries ROOT (it is the leaf).
+// blockIdx = chunk * blocks + b: the last chunk, the only short one, comes last.
+// PF: the next tile's round-0 loads are issued before the last round and the hash.
+template <class F, int LOG_S, int LOG_CW, int LOG_T, class TW, bool PF>
+__global__ __launch_bounds__(1 << LOG_T, 3) void k_pass_b_leaf(uint32_t *__restrict__ data, size_t stride,
+                                                               const uint32_t *__restrict__ twn, int log_n,
+                                                               int n_rows, int n_chunks, uint32_t *__restrict__ cvs) {
+  constexpr int S = 1 << LOG_S, CW = 1 << LOG_CW, LD = CW > 1 ? CW + 1 : 1, T = 1 << LOG_T;
+  constexpr int R = LOG_S + LOG_CW - LOG_T;
+  static_assert(R >= 1 && R < LOG_S, "tile / thread shape (more than one round)");
+  static_assert(F::N == 4 && T == S && CW >= 4 && 64 % CW == 0, "a thread owns CW/4 whole blocks of one column");
+  constexpr int LS0 = last_s0<LOG_S, R>();
+  constexpr int RR0 = rr_of<LOG_S, R, 0>(), K0 = 1 << RR0, LOG_GL0 = LOG_S - RR0, GL0 = 1 << LOG_GL0;
+  __shared__ __align__(16) uint32_t smem[(S * LD + S / 2 * TW::ELEMS) * F::N];
+  Fe<F> *tw = reinterpret_cast<Fe<F> *>(smem);
+  Fe<F> *tile = tw + S / 2 * TW::ELEMS;
+  const int tid = threadIdx.x;
+  const int log_blocks = log_n - LOG_S;
+  const int chunk = (int)(blockIdx.x >> log_blocks);
+  const size_t b = blockIdx.x & (((size_t)1 << log_blocks) - 1);
+  TW::template stage<S / 2>(tw, twn, log_blocks, tid, T);
+  // the chunk's rows, tiles and message blocks (the same in every thread)
+  const int row_base = 64 * chunk - 2;
+  const int row_end = 64 * chunk + 62 < n_rows ? 64 * chunk + 62 : n_rows;
+  const int n_tiles = (row_end - row_base + CW - 1) / CW;
+  const int left_words = 8 + 4 * n_rows - 256 * chunk;  // message words from this chunk on
+  const int cw = left_words < 256 ? left_words : 256;
+  const int nb = (cw + 15) / 16;
+  uint32_t *io = data + (b << LOG_S) * F::N;  // column b S of row 0
+  const int q0 = tid & (GL0 - 1), v0 = tid >> LOG_GL0;  // round 0: lanes = adjacent positions of one row's block
+  auto load0 = [&](int i, Fe<F> *r) {
+    const int row = row_base + CW * i + v0;
+    const bool in = row >= 0 && row < n_rows;
+#pragma unroll
+    for (int j = 0; j < K0; j++) r[j] = in ? fe_load<F>(io + (size_t)row * stride * F::N, q0 + j * GL0) : fe_zero<F>();
+  };
+  uint32_t cv[8];
+  b3::iv(cv);
+  Fe<F> nx[PF ? K0 : 1];
+  if constexpr (PF) load0(0, nx);
+  for (int i = 0; i < n_tiles; i++) {
+    {
+      Fe<F> x[K0];
+      if constexpr (PF) {
+#pragma unroll
+        for (int j = 0; j < K0; j++) x[j] = nx[j];
+      } else {
+        load0(i, x);
+      }
+      __syncthreads();  // twiddle table (first tile); the previous tile's final reads of `tile`
+      dif_regs<F, LOG_S, 0, RR0, false, TW>(x, q0, tw);
+#pragma unroll
+      for (int j = 0; j < K0; j++) tile[(q0 + j * GL0) * LD + v0] = x[j];
+    }
+    __syncthreads();
+    mid_rounds<F, LOG_S, LOG_CW, LOG_T, R, RR0, LS0, TW>(tile, tw, tid);
+    if constexpr (PF) {
+      if (i + 1 < n_tiles) load0(i + 1, nx);
+    }
+    mid_rounds<F, LOG_S, LOG_CW, LOG_T, R, LS0, LOG_S, TW>(tile, tw, tid);  // the last round
+    if constexpr (PF) land_loads<F>(nx);
+    // ---- column b S + tid of the tile's rows: store, then hash
+    Fe<F> y[CW];
+#pragma unroll
+    for (int v = 0; v < CW; v++) {
+#if LCPC_NTT_LAZY
+      y[v] = fe_reduce_2p<F>(tile[tid * LD + v]);
+#else
+      y[v] = tile[tid * LD + v];
+#endif
+    }
+#pragma unroll
+    for (int v = 0; v < CW; v++) {
+      const int row = row_base + CW * i + v;
+      if (row >= 0 && row < n_rows) fe_store<F>(io + (size_t)row * stride * F::N, tid, y[v]);
+    }
+#pragma unroll
+    for (int k = 0; k < CW / 4; k++) {
+      const int blk = i * (CW / 4) + k;  // block of the chunk
+      if (blk < nb) {
+        uint32_t msg[16];
+#pragma unroll
+        for (int e = 0; e < 4; e++) fe_canon_repr_words<F>(y[4 * k + e], msg + 4 * e);
+        const int left = cw - 16 * blk;
+        uint32_t flags = blk == 0 ? b3::CHUNK_START : 0u;
+        if (blk == nb - 1) flags |= b3::CHUNK_END | (n_chunks == 1 ? b3::ROOT : 0u);
+        b3::compress(cv, msg, (uint64_t)chunk, left >= 16 ? 64u : (uint32_t)(4 * left), flags);
+      }
+    }
+  }
+  b3::store8(cvs + ((((size_t)chunk << log_blocks) + b) * S + tid) * 8, cv);
+}
+#endif  // LCPC_NTT_LEAF_FUSE
+
 // Blocks of `threads` threads of kernel `k` that one CU holds, from the kernel's own LDS and
 // register footprint (160 KiB of LDS, 512 VGPRs per lane in granules of 8, 8 waves per SIMD).
 template <class K>
@@ -606,6 +732,21 @@ hipError_t launch_b(uint32_t *dst, size_t ds, const uint32_t *tw, int log_n, siz
                      dim3(1 << LOG_T), 0, s, dst, ds, tw, log_n);
   return hipGetLastError();
 }
+
+#if LCPC_NTT_LEAF_FUSE
+// One workgroup per (chunk, block of 2^LOG_S columns).  The scope keeps pass B's name, so a profile
+// still sums an encode time; it now includes the leaf hashing.
+template <class F, int LOG_S, int LOG_CW, int LOG_T, class TW, bool PF = LCPC_NTT_LEAF_FUSE_PF != 0>
+hipError_t launch_b_leaf(uint32_t *dst, size_t ds, const uint32_t *tw, int log_n, size_t n_rows, size_t n_chunks,
+                         uint32_t *cvs, hipStream_t s) {
+  const size_t grid = n_chunks << (log_n - LOG_S);
+  if (n_rows == 0 || n_rows > ((size_t)1 << 24) || grid > 0x7fffffffu) return hipErrorInvalidValue;
+  prof::Scope ps("ntt_pass_b", s);
+  hipLaunchKernelGGL((k_pass_b_leaf<F, LOG_S, LOG_CW, LOG_T, TW, PF>), dim3((unsigned)grid), dim3(1 << LOG_T), 0, s, dst,
+                     ds, tw, log_n, (int)n_rows, (int)n_chunks, cvs);
+  return hipGetLastError();
+}
+#endif
 
 }  // namespace ntt_v2
 }  // namespace lcpc

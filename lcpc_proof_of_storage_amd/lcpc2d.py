@@ -480,6 +480,11 @@ class LcEncoding:
         _raise(N.load().lcpc_encoding_set_row_kernel(self._h, kernel))
         return self
 
+    @property
+    def leaf_fuse(self) -> bool:
+        """lcpc_encoding_leaf_fuse: whether commit_device hashes the leaves inside the encode's second pass."""
+        return bool(N.load().lcpc_encoding_leaf_fuse(self._h))
+
     def set_digest(self, digest: int):
         """lcpc_encoding_set_digest: the digest D of commitments made, proved and verified under this
         encoding (BLAKE3, SHA256, SHA3_256, KECCAK256).  Configuration: set it right after creation.
