@@ -55,7 +55,8 @@ extern "C" {
  * lcpc_selftest_recombine63).  So are the grouped stored-file audits (lcpc_pos_left_multiply_bytes_grouped*,
  * lcpc_pos_group_plan, lcpc_field_to_montgomery).  So is the grouped check of stored-file audit
  * responses (lcpc_pos_audit_job, lcpc_pos_verify_evaluations_grouped, lcpc_pos_verify_tile,
- * lcpc_pos_verify_group_plan). */
+ * lcpc_pos_verify_group_plan).  So is the grouped ingest of small files (lcpc_pos_ingest_job,
+ * lcpc_pos_encode_files_grouped, lcpc_pos_ingest_tile, lcpc_pos_ingest_plan). */
 #define LCPC_ABI_VERSION 3
 
 typedef enum lcpc_status {
@@ -745,6 +746,70 @@ lcpc_status lcpc_pos_encode_file(const uint8_t *data, size_t n_bytes, size_t pre
 lcpc_status lcpc_pos_encode_file_batched(const uint8_t *data, size_t n_bytes, size_t pre, size_t enc,
                                          size_t row_capacity, uint8_t *porenc, uint8_t *tree,
                                          size_t *rows_written, size_t batch_rows);
+/* ---- PoS grouped ingest: many small files encoded, hashed and folded to trees in one pass ----
+ * NO COUNTERPART IN THE REFERENCE (its server takes one upload per request, networking/server.rs:
+ * 396-433).  Additive within LCPC_ABI_VERSION 3.  The step before the grouped audits and the grouped
+ * check: a queue of (raw image, pre, enc) jobs becomes stored files and roots with a number of launches
+ * that does not grow with the number of files.
+ * EQUALITY: for every job, rows_written, rows [0, rows_written) of every column of porenc, tree and root
+ * are byte for byte what lcpc_pos_encode_file(data, n_bytes, pre, enc, row_capacity, ...) produces, and
+ * cvs is what lcpc_pos_writer_copy_cvs returns for a finalized writer over the same file.  Elements of
+ * porenc at rows >= rows_written are not touched.  Every output pointer may be NULL (porenc with
+ * row_capacity 0): nothing of that kind is returned for the job, and a call in which no job has a porenc
+ * copies no encoded word back to the host (a client that only needs the roots).
+ * PADDING is per image: job j is read through (data, n_bytes) alone and zero padded past its own end;
+ * host images may have any alignment.  A job with n_bytes == 0 is legal: zero rows, every leaf BLAKE3 of
+ * 32 zero bytes.
+ * STAGING: consecutive jobs form a staging group of at most LCPC_POS_GROUP_STAGE_BYTES of images (8-byte
+ * aligned offsets; LCPC_POS_GROUP_BYTES, the test seam, can only lower it), at most four times that in
+ * encoded bytes (sum rows * enc * 8, rows rounded up to even), at most LCPC_POS_INGEST_MAX_JOBS jobs,
+ * LCPC_POS_INGEST_MAX_ROWS rows, LCPC_POS_INGEST_MAX_TILES tiles and LCPC_POS_INGEST_MAX_TREE_BYTES of
+ * trees.  One page-locked block per group (images and tables) goes up in one copy and the outputs come
+ * back into it; two blocks alternate, and the host scatters a group's columns into the jobs' porenc
+ * while the next group runs.  A group takes at most LCPC_POS_INGEST_LAUNCHES_PER_GROUP kernel launches,
+ * whatever the number of jobs or of distinct enc, all inside one profiling region (pos_group_ingest).
+ * ROUTING: a job with enc > LCPC_POS_INGEST_MAX_ENC, or whose image or encoded bytes alone exceed a
+ * group, or whose columns have more than 2^16 1-KiB chunks, ends the group before it and goes through
+ * lcpc_pos_encode_file's own path inside the same call.  Every 1 <= pre < enc <= 1024 is grouped.
+ * Errors, before any device work and before any output byte is written: a NULL jobs, n_jobs == 0,
+ * data == NULL with n_bytes > 0, pre == 0, enc no power of two or enc <= pre, porenc with row_capacity <
+ * the job's rows, porenc == NULL with row_capacity != 0: LCPC_ERR_INVALID_ARG; enc beyond the field's
+ * two-adicity: LCPC_FFT_TOO_BIG; no device: LCPC_ERR_NO_DEVICE.  Ft63 and BLAKE3 only; the entry takes no
+ * encoding, so no other digest can reach it.  Threading as every entry: a stream of its own per call. */
+#define LCPC_POS_INGEST_MAX_ENC ((size_t)1024)  /* rows of more points take the single path (8 rows: 64 KiB of LDS) */
+#define LCPC_POS_INGEST_MAX_JOBS ((size_t)1 << 16)
+#define LCPC_POS_INGEST_MAX_ROWS ((size_t)1 << 23)
+#define LCPC_POS_INGEST_MAX_TILES ((size_t)1 << 20)
+#define LCPC_POS_INGEST_MAX_TREE_BYTES ((size_t)64 << 20)
+#define LCPC_POS_INGEST_LAUNCHES_PER_GROUP 3    /* encode, chunk chaining values, leaves and trees */
+#define LCPC_POS_INGEST_TILE_ROWS ((size_t)8)   /* rows of a full tile of the encode launch */
+typedef struct lcpc_pos_ingest_job {
+  const uint8_t *data;  /* raw image; may be NULL iff n_bytes == 0 */
+  size_t n_bytes;
+  size_t pre, enc;      /* 1 <= pre < enc, enc a power of two */
+  uint8_t *porenc;      /* column-major image of row_capacity rows, or NULL with row_capacity 0 */
+  size_t row_capacity;
+  uint8_t *tree;        /* (2 enc - 1) x 32 B, MerkleTree::to_bytes, or NULL */
+  uint8_t *root;        /* 32 B, or NULL */
+  uint8_t *cvs;         /* lcpc_leaf_n_chunks(LCPC_FT63, rows) x enc x 32 B, [chunk][column], or NULL */
+  size_t rows_written;  /* out */
+} lcpc_pos_ingest_job;
+lcpc_status lcpc_pos_encode_files_grouped(lcpc_pos_ingest_job *jobs, size_t n_jobs);
+/* Host-only, no device (like lcpc_pos_group_plan): the work list of the encode launch of each staging
+ * group the entry above makes for jobs of these sizes and dims, a pure function of its arguments (and of
+ * LCPC_POS_GROUP_BYTES).  A record is a tile: rows [row_lo, row_hi) of one job, at most
+ * LCPC_POS_INGEST_TILE_ROWS of them; `launch` counts the staging groups from 0 and `workgroup` the
+ * workgroups of the group's encode launch: the tiles of a workgroup share enc.  A routed job has one
+ * record with launch = LCPC_POS_GROUP_SINGLE, workgroup = 0, over all its rows.  Every (job, row) is in
+ * exactly one record; a job with zero rows has none (it still belongs to a group).  Writes at most cap
+ * records to tiles (may be NULL with cap 0), the count needed to *n_tiles and the number of staging
+ * groups to *n_launches (either may be NULL).  Errors: a NULL array, n_jobs == 0, and pre / enc as above. */
+typedef struct lcpc_pos_ingest_tile {
+  uint64_t job, row_lo, row_hi;
+  uint32_t launch, workgroup;
+} lcpc_pos_ingest_tile;
+lcpc_status lcpc_pos_ingest_plan(const size_t *n_bytes, const size_t *pre, const size_t *enc, size_t n_jobs,
+                                 lcpc_pos_ingest_tile *tiles, size_t cap, size_t *n_tiles, size_t *n_launches);
 /* The streaming writer itself: EncodedFileWriter::new (:40-105; porenc = the preallocated
  * image of row_capacity rows, batch_rows as above), push_bytes (:233-262), and
  * finalize_to_column_digest / _to_commit / _to_merkle_tree (:452-501): digests = the enc column

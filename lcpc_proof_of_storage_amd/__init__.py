@@ -21,3 +21,5 @@ from .pos import left_multiply_unencoded_matrices_by_vectors  # noqa: F401,E402
 from .pos_files import answer_evaluation_requests  # noqa: F401,E402
 # the client's check of those responses, one at a time or grouped
 from .pos import client_verify_evaluation, client_verify_evaluations_grouped, verify_group_plan  # noqa: F401,E402
+# many small files turned into stored files, or into their roots, in one pass
+from .pos import commit_roots_of_files, encode_files_grouped, ingest_plan  # noqa: F401,E402

@@ -70,6 +70,18 @@ class PosVerifyTile(C.Structure):
                 ("launch", C.c_uint32), ("wave", C.c_uint32)]
 
 
+class PosIngestJob(C.Structure):
+    """lcpc_pos_ingest_job (include/lcpc_mi.h)"""
+    _fields_ = [("data", vp), ("n_bytes", C.c_size_t), ("pre", C.c_size_t), ("enc", C.c_size_t), ("porenc", vp),
+                ("row_capacity", C.c_size_t), ("tree", vp), ("root", vp), ("cvs", vp), ("rows_written", C.c_size_t)]
+
+
+class PosIngestTile(C.Structure):
+    """lcpc_pos_ingest_tile (include/lcpc_mi.h)"""
+    _fields_ = [("job", C.c_uint64), ("row_lo", C.c_uint64), ("row_hi", C.c_uint64), ("launch", C.c_uint32),
+                ("workgroup", C.c_uint32)]
+
+
 class CommOps(C.Structure):
     _fields_ = [("user", vp), ("all_gather", ALL_GATHER_FN), ("all_to_all_v", ALL_TO_ALL_V_FN),
                 ("broadcast", BROADCAST_FN)]
@@ -217,6 +229,8 @@ SIGNATURES = {
     "lcpc_field_to_montgomery": (i32, [i32, u64p, u64p, sz]),
     "lcpc_pos_verify_evaluations_grouped": (i32, [C.POINTER(PosAuditJob), sz, u8p, u64p]),
     "lcpc_pos_verify_group_plan": (i32, [szp, szp, szp, sz, C.POINTER(PosVerifyTile), sz, szp, szp]),
+    "lcpc_pos_encode_files_grouped": (i32, [C.POINTER(PosIngestJob), sz]),
+    "lcpc_pos_ingest_plan": (i32, [szp, szp, szp, sz, C.POINTER(PosIngestTile), sz, szp, szp]),
     "lcpc_pos_update_rows": (i32, [sz, sz, sz, sz, szp, szp, szp, szp]),
     "lcpc_pos_update_evaluation": (i32, [vp, vp, sz, vp, vp, sz, u64p, u64p, sz, u64p, sz,
                                          u64p, u64p, u8p, u8p, u64p, u64p, u8p, u8p, u64p]),

@@ -224,6 +224,50 @@ __device__ __forceinline__ void cm_chunk_cv(uint4 (*__restrict__ stage)[5], cons
   }
 }
 
+// The leaf of one column from its n_chunks chunk chaining values cvs[0], cvs[stride], ... (32-byte
+// values `stride` values apart), which are left untouched: the register stack of blake3.hip's
+// k_leaf_fold_stack as a function.  level[k] = the root of a complete 2^k-chunk subtree, present iff
+// bit k of the number of chunks taken so far is set; the last chunk merges with every level still
+// present, lowest first, ROOT on the last parent (a one-chunk column's chaining value carries ROOT
+// already).  n_chunks must be uniform over the wave: the stack is then picked over by unrolled
+// compares, never indexed dynamically.  n_chunks >= 1 and n_chunks - 1 < 2^D.
+template <int D>
+__device__ __forceinline__ void leaf_fold_stack(const uint32_t *__restrict__ cvs, size_t stride, int n_chunks,
+                                                uint32_t cv[8]) {
+  uint32_t level[D][8], nxt[8];
+  load8(cvs, nxt);
+  for (int i = 0; i < n_chunks; i++) {
+#pragma unroll
+    for (int q = 0; q < 8; q++) cv[q] = nxt[q];
+    if (i + 1 < n_chunks) load8(cvs + (size_t)(i + 1) * stride * 8, nxt);  // in flight over the merges
+    const bool last = i + 1 == n_chunks;
+    for (int k = 0; k < D; k++) {
+      const bool top = (i >> (k + 1)) == 0;  // no level above k is present
+      if ((i >> k) & 1) {
+        uint32_t l[8], o[8];
+#pragma unroll
+        for (int j = 0; j < D; j++)
+          if (j == k) {
+#pragma unroll
+            for (int q = 0; q < 8; q++) l[q] = level[j][q];
+          }
+        parent_cv(l, cv, last && top, o);
+#pragma unroll
+        for (int q = 0; q < 8; q++) cv[q] = o[q];
+      } else if (!last) {
+#pragma unroll
+        for (int j = 0; j < D; j++)
+          if (j == k) {
+#pragma unroll
+            for (int q = 0; q < 8; q++) level[j][q] = cv[q];
+          }
+        break;
+      }
+      if (last && top) break;
+    }
+  }
+}
+
 template <class F, bool CANON, bool SLICE, bool EVAL = false>
 __device__ __forceinline__ void leaf_chunks_cm_body(const uint32_t *__restrict__ m, size_t n_rows, size_t n_cols,
                                                     uint32_t *__restrict__ cvs, uint8_t *__restrict__ leaves,

@@ -123,4 +123,48 @@ hipError_t pos_group_verify(const uint8_t *arena, const PosVerifyJob *jobs, cons
                             const uint8_t *roots, const uint64_t *idx, const uint32_t *want, uint32_t *cvs,
                             uint32_t *partials, uint32_t *bits, hipStream_t s);
 
+// ---- pos_ingest.hip: many small files encoded, hashed and folded to trees in one pass
+// The host builds the tables of a staging group (pos_ingest_host.cpp).
+//   job    an image of n_bytes bytes at byte offset base of the group's arena (a multiple of 8), rows of
+//          pre elements encoded to 2^log_enc; its encoded block [enc][rows_pad] of canonical 8-byte
+//          words at byte offset enc_off of the encoded buffer (a multiple of 16; rows_pad = n_rows
+//          rounded up to even, so every column starts 16-byte aligned and the pad word is never
+//          written); the chaining value of (chunk, column c) is slot cv0 + chunk * enc + c of cvs and
+//          the job's 2 enc - 1 digests start at digest tree0 of trees
+//   tile   rows [row_lo, row_lo + n_rows) of one job, n_rows <= POS_INGEST_TILE_ROWS
+//   wg     n_tiles tiles from tile0 on, all of rows of 2^log_enc points: a workgroup of k_group_encode,
+//          each tile in a slot of POS_INGEST_TILE_ROWS x enc elements of its LDS
+//   wave   columns [col_lo, min(col_lo + 64, enc)) of one job, a lane each, and one 1-KiB chunk of
+//          their leaf messages (k_group_ingest_chunks)
+struct PosIngestJob {
+  uint64_t base, n_bytes, enc_off, cv0, tree0;
+  uint32_t pre, log_enc, n_rows, rows_pad, n_chunks, pad;
+};
+struct PosIngestTile {
+  uint32_t job, row_lo, n_rows, pad;
+};
+struct PosIngestWg {
+  uint32_t tile0, n_tiles, log_enc, pad;
+};
+struct PosIngestWave {
+  uint32_t job, col_lo, chunk, pad;
+};
+constexpr int POS_INGEST_MAX_LOG_ENC = 10;  // == log2(LCPC_POS_INGEST_MAX_ENC): a tile of 8 rows is 64 KiB of LDS
+constexpr size_t POS_INGEST_TILE_ROWS = 8;  // a column segment of a full tile is one 64-byte store
+// elements of a workgroup's LDS: tiles of short rows share a workgroup until it holds this many
+// (8 per thread), a tile of longer rows has one to itself
+constexpr size_t POS_INGEST_WG_ELEMS = 2048;
+constexpr size_t POS_INGEST_MAX_CHUNKS = (size_t)1 << 16;  // chunks of one column's leaf (the fold's stack)
+// the twiddles of the grouped lengths: tw[e] = w^e, w of order 2^POS_INGEST_MAX_LOG_ENC (the forward
+// root of include/lcpc_fft_convention.h), 2^POS_INGEST_MAX_LOG_ENC Montgomery elements
+hipError_t pos_ingest_twiddles(uint32_t *tw, hipStream_t s);
+// The launches of a staging group, at most three: k_group_encode over n_wgs workgroups with lds_bytes
+// of LDS each (none when no job has a row), k_group_ingest_chunks over n_waves waves (4 per
+// workgroup), k_group_ingest_trees with a workgroup per job.  max_chunks: the largest n_chunks of the
+// group's jobs (<= POS_INGEST_MAX_CHUNKS).  n_wgs, n_waves / 4 and n_jobs stay below 2^24.
+hipError_t pos_group_ingest(const uint8_t *arena, const PosIngestJob *jobs, size_t n_jobs, const PosIngestTile *tiles,
+                            const PosIngestWg *wgs, size_t n_wgs, size_t lds_bytes, const PosIngestWave *waves,
+                            size_t n_waves, size_t max_chunks, const uint32_t *tw, uint8_t *enc, uint32_t *cvs,
+                            uint8_t *trees, hipStream_t s);
+
 }  // namespace lcpc

@@ -1274,6 +1274,128 @@ def client_verify_evaluations_grouped(audits) -> list:
     return out
 
 
+# ---------------------------------------------------------------- grouped ingest of small files
+INGEST_MAX_ENC = 1024            # LCPC_POS_INGEST_MAX_ENC: rows of more points take the single path
+INGEST_TILE_ROWS = 8             # LCPC_POS_INGEST_TILE_ROWS
+INGEST_LAUNCHES_PER_GROUP = 3    # LCPC_POS_INGEST_LAUNCHES_PER_GROUP
+DIGEST_BYTES = 32
+
+
+def _job_rows(n_bytes: int, pre: int) -> int:
+    return -(-(-(-n_bytes // DATA_BYTE_CAPACITY)) // pre)
+
+
+def _leaf_chunks(rows: int) -> int:
+    return (32 + WRITTEN_BYTES_WIDTH * rows + 1023) // 1024
+
+
+def ingest_plan(n_bytes, pres, encs):
+    """lcpc_pos_ingest_plan: (tiles, n_groups) for files of n_bytes[j] bytes at dims pres[j] / encs[j].
+    tiles is a structured array with the fields job, row_lo, row_hi, launch and workgroup: the work list
+    of the encode launch of every staging group encode_files_grouped makes (launch = the group), a job
+    routed to the single-file path as one record with launch == GROUP_SINGLE.  Host only, a pure function."""
+    nb, pr, en = _sizes(n_bytes), _sizes(pres), _sizes(encs)
+    if not (nb.size == pr.size == en.size):
+        raise ValueError("n_bytes, pres and encs must have one entry per job")
+    n, launches = C.c_size_t(), C.c_size_t()
+    L = N.load()
+    args = (nb.ctypes.data_as(N.szp), pr.ctypes.data_as(N.szp), en.ctypes.data_as(N.szp), nb.size)
+    _raise(L.lcpc_pos_ingest_plan(*args, None, 0, C.byref(n), C.byref(launches)))
+    dt = np.dtype([("job", "<u8"), ("row_lo", "<u8"), ("row_hi", "<u8"), ("launch", "<u4"), ("workgroup", "<u4")])
+    assert dt.itemsize == C.sizeof(N.PosIngestTile)
+    tiles = np.zeros(n.value, dt)
+    _raise(L.lcpc_pos_ingest_plan(*args, tiles.ctypes.data_as(C.POINTER(N.PosIngestTile)), tiles.size, C.byref(n),
+                                  C.byref(launches)))
+    return tiles, launches.value
+
+
+def _addr(a):
+    """the address of an array's first byte, None for no array or an empty one"""
+    return a.ctypes.data if a is not None and a.size else None
+
+
+def _per_job(value, n: int) -> list:
+    return [bool(value)] * n if isinstance(value, (bool, np.bool_)) else [bool(v) for v in value]
+
+
+def encode_files_grouped_into(datas, pres, encs, porencs=None, row_capacities=None, want_tree=True, want_root=False,
+                              want_cvs=False):
+    """lcpc_pos_encode_files_grouped over caller buffers: job j encodes datas[j] (bytes or a uint8 array, at
+    any address) at pres[j] / encs[j] into porencs[j], a writable contiguous uint8 / uint64 array that holds a
+    column-major image of row_capacities[j] rows (None: no image for that job; porencs=None: for no job, and
+    then no encoded word leaves the device).  want_tree / want_root / want_cvs: a bool or one per job.
+    Returns a list of dicts with rows_written and, where asked, tree ((2 enc - 1, 32) uint8), root (bytes)
+    and cvs ((chunks, enc, 32) uint8).  Rows of an image past rows_written are not touched."""
+    images = [_as_image(d) for d in datas]
+    n = len(images)
+    pres, encs = [int(p) for p in pres], [int(e) for e in encs]
+    if not (len(pres) == len(encs) == n):
+        raise ValueError("datas, pres and encs must have one entry per job")
+    porencs = [None] * n if porencs is None else list(porencs)
+    caps = [0] * n if row_capacities is None else [int(c) for c in row_capacities]
+    if not (len(porencs) == len(caps) == n):
+        raise ValueError("porencs and row_capacities must have one entry per job")
+    trees_on, roots_on, cvs_on = _per_job(want_tree, n), _per_job(want_root, n), _per_job(want_cvs, n)
+    jobs, out = [], []
+    for j in range(n):
+        pre, enc = pres[j], encs[j]
+        ok = pre >= 1 and enc > pre
+        rows = _job_rows(images[j].size, pre) if ok else 0
+        o = {"rows_written": 0}
+        if trees_on[j] and ok:
+            o["tree"] = np.zeros((2 * enc - 1, DIGEST_BYTES), np.uint8)
+        if roots_on[j]:
+            o["root"] = np.zeros(DIGEST_BYTES, np.uint8)
+        if cvs_on[j] and ok:
+            o["cvs"] = np.zeros((_leaf_chunks(rows), enc, DIGEST_BYTES), np.uint8)
+        img = porencs[j]
+        if img is not None:
+            if not (isinstance(img, np.ndarray) and img.flags.c_contiguous and img.flags.writeable):
+                raise ValueError("a porenc must be a writable contiguous array")
+            if img.nbytes < caps[j] * enc * WRITTEN_BYTES_WIDTH:
+                raise ValueError("a porenc is smaller than row_capacity x enc elements")
+        jobs.append(N.PosIngestJob(_addr(images[j]), images[j].size, pre, enc,
+                                   img.ctypes.data if img is not None else None, caps[j], _addr(o.get("tree")),
+                                   _addr(o.get("root")), _addr(o.get("cvs")), 0))
+        out.append(o)
+    arr = (N.PosIngestJob * max(n, 1))(*jobs)
+    _raise(N.load().lcpc_pos_encode_files_grouped(arr if n else None, n))
+    for j, o in enumerate(out):
+        o["rows_written"] = int(arr[j].rows_written)
+        if "root" in o:
+            o["root"] = o["root"].tobytes()
+    del images
+    return out
+
+
+def encode_files_grouped(datas, pres, encs, want_porenc: bool = True, want_cvs: bool = False):
+    """The stored form of many files in one call (lcpc_pos_encode_files_grouped): per file a tuple
+    (image, tree, rows_written[, cvs]) -- image the written rows of the column-major `.porenc` as an
+    (enc, rows_written) uint64 array (None without want_porenc), tree the (2 enc - 1, 32) digests of the
+    `.portree`, cvs the [chunk][column] chaining values of the `.porcv` sidecar -- each byte for byte what
+    one lcpc_pos_encode_file per file gives, with a number of launches that does not grow with the number
+    of files (files whose rows have more than INGEST_MAX_ENC points take that path inside the call)."""
+    images = [_as_image(d) for d in datas]
+    pres, encs = [int(p) for p in pres], [int(e) for e in encs]
+    porencs = caps = None
+    if want_porenc:
+        caps = [_job_rows(a.size, p) if p >= 1 else 0 for a, p in zip(images, pres)]
+        porencs = [np.zeros((e, c), np.uint64) for e, c in zip(encs, caps)]
+    res = encode_files_grouped_into(images, pres, encs, porencs, caps, True, False, want_cvs)
+    out = []
+    for j, o in enumerate(res):
+        t = (porencs[j] if want_porenc else None, o["tree"], o["rows_written"])
+        out.append(t + (o["cvs"],) if want_cvs else t)
+    return out
+
+
+def commit_roots_of_files(datas, pres, encs) -> List[bytes]:
+    """The Merkle root of every file's stored form (RowGeneratorIter.convert_to_commit_root per file) in
+    one grouped call; no encoded word is copied back from the device."""
+    res = encode_files_grouped_into(datas, pres, encs, None, None, False, True, False)
+    return [o["root"] for o in res]
+
+
 def field_to_montgomery(values, field: int = FT63) -> np.ndarray:
     """lcpc_field_to_montgomery: (v R) mod p per 64-bit word, R = 2^64 (Ft63 only): canonical values,
     as a `.porenc` holds them, to the Montgomery words a commitment opens.  Same shape as `values`."""

@@ -545,6 +545,68 @@ class EncodedFileWriter:
             write_chunk_cv_sidecar(target_chunk_cv_file, num_encoded_columns, rows.value, mt.root(), cvs)
         return meta, mt
 
+    @staticmethod
+    def convert_unencoded_files(items) -> List[Tuple[EncodedFileMetadata, MerkleTree]]:
+        """convert_unencoded_file for many files in one grouped pass (lcpc_pos_encode_files_grouped): items
+        is a sequence of its argument tuples (unencoded_file, target_encoded_file, target_digest_file,
+        target_metadata_file, num_pre_encoded_columns, num_encoded_columns[, target_chunk_cv_file]).  Every
+        file written is byte for byte what the single call writes; the launches do not grow with the
+        number of files.  Every item's dims are checked before the first target is created."""
+        from .pos import encode_files_grouped_into
+        items = [tuple(it) + (None,) * (7 - len(it)) for it in items]
+        for it in items:
+            pre, enc = it[4], it[5]
+            if pre < 1:
+                raise ValueError("Number of pre-encoded columns must be greater than 0")
+            if enc < 2 or enc & (enc - 1):
+                raise ValueError("Number of encoded columns must be a power of 2")
+            if enc <= pre:
+                raise ValueError("Number of encoded columns must be greater than the number of columns")
+        if not items:
+            return []
+        totals, caps, files, imgs, srcs, datas = [], [], [], [], [], []
+        try:
+            for src_f, target, _, _, pre, enc, _ in items:
+                src_f.seek(0, os.SEEK_END)
+                total = src_f.tell()
+                src_f.seek(0)
+                cap = 2 * (-(-(-(-total // DATA_BYTE_CAPACITY)) // pre))
+                tf = open(target, "w+b")
+                files.append(tf)
+                imgs.append(_Image(tf, cap * enc * WRITTEN_BYTES_WIDTH))
+                src = mmap.mmap(src_f.fileno(), total, access=mmap.ACCESS_READ) if total else None
+                srcs.append(src)
+                datas.append(np.frombuffer(src, np.uint8) if total else np.zeros(0, np.uint8))
+                totals.append(total)
+                caps.append(cap)
+            res = encode_files_grouped_into(datas, [it[4] for it in items], [it[5] for it in items],
+                                            [im.arr for im in imgs], caps, True, False,
+                                            [it[6] is not None for it in items])
+        finally:
+            del datas
+            for src in srcs:
+                if src is not None:
+                    src.close()
+            for im in imgs:
+                im.close()
+            for tf in files:
+                tf.close()
+        out = []
+        for it, total, cap, o in zip(items, totals, caps, res):
+            _, _, digest_file, meta_file, pre, enc, cv_file = it
+            meta = EncodedFileMetadata(pre, enc, o["rows_written"], cap, total)
+            mt = MerkleTree(o["tree"])
+            if meta_file:
+                with open(meta_file, "wb") as f:
+                    meta.write_to_file(f)
+            if digest_file:
+                with open(digest_file, "wb") as f:
+                    write_tree_to_file(f, mt)
+            if cv_file:
+                write_chunk_cv_sidecar(cv_file, enc, o["rows_written"], mt.root(), o["cvs"])
+            out.append((meta, mt))
+        return out
+
 
 def _writer_chunk_cvs(writer_handle, enc: int) -> np.ndarray:
     """The [chunk][column] CVs of a finalized lcpc_pos_writer."""
@@ -1075,6 +1137,51 @@ class FileHandler:
         with open(meta, "wb") as f:
             m.write_to_file(f)
         return cls(ulid, raw, enc, tree, meta, chunk_cache=chunk_cache)
+
+    @classmethod
+    def create_from_unencoded_files(cls, specs, directory: Optional[str] = None,
+                                    chunk_cache: bool = False) -> List["FileHandler"]:
+        """create_from_unencoded_file for many files in one grouped pass: specs is a sequence of (ulid,
+        file_handle_if_not_already_ulid or None, pre_encoded_size, encoded_size).  The `.porraw`, `.porenc`,
+        `.portree`, `.meta` and (chunk_cache) `.porcv` files are byte for byte those of a loop of the single
+        call.  Every spec is checked before the first file is renamed or created."""
+        specs = [tuple(s) for s in specs]
+        for ulid, src, pre, enc in specs:
+            if enc <= 0 or enc & (enc - 1):
+                raise ValueError("encoded file size must be a power of two!")
+            if pre < 1:
+                raise ValueError("Number of pre-encoded columns must be greater than 0")
+            if enc < 2 or enc <= pre:
+                raise ValueError("Number of encoded columns must be greater than the number of columns")
+            if src is not None and not os.path.isfile(src):
+                raise FileNotFoundError(f"no unencoded file found for {ulid}!")
+        if len({s[0] for s in specs}) != len(specs):
+            raise ValueError("every file needs a ulid of its own")
+        paths = []
+        for ulid, src, pre, enc in specs:
+            p = [_location(directory, ulid, e) for e in (UNENCODED_FILE_EXTENSION, ENCODED_FILE_EXTENSION,
+                                                         MERKLE_FILE_EXTENSION, METADATA_FILE_EXTENSION)]
+            p.append(_location(directory, ulid, CHUNK_CV_EXTENSION) if chunk_cache else None)
+            if src is None and not os.path.isfile(p[0]):
+                raise FileNotFoundError(f"no unencoded file found for {ulid}!")
+            paths.append(p)
+        for (ulid, src, pre, enc), p in zip(specs, paths):
+            if src is not None:
+                os.rename(src, p[0])
+        raws = [open(p[0], "r+b") for p in paths]
+        try:
+            metas = EncodedFileWriter.convert_unencoded_files(
+                [(f, p[1], p[2], p[3], pre, enc, p[4]) for f, p, (_, _, pre, enc) in zip(raws, paths, specs)])
+        finally:
+            for f in raws:
+                f.close()
+        out = []
+        for (ulid, _, _, _), p, (m, _) in zip(specs, paths, metas):
+            m.ulid = ulid
+            with open(p[3], "wb") as f:
+                m.write_to_file(f)
+            out.append(cls(ulid, p[0], p[1], p[2], p[3], chunk_cache=chunk_cache))
+        return out
 
     # -- accessors
     def get_encoded_file_handle(self) -> str:
