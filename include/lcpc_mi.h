@@ -56,7 +56,8 @@ extern "C" {
  * lcpc_pos_group_plan, lcpc_field_to_montgomery).  So is the grouped check of stored-file audit
  * responses (lcpc_pos_audit_job, lcpc_pos_verify_evaluations_grouped, lcpc_pos_verify_tile,
  * lcpc_pos_verify_group_plan).  So is the grouped ingest of small files (lcpc_pos_ingest_job,
- * lcpc_pos_encode_files_grouped, lcpc_pos_ingest_tile, lcpc_pos_ingest_plan). */
+ * lcpc_pos_encode_files_grouped, lcpc_pos_ingest_tile, lcpc_pos_ingest_plan).  So is the grouped scrub of
+ * stored files (lcpc_pos_scrub_job, lcpc_pos_scrub_files_grouped, lcpc_pos_scrub_plan). */
 #define LCPC_ABI_VERSION 3
 
 typedef enum lcpc_status {
@@ -810,6 +811,77 @@ typedef struct lcpc_pos_ingest_tile {
 } lcpc_pos_ingest_tile;
 lcpc_status lcpc_pos_ingest_plan(const size_t *n_bytes, const size_t *pre, const size_t *enc, size_t n_jobs,
                                  lcpc_pos_ingest_tile *tiles, size_t cap, size_t *n_tiles, size_t *n_launches);
+/* ---- PoS grouped scrub: many stored files checked against leaves, tree and row code in one pass ----
+ * NO COUNTERPART IN THE REFERENCE (verify_all_files_agree, file_handler.rs:505-541, is per file and can
+ * only say "trees differ").  Additive within LCPC_ABI_VERSION 3.  The triage of a scrubber that walks a
+ * whole store: which of these files need the per-file locate or repair?  A queue of (stored image, stored
+ * digests, expected root) jobs is answered with a number of launches that does not grow with the number
+ * of files; lcpc_pos_locate_porenc, lcpc_pos_repair_columns and the Berlekamp-Massey locator stay what
+ * they are and are reached only for the files with a finding.
+ * EQUALITY: for every job,
+ *   col_status, digests, n_bad   are byte for byte what lcpc_pos_scrub_porenc over (porenc, enc,
+ *       rows_written, row_capacity, tree as leaves) returns: 0 the column's digest equals its stored
+ *       leaf, 1 it differs, 2 the column holds an element that is not < p (its digest written as zeros).
+ *       With tree == NULL the compare is skipped: 0 or 2 only, digests still filled.  The status is
+ *       decided on the device against the caller's leaves; the library's digests are never compared with
+ *       themselves.  Rows at and past rows_written are never read;
+ *   tree_consistent   1 iff tree_digests == 2 enc - 1 and every stored parent is the BLAKE3 node hash of
+ *       its two STORED children, which by induction from the leaves up is MerkleTree::new(the first enc
+ *       digests) == tree; 0 otherwise; LCPC_POS_SCRUB_NOT_EVALUATED for tree_digests 0 or enc;
+ *   root_ok           stored root == expected_root; LCPC_POS_SCRUB_NOT_EVALUATED without a whole tree or
+ *       without an expected_root;
+ *   n_dirty_rows      the number of rows r < rows_written whose enc stored elements are not the
+ *       evaluations of a polynomial of degree < pre.  For a job without a status-2 column this is exactly
+ *       *n_dirty_rows of lcpc_pos_locate_porenc with no known_bad.  A job with a status-2 column reports
+ *       LCPC_POS_SCRUB_ROWS_UNCHECKED: it has a finding anyway, and the per-file path treats such
+ *       columns as erasures; the grouped pass masks nothing.
+ * A job with rows_written == 0 is legal: the digests of zero rows, n_dirty_rows = 0.
+ * STAGING: consecutive jobs form a staging group of at most LCPC_POS_GROUP_STAGE_BYTES of packed image
+ * (LCPC_POS_GROUP_BYTES, the test seam, can only lower it; also bounded as the ingest's groups in jobs,
+ * rows, tiles and tree bytes).  The host packs, per column, only the first rows_written elements (rounded
+ * up to even, the pad word zero): the slack up to row_capacity never crosses the bus.  Stored digests,
+ * expected roots and tables go up in the same copy; flags, statuses, dirty bytes and (where a job asks)
+ * digests come back in one.  Two page-locked blocks alternate: the host packs group g + 1 while g runs.
+ * A group takes at most LCPC_POS_SCRUB_LAUNCHES_PER_GROUP kernel launches, whatever the number of jobs
+ * or of distinct enc, all inside one profiling region (pos_group_scrub).
+ * ROUTING: a job with enc > LCPC_POS_SCRUB_MAX_ENC, or whose packed image alone exceeds a group, or whose
+ * columns have more than 2^16 1-KiB chunks, ends the group before it and is answered inside the same
+ * call by lcpc_pos_scrub_porenc and the dirty-row count of lcpc_pos_locate_porenc (its stored tree by
+ * the group's third launch alone), to the same equalities.
+ * Errors, before any device work and before any output byte is written: a NULL jobs, n_jobs == 0, a
+ * NULL col_status, porenc == NULL with rows_written > 0, rows_written > row_capacity, pre == 0, enc no
+ * power of two or enc <= pre, tree_digests not 0, enc or 2 enc - 1, tree NULL with tree_digests != 0 or
+ * the reverse: LCPC_ERR_INVALID_ARG; enc beyond the field's two-adicity: LCPC_FFT_TOO_BIG; no device:
+ * LCPC_ERR_NO_DEVICE.  Ft63 and BLAKE3 only.  Threading as every entry: a stream of its own per call. */
+#define LCPC_POS_SCRUB_MAX_ENC ((size_t)1024)  /* as LCPC_POS_INGEST_MAX_ENC: 8 rows = 64 KiB of LDS */
+#define LCPC_POS_SCRUB_TILE_ROWS ((size_t)8)   /* rows of a full tile of the row-check launch */
+#define LCPC_POS_SCRUB_LAUNCHES_PER_GROUP 3    /* row check, chunk chaining values, leaves + status + tree check */
+#define LCPC_POS_SCRUB_NOT_EVALUATED ((uint8_t)0xFF)
+#define LCPC_POS_SCRUB_ROWS_UNCHECKED ((size_t)-1)
+typedef struct lcpc_pos_scrub_job {
+  const uint8_t *porenc;        /* column-major image, layout of lcpc_pos_encode_file; NULL iff rows_written == 0 */
+  size_t pre, enc, rows_written, row_capacity;
+  const uint8_t *tree;          /* stored digests, or NULL */
+  size_t tree_digests;          /* 0 (tree NULL), enc (leaves only) or 2 enc - 1 (the whole .portree) */
+  const uint8_t *expected_root; /* 32 B, or NULL */
+  uint8_t *col_status;          /* enc bytes, out, required */
+  uint8_t *digests;             /* enc x 32 B, out, may be NULL */
+  size_t n_bad;                 /* out: non-zero status bytes */
+  size_t n_dirty_rows;          /* out */
+  uint8_t tree_consistent;      /* out: 1 / 0 / LCPC_POS_SCRUB_NOT_EVALUATED */
+  uint8_t root_ok;              /* out: 1 / 0 / LCPC_POS_SCRUB_NOT_EVALUATED */
+} lcpc_pos_scrub_job;
+lcpc_status lcpc_pos_scrub_files_grouped(lcpc_pos_scrub_job *jobs, size_t n_jobs);
+/* Host-only, no device (like lcpc_pos_ingest_plan): the work list of the row-check launch of each staging
+ * group the entry above makes for jobs of these row counts and dims, a pure function of its arguments
+ * (and of LCPC_POS_GROUP_BYTES).  A record is a tile: rows [row_lo, row_hi) of one job, at most
+ * LCPC_POS_SCRUB_TILE_ROWS of them; `launch` counts the staging groups from 0 and `workgroup` the
+ * workgroups of the group's row-check launch: the tiles of a workgroup share enc.  A routed job has one
+ * record with launch = LCPC_POS_GROUP_SINGLE, workgroup = 0, over all its rows.  Every (job, row) is in
+ * exactly one record; a job with zero rows has none (it still belongs to a group).  Outputs and errors as
+ * lcpc_pos_ingest_plan. */
+lcpc_status lcpc_pos_scrub_plan(const size_t *rows_written, const size_t *pre, const size_t *enc, size_t n_jobs,
+                                lcpc_pos_ingest_tile *tiles, size_t cap, size_t *n_tiles, size_t *n_launches);
 /* The streaming writer itself: EncodedFileWriter::new (:40-105; porenc = the preallocated
  * image of row_capacity rows, batch_rows as above), push_bytes (:233-262), and
  * finalize_to_column_digest / _to_commit / _to_merkle_tree (:452-501): digests = the enc column

@@ -23,3 +23,6 @@ from .pos_files import answer_evaluation_requests  # noqa: F401,E402
 from .pos import client_verify_evaluation, client_verify_evaluations_grouped, verify_group_plan  # noqa: F401,E402
 # many small files turned into stored files, or into their roots, in one pass
 from .pos import commit_roots_of_files, encode_files_grouped, ingest_plan  # noqa: F401,E402
+# the scrubber's triage of many stored files in one pass
+from .pos import scrub_files_grouped, scrub_plan  # noqa: F401,E402
+from .pos_files import scrub_files  # noqa: F401,E402

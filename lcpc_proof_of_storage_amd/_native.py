@@ -82,6 +82,14 @@ class PosIngestTile(C.Structure):
                 ("workgroup", C.c_uint32)]
 
 
+class PosScrubJob(C.Structure):
+    """lcpc_pos_scrub_job (include/lcpc_mi.h)"""
+    _fields_ = [("porenc", vp), ("pre", C.c_size_t), ("enc", C.c_size_t), ("rows_written", C.c_size_t),
+                ("row_capacity", C.c_size_t), ("tree", vp), ("tree_digests", C.c_size_t), ("expected_root", vp),
+                ("col_status", vp), ("digests", vp), ("n_bad", C.c_size_t), ("n_dirty_rows", C.c_size_t),
+                ("tree_consistent", C.c_uint8), ("root_ok", C.c_uint8)]
+
+
 class CommOps(C.Structure):
     _fields_ = [("user", vp), ("all_gather", ALL_GATHER_FN), ("all_to_all_v", ALL_TO_ALL_V_FN),
                 ("broadcast", BROADCAST_FN)]
@@ -231,6 +239,8 @@ SIGNATURES = {
     "lcpc_pos_verify_group_plan": (i32, [szp, szp, szp, sz, C.POINTER(PosVerifyTile), sz, szp, szp]),
     "lcpc_pos_encode_files_grouped": (i32, [C.POINTER(PosIngestJob), sz]),
     "lcpc_pos_ingest_plan": (i32, [szp, szp, szp, sz, C.POINTER(PosIngestTile), sz, szp, szp]),
+    "lcpc_pos_scrub_files_grouped": (i32, [C.POINTER(PosScrubJob), sz]),
+    "lcpc_pos_scrub_plan": (i32, [szp, szp, szp, sz, C.POINTER(PosIngestTile), sz, szp, szp]),
     "lcpc_pos_update_rows": (i32, [sz, sz, sz, sz, szp, szp, szp, szp]),
     "lcpc_pos_update_evaluation": (i32, [vp, vp, sz, vp, vp, sz, u64p, u64p, sz, u64p, sz,
                                          u64p, u64p, u8p, u8p, u64p, u64p, u8p, u8p, u64p]),

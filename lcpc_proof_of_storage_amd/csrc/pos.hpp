@@ -167,4 +167,32 @@ hipError_t pos_group_ingest(const uint8_t *arena, const PosIngestJob *jobs, size
                             size_t n_waves, size_t max_chunks, const uint32_t *tw, uint8_t *enc, uint32_t *cvs,
                             uint8_t *trees, hipStream_t s);
 
+// ---- pos_scrub.hip: many stored files checked against their leaves, trees and the row code in one pass
+// (DESIGN §5j).  The host builds the tables of a staging group (pos_scrub_host.cpp); tiles, workgroups
+// and waves are the ingest's records.
+//   job    the first n_rows rows of a stored image, packed [enc][rows_pad] canonical 8-byte words at byte
+//          offset img of the group's arena (a multiple of 16; rows_pad = n_rows rounded up to even, the
+//          pad word zero); its stored digests (tree_kind 1: the enc leaves, 2: all 2 enc - 1) at byte
+//          offset tree and, with has_root, the root to expect at byte offset root (multiples of 16); the
+//          chaining value and the canonicity flag of (chunk, column c) are slot cv0 + chunk * enc + c of
+//          cvs / cflags; its columns are [col0, col0 + enc) of the group's status and digests and its
+//          rows [row0, row0 + n_rows) of the group's dirty bytes.  tree_only: a job routed to the
+//          single-file entries, whose stored tree alone is checked here (no rows, no columns).
+struct PosScrubJob {
+  uint64_t img, tree, root, cv0, col0, row0;
+  uint32_t pre, log_enc, n_rows, rows_pad, n_chunks, tree_kind, has_root, tree_only;
+};
+constexpr uint8_t POS_SCRUB_NOT_EVALUATED = 0xff;  // == LCPC_POS_SCRUB_NOT_EVALUATED
+// The launches of a staging group, at most three: k_group_scrub_rows over n_wgs workgroups with
+// lds_bytes of LDS each (none when no job has a row): dirty[row] = the row is no codeword;
+// k_group_scrub_chunks over n_waves waves (4 per workgroup; none for tree-only jobs);
+// k_group_scrub_leaves with a workgroup per job: status and digests per column, and per job
+// flags[2 j] = the stored parents hash from their stored children, flags[2 j + 1] = the stored root is the
+// expected one (POS_SCRUB_NOT_EVALUATED where there is nothing to compare).  tw: pos_ingest_twiddles.
+// max_chunks as pos_group_ingest; n_wgs, n_waves / 4 and n_jobs stay below 2^24.
+hipError_t pos_group_scrub(const uint8_t *arena, const PosScrubJob *jobs, size_t n_jobs, const PosIngestTile *tiles,
+                           const PosIngestWg *wgs, size_t n_wgs, size_t lds_bytes, const PosIngestWave *waves,
+                           size_t n_waves, size_t max_chunks, const uint32_t *tw, uint32_t *cvs, uint8_t *cflags,
+                           uint8_t *flags, uint8_t *status, uint8_t *dirty, uint8_t *digests, hipStream_t s);
+
 }  // namespace lcpc

@@ -1396,6 +1396,95 @@ def commit_roots_of_files(datas, pres, encs) -> List[bytes]:
     return [o["root"] for o in res]
 
 
+# ---------------------------------------------------------------- grouped scrub of stored files
+SCRUB_MAX_ENC = 1024             # LCPC_POS_SCRUB_MAX_ENC: rows of more points take the single-file entries
+SCRUB_TILE_ROWS = 8              # LCPC_POS_SCRUB_TILE_ROWS
+SCRUB_LAUNCHES_PER_GROUP = 3     # LCPC_POS_SCRUB_LAUNCHES_PER_GROUP
+_SCRUB_NOT_EVALUATED = 0xFF      # LCPC_POS_SCRUB_NOT_EVALUATED
+_SCRUB_ROWS_UNCHECKED = (1 << (8 * C.sizeof(C.c_size_t))) - 1   # LCPC_POS_SCRUB_ROWS_UNCHECKED
+
+
+def scrub_plan(rows_written, pres, encs):
+    """lcpc_pos_scrub_plan: (tiles, n_groups) for stored files of rows_written[j] rows at dims pres[j] /
+    encs[j].  tiles is a structured array with the fields job, row_lo, row_hi, launch and workgroup: the
+    work list of the row-check launch of every staging group scrub_files_grouped makes (launch = the
+    group), a job routed to the single-file entries as one record with launch == GROUP_SINGLE.  Host
+    only, a pure function."""
+    rw, pr, en = _sizes(rows_written), _sizes(pres), _sizes(encs)
+    if not (rw.size == pr.size == en.size):
+        raise ValueError("rows_written, pres and encs must have one entry per job")
+    n, launches = C.c_size_t(), C.c_size_t()
+    L = N.load()
+    args = (rw.ctypes.data_as(N.szp), pr.ctypes.data_as(N.szp), en.ctypes.data_as(N.szp), rw.size)
+    _raise(L.lcpc_pos_scrub_plan(*args, None, 0, C.byref(n), C.byref(launches)))
+    dt = np.dtype([("job", "<u8"), ("row_lo", "<u8"), ("row_hi", "<u8"), ("launch", "<u4"), ("workgroup", "<u4")])
+    assert dt.itemsize == C.sizeof(N.PosIngestTile)
+    tiles = np.zeros(n.value, dt)
+    _raise(L.lcpc_pos_scrub_plan(*args, tiles.ctypes.data_as(C.POINTER(N.PosIngestTile)), tiles.size, C.byref(n),
+                                 C.byref(launches)))
+    return tiles, launches.value
+
+
+def _byte_view(data) -> np.ndarray:
+    """the bytes of a stored image (an array of any dtype, an mmap, bytes) without a copy where it is contiguous"""
+    if isinstance(data, np.ndarray):
+        return np.ascontiguousarray(data).reshape(-1).view(np.uint8)
+    return np.frombuffer(data, np.uint8)
+
+
+def scrub_files_grouped(images, pres, encs, rows_written, row_capacities, trees=None, expected_roots=None,
+                        want_digests: bool = False) -> list:
+    """lcpc_pos_scrub_files_grouped: the triage of many stored files in one call.  Job j is the column-major
+    `.porenc` image images[j] (a numpy array or an mmap of row_capacities[j] x encs[j] elements, None with no
+    rows) of which rows_written[j] rows count, trees[j] its stored digests (None, the encs[j] leaves, or the
+    whole 2 enc - 1 `.portree`, as bytes or a uint8 array) and expected_roots[j] the root its owner holds
+    (32 bytes or None).  Returns one dict per job: status ((enc,) uint8: 0 the column's digest equals its
+    stored leaf, 1 it differs, 2 it holds an element that is not < p; without a tree 0 or 2 only), digests
+    ((enc, 32) uint8 with want_digests, else None), n_bad, n_dirty_rows (the rows that are no codewords of
+    the row code; None where a status-2 column leaves them unchecked), tree_consistent and root_ok (None
+    where there is nothing to evaluate).  Status, digests and n_bad are those of lcpc_pos_scrub_porenc and
+    n_dirty_rows that of lcpc_pos_locate_porenc per file; the launches are per staging group of files."""
+    n = len(images)
+    pres, encs = [int(p) for p in pres], [int(e) for e in encs]
+    rows, caps = [int(r) for r in rows_written], [int(c) for c in row_capacities]
+    trees = [None] * n if trees is None else list(trees)
+    roots = [None] * n if expected_roots is None else list(expected_roots)
+    if not (len(pres) == len(encs) == len(rows) == len(caps) == len(trees) == len(roots) == n):
+        raise ValueError("every argument must have one entry per job")
+    jobs, keep, out = [], [], []
+    for j in range(n):
+        enc = encs[j]
+        img = None if images[j] is None else _byte_view(images[j])
+        if img is not None and img.size < caps[j] * enc * WRITTEN_BYTES_WIDTH:
+            raise ValueError(f"job {j}: the image is smaller than row_capacity x enc elements")
+        tree = None if trees[j] is None else _byte_view(trees[j])
+        if tree is not None and tree.size % DIGEST_BYTES:
+            raise ValueError(f"job {j}: a tree is whole 32-byte digests")
+        root = None if roots[j] is None else np.frombuffer(bytes(roots[j]), np.uint8)
+        if root is not None and root.size != DIGEST_BYTES:
+            raise ValueError(f"job {j}: an expected root is 32 bytes")
+        status = np.zeros(max(enc, 0), np.uint8)
+        digests = np.zeros((max(enc, 0), DIGEST_BYTES), np.uint8) if want_digests else None
+        keep.append((img, tree, root))
+        jobs.append(N.PosScrubJob(_addr(img), pres[j], enc, rows[j], caps[j], _addr(tree),
+                                  tree.size // DIGEST_BYTES if tree is not None else 0, _addr(root),
+                                  status.ctypes.data if status.size else None, _addr(digests), 0, 0, 0, 0))
+        out.append({"status": status, "digests": digests})
+    arr = (N.PosScrubJob * max(n, 1))(*jobs)
+    _raise(N.load().lcpc_pos_scrub_files_grouped(arr if n else None, n))
+    del keep
+
+    def flag(v):
+        return None if v == _SCRUB_NOT_EVALUATED else bool(v)
+    for j, o in enumerate(out):
+        o["n_bad"] = int(arr[j].n_bad)
+        nd = int(arr[j].n_dirty_rows)
+        o["n_dirty_rows"] = None if nd == _SCRUB_ROWS_UNCHECKED else nd
+        o["tree_consistent"] = flag(arr[j].tree_consistent)
+        o["root_ok"] = flag(arr[j].root_ok)
+    return out
+
+
 def field_to_montgomery(values, field: int = FT63) -> np.ndarray:
     """lcpc_field_to_montgomery: (v R) mod p per 64-bit word, R = 2^64 (Ft63 only): canonical values,
     as a `.porenc` holds them, to the Montgomery words a commitment opens.  Same shape as `values`."""

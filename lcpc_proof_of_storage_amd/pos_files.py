@@ -1587,6 +1587,10 @@ class FileHandler:
         except (UnrecoverableError, OSError):
             report = ScrubReport(bad_columns=[], noncanonical_columns=[], tree_consistent=False,
                                  root_ok=None if expected_root is None else False, raw_ok=False)
+        return self._locate_report(report)
+
+    def _locate_report(self, report: ScrubReport) -> ScrubReport:
+        """The locate half of scrub(locate=True) over a report of the tree's findings."""
         try:
             status = self._locate_into(report)
             if not report.bad_columns and not report.tree_consistent:
@@ -1776,6 +1780,124 @@ class FileHandler:
         d = os.path.dirname(self.unencoded_file_handle)
         if not os.listdir(d):
             os.rmdir(d)
+
+
+# -- grouped scrub
+# files mapped at once by scrub_files: an image and a raw file each hold a descriptor while their batch runs
+_SCRUB_FILES_BATCH = 192
+
+
+def _close_map(mm) -> None:
+    try:
+        mm.close()
+    except BufferError:  # an in-flight exception's traceback still holds a view
+        pass
+
+
+def _scrub_files_batch(handlers, roots, locate: bool) -> List[ScrubReport]:
+    from .pos import encode_files_grouped_into, scrub_files_grouped
+    trees: List[Optional[MerkleTree]] = []
+    for h in handlers:
+        try:
+            trees.append(h._stored_tree())
+        except (UnrecoverableError, OSError):
+            if not locate:   # scrub() raises; scrub(locate=True) reports a file without a usable tree
+                raise
+            trees.append(None)
+    files, maps, images = [], [], []
+    try:
+        for h in handlers:
+            need = h.row_capacity * h.encoded_size * WRITTEN_BYTES_WIDTH
+            f = open(h.encoded_file_handle, "rb")
+            files.append(f)
+            if os.fstat(f.fileno()).st_size < need:
+                raise ValueError("encoded file shorter than row_capacity * encoded_size elements")
+            mm = mmap.mmap(f.fileno(), need, access=mmap.ACCESS_READ) if need else None
+            maps.append(mm)
+            images.append(np.frombuffer(mm, np.uint8) if need else None)
+        res = scrub_files_grouped(
+            images, [h.pre_encoded_size for h in handlers], [h.encoded_size for h in handlers],
+            [h.rows_written for h in handlers], [h.row_capacity for h in handlers],
+            [None if t is None else t.digests for t in trees],
+            [None if t is None else r for t, r in zip(trees, roots)])
+    finally:
+        del images
+        for mm in maps:
+            if mm is not None:
+                _close_map(mm)
+        for f in files:
+            f.close()
+    # raw_ok: one grouped ingest of the raw files that can still match, trees only
+    raw_trees: List[Optional[np.ndarray]] = [None] * len(handlers)
+    files, maps, datas, who = [], [], [], []
+    try:
+        for i, h in enumerate(handlers):
+            if trees[i] is None:
+                continue
+            try:
+                if os.path.getsize(h.unencoded_file_handle) != h.total_data_bytes:
+                    continue
+                f = open(h.unencoded_file_handle, "rb")
+            except OSError:
+                continue
+            files.append(f)
+            mm = mmap.mmap(f.fileno(), h.total_data_bytes, access=mmap.ACCESS_READ) if h.total_data_bytes else None
+            maps.append(mm)
+            datas.append(np.frombuffer(mm, np.uint8) if mm is not None else np.zeros(0, np.uint8))
+            who.append(i)
+        if who:
+            enc = encode_files_grouped_into(datas, [handlers[i].pre_encoded_size for i in who],
+                                            [handlers[i].encoded_size for i in who], None, None, True, False, False)
+            for i, o in zip(who, enc):
+                raw_trees[i] = o["tree"]
+    finally:
+        del datas
+        for mm in maps:
+            if mm is not None:
+                _close_map(mm)
+        for f in files:
+            f.close()
+    out = []
+    for h, tree, root, r, raw in zip(handlers, trees, roots, res, raw_trees):
+        status = r["status"]
+        if tree is None:
+            report = ScrubReport(bad_columns=[], noncanonical_columns=[], tree_consistent=False,
+                                 root_ok=None if root is None else False, raw_ok=False)
+        else:
+            report = ScrubReport(
+                bad_columns=[int(c) for c in np.flatnonzero(status)],
+                noncanonical_columns=[int(c) for c in np.flatnonzero(status == 2)],
+                tree_consistent=bool(r["tree_consistent"]),
+                root_ok=None if root is None else bool(r["root_ok"]),
+                raw_ok=raw is not None and np.array_equal(raw, tree.digests))
+        if locate:
+            if r["n_dirty_rows"] == 0 and not (status == 2).any():
+                # every row a codeword and every word canonical: what the locator returns for such a file
+                report.located_columns, report.unlocatable_rows = [], 0
+            else:
+                h._locate_report(report)
+        out.append(report)
+    return out
+
+
+def scrub_files(handlers, expected_roots=None, locate: bool = False) -> List[ScrubReport]:
+    """FileHandler.scrub for many stored files in grouped passes: entry i equals
+    handlers[i].scrub(expected_root=expected_roots[i], locate=locate) field by field.  Every `.porenc` is
+    mapped and every `.portree` read; column statuses, the trees' consistency, their roots and the rows
+    that are no codewords come from lcpc_pos_scrub_files_grouped, and raw_ok from one grouped ingest of the
+    raw files (trees only) per batch of files.  A tree file that is missing or of the wrong length raises
+    as scrub does with locate=False and is the finding scrub(locate=True) reports otherwise.  With
+    locate=True a file whose rows are all codewords and whose words are all canonical needs no per-file
+    device call; every other file goes through its handler's own locate.  A clean store is scrubbed, locate
+    included, with launches per staging group of files, not per file."""
+    handlers = list(handlers)
+    roots = [None] * len(handlers) if expected_roots is None else list(expected_roots)
+    if len(roots) != len(handlers):
+        raise ValueError("expected_roots must have one entry per handler")
+    out: List[ScrubReport] = []
+    for lo in range(0, len(handlers), _SCRUB_FILES_BATCH):
+        out += _scrub_files_batch(handlers[lo:lo + _SCRUB_FILES_BATCH], roots[lo:lo + _SCRUB_FILES_BATCH], locate)
+    return out
 
 
 # -- grouped audits (DESIGN.md §5g)
