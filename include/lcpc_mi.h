@@ -57,7 +57,8 @@ extern "C" {
  * responses (lcpc_pos_audit_job, lcpc_pos_verify_evaluations_grouped, lcpc_pos_verify_tile,
  * lcpc_pos_verify_group_plan).  So is the grouped ingest of small files (lcpc_pos_ingest_job,
  * lcpc_pos_encode_files_grouped, lcpc_pos_ingest_tile, lcpc_pos_ingest_plan).  So is the grouped scrub of
- * stored files (lcpc_pos_scrub_job, lcpc_pos_scrub_files_grouped, lcpc_pos_scrub_plan). */
+ * stored files (lcpc_pos_scrub_job, lcpc_pos_scrub_files_grouped, lcpc_pos_scrub_plan).  So is the grouped
+ * repair of stored files (lcpc_pos_repair_job, lcpc_pos_repair_files_grouped, lcpc_pos_repair_plan). */
 #define LCPC_ABI_VERSION 3
 
 typedef enum lcpc_status {
@@ -882,6 +883,64 @@ lcpc_status lcpc_pos_scrub_files_grouped(lcpc_pos_scrub_job *jobs, size_t n_jobs
  * lcpc_pos_ingest_plan. */
 lcpc_status lcpc_pos_scrub_plan(const size_t *rows_written, const size_t *pre, const size_t *enc, size_t n_jobs,
                                 lcpc_pos_ingest_tile *tiles, size_t cap, size_t *n_tiles, size_t *n_launches);
+/* ---- PoS grouped repair: the damaged columns of many stored files recomputed, hashed and folded into
+ * their trees in one pass ----
+ * NO COUNTERPART IN THE REFERENCE.  Additive within LCPC_ABI_VERSION 3.  The leg after a scrub: every file
+ * with a finding went through lcpc_pos_repair_columns on its own.  Here a queue of (stored image, erasure
+ * set, leaves) jobs is answered with a number of launches that does not grow with the number of files.
+ * EQUALITY: for every job, status, cols_out and digests_out are byte for byte what
+ * lcpc_pos_repair_columns(porenc, pre, enc, rows_written, row_capacity, bad_cols, n_bad, ...) returns and
+ * writes; tree_out / root_out are MerkleTree::new over `leaves` with the entries of bad_cols replaced by
+ * the repaired digests.
+ * VERDICTS are per job: one job's failure never fails the call and never touches a neighbour's outputs.
+ * status is LCPC_ERR_UNRECOVERABLE when n_bad > enc - pre (that job does no device work), when some row
+ * is no codeword on the columns that are not listed (checked whenever n_bad < enc - pre), or when a
+ * column that is not listed holds a word that is not < p.  The data outputs of a failed job are
+ * unspecified.  n_bad == 0 is the consistency check alone; rows_written == 0 is legal (the digests of
+ * zero rows).  LISTED COLUMNS ARE NEVER READ, neither by the host packing nor by a kernel: what they
+ * hold, and whether their pages can be read at all, cannot matter.
+ * STAGING: consecutive jobs form a staging group of at most LCPC_POS_GROUP_STAGE_BYTES of image
+ * (rows_written rounded up to even, times enc, times 8: the packed columns and the repaired ones;
+ * LCPC_POS_GROUP_BYTES, the test seam, can only lower it; also bounded as the ingest's groups in jobs,
+ * rows, tiles and tree bytes).  Only the first rows_written elements of the columns that are not listed
+ * cross the bus, with the leaves, the lists and the tables in the same copy; flags, digests and trees come
+ * back in one, the repaired columns (where a job wants them) in a second.  Two page-locked blocks
+ * alternate: the host packs group g + 1 and scatters group g - 1 while g runs.  A group takes at most
+ * LCPC_POS_REPAIR_LAUNCHES_PER_GROUP kernel launches, whatever the number of jobs or of distinct enc, all
+ * inside one profiling region (pos_group_repair).
+ * ROUTING: a job with enc > LCPC_POS_REPAIR_MAX_ENC, or whose image alone exceeds a group, or whose columns
+ * have more than 2^16 1-KiB chunks, ends the group before it and goes through lcpc_pos_repair_columns
+ * inside the same call (its tree by the group's last launch alone), to the same equalities.
+ * Errors, before any device work and before any output byte is written: a NULL jobs, n_jobs == 0,
+ * porenc == NULL with rows_written > 0, rows_written > row_capacity, pre == 0, enc no power of two or
+ * enc <= pre, bad_cols NULL with n_bad > 0, a column index >= enc, a duplicate index, tree_out or root_out
+ * without leaves: LCPC_ERR_INVALID_ARG; enc beyond the field's two-adicity: LCPC_FFT_TOO_BIG; no device:
+ * LCPC_ERR_NO_DEVICE.  Ft63 and BLAKE3 only.  Threading as every entry: a stream of its own per call. */
+#define LCPC_POS_REPAIR_MAX_ENC ((size_t)1024)  /* as LCPC_POS_INGEST_MAX_ENC: 8 rows = 64 KiB of LDS */
+#define LCPC_POS_REPAIR_TILE_ROWS ((size_t)8)   /* rows of a full tile of the row launch */
+#define LCPC_POS_REPAIR_LAUNCHES_PER_GROUP 4    /* locators, rows, chunk chaining values, leaves + tree */
+typedef struct lcpc_pos_repair_job {
+  const uint8_t *porenc;     /* column-major image (lcpc_pos_encode_file's layout); NULL iff rows_written == 0 */
+  size_t pre, enc, rows_written, row_capacity;
+  const uint64_t *bad_cols;  /* the erasure set: n_bad distinct columns < enc; never read from the image */
+  size_t n_bad;
+  const uint8_t *leaves;     /* enc x 32 B digests of the columns as they stand (e.g. the scrub's), or NULL */
+  uint8_t *cols_out;         /* n_bad x rows_written x 8 B, as lcpc_pos_repair_columns, or NULL */
+  uint8_t *digests_out;      /* n_bad x 32 B, or NULL */
+  uint8_t *tree_out;         /* (2 enc - 1) x 32 B: MerkleTree::new(leaves with bad_cols' entries replaced by the
+                                repaired digests); needs leaves; or NULL */
+  uint8_t *root_out;         /* 32 B, needs leaves; or NULL */
+  lcpc_status status;        /* out: LCPC_OK or LCPC_ERR_UNRECOVERABLE, this job's own verdict */
+} lcpc_pos_repair_job;
+lcpc_status lcpc_pos_repair_files_grouped(lcpc_pos_repair_job *jobs, size_t n_jobs);
+/* Host-only, no device (like lcpc_pos_scrub_plan): the work list of the row launch of each staging group
+ * the entry above makes for jobs of these row counts, dims and erasure counts, a pure function of its
+ * arguments (and of LCPC_POS_GROUP_BYTES), under lcpc_pos_scrub_plan's rules.  A job with
+ * n_bad > enc - pre or with zero rows has no record; `launch` counts the staging groups that launch.
+ * Outputs and errors as lcpc_pos_scrub_plan. */
+lcpc_status lcpc_pos_repair_plan(const size_t *rows_written, const size_t *pre, const size_t *enc,
+                                 const size_t *n_bad, size_t n_jobs, lcpc_pos_ingest_tile *tiles,
+                                 size_t cap, size_t *n_tiles, size_t *n_launches);
 /* The streaming writer itself: EncodedFileWriter::new (:40-105; porenc = the preallocated
  * image of row_capacity rows, batch_rows as above), push_bytes (:233-262), and
  * finalize_to_column_digest / _to_commit / _to_merkle_tree (:452-501): digests = the enc column

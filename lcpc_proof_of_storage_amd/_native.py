@@ -90,6 +90,13 @@ class PosScrubJob(C.Structure):
                 ("tree_consistent", C.c_uint8), ("root_ok", C.c_uint8)]
 
 
+class PosRepairJob(C.Structure):
+    """lcpc_pos_repair_job (include/lcpc_mi.h)"""
+    _fields_ = [("porenc", vp), ("pre", C.c_size_t), ("enc", C.c_size_t), ("rows_written", C.c_size_t),
+                ("row_capacity", C.c_size_t), ("bad_cols", vp), ("n_bad", C.c_size_t), ("leaves", vp),
+                ("cols_out", vp), ("digests_out", vp), ("tree_out", vp), ("root_out", vp), ("status", C.c_int32)]
+
+
 class CommOps(C.Structure):
     _fields_ = [("user", vp), ("all_gather", ALL_GATHER_FN), ("all_to_all_v", ALL_TO_ALL_V_FN),
                 ("broadcast", BROADCAST_FN)]
@@ -241,6 +248,8 @@ SIGNATURES = {
     "lcpc_pos_ingest_plan": (i32, [szp, szp, szp, sz, C.POINTER(PosIngestTile), sz, szp, szp]),
     "lcpc_pos_scrub_files_grouped": (i32, [C.POINTER(PosScrubJob), sz]),
     "lcpc_pos_scrub_plan": (i32, [szp, szp, szp, sz, C.POINTER(PosIngestTile), sz, szp, szp]),
+    "lcpc_pos_repair_files_grouped": (i32, [C.POINTER(PosRepairJob), sz]),
+    "lcpc_pos_repair_plan": (i32, [szp, szp, szp, szp, sz, C.POINTER(PosIngestTile), sz, szp, szp]),
     "lcpc_pos_update_rows": (i32, [sz, sz, sz, sz, szp, szp, szp, szp]),
     "lcpc_pos_update_evaluation": (i32, [vp, vp, sz, vp, vp, sz, u64p, u64p, sz, u64p, sz,
                                          u64p, u64p, u8p, u8p, u64p, u64p, u8p, u8p, u64p]),

@@ -38,29 +38,6 @@ __device__ __forceinline__ size_t rs_point_index(size_t c, int log_n) {
 #endif
 }
 
-// a^(p - 2)
-template <class F>
-__device__ __forceinline__ Fe<F> fe_inv_fermat(const Fe<F> &a) {
-  Fe<F> acc = fe_one<F>();
-  uint32_t borrow = 2;
-  uint32_t e[F::N];
-#pragma unroll
-  for (int i = 0; i < F::N; i++) {
-    const uint32_t pi = F::P[i];
-    e[i] = pi - borrow;
-    borrow = pi < borrow ? 1u : 0u;
-  }
-#pragma unroll
-  for (int i = F::N - 1; i >= 0; i--) {
-    const uint32_t w = e[i];
-    for (int b = 31; b >= 0; b--) {
-      acc = fe_sqr<F>(acc);
-      if ((w >> b) & 1u) acc = fe_mul<F>(acc, a);
-    }
-  }
-  return acc;
-}
-
 __global__ __launch_bounds__(256) void k_slot_set(const uint32_t *__restrict__ erased, size_t n_erased,
                                                   int32_t *__restrict__ slot) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -634,6 +634,29 @@ __device__ __forceinline__ Fe<F> fe_pow(Fe<F> a, uint64_t e) {
   return acc;
 }
 
+// a^(p - 2): the inverse of a non-zero a (Fermat), both in Montgomery form
+template <class F>
+__device__ __forceinline__ Fe<F> fe_inv_fermat(const Fe<F>& a) {
+  Fe<F> acc = fe_one<F>();
+  uint32_t borrow = 2;
+  uint32_t e[F::N];
+#pragma unroll
+  for (int i = 0; i < F::N; i++) {
+    const uint32_t pi = F::P[i];
+    e[i] = pi - borrow;
+    borrow = pi < borrow ? 1u : 0u;
+  }
+#pragma unroll
+  for (int i = F::N - 1; i >= 0; i--) {
+    const uint32_t w = e[i];
+    for (int b = 31; b >= 0; b--) {
+      acc = fe_sqr<F>(acc);
+      if ((w >> b) & 1u) acc = fe_mul<F>(acc, a);
+    }
+  }
+  return acc;
+}
+
 // canonical (non-Montgomery) value of a: a * R^-1 mod p (Montgomery reduction of a
 // single-width value; a < p so the result is < p without a final subtraction)
 template <class F>

@@ -195,4 +195,39 @@ hipError_t pos_group_scrub(const uint8_t *arena, const PosScrubJob *jobs, size_t
                            size_t n_waves, size_t max_chunks, const uint32_t *tw, uint32_t *cvs, uint8_t *cflags,
                            uint8_t *flags, uint8_t *status, uint8_t *dirty, uint8_t *digests, hipStream_t s);
 
+// ---- pos_repair_group.hip: the listed columns of many stored files recomputed from the others, hashed
+// and folded into their trees in one pass.  The host builds the tables of a staging group
+// (pos_repair_group_host.cpp); tiles, workgroups and waves are the ingest's records, a wave's columns
+// being columns of the job's erasure list.
+//   job    the first n_rows rows of the enc - n_bad columns that are not listed, packed in column order
+//          [enc - n_bad][rows_pad] canonical 8-byte words at byte offset img of the group's arena (a
+//          multiple of 16; rows_pad = n_rows rounded up to even); cmap (enc int32 at byte offset cmap):
+//          k >= 0 for the k-th listed column, -1 - q for packed column q; the list itself (n_bad uint32)
+//          at byte offset bad; with has_tree the enc digests of the columns as they stand at byte offset
+//          leaves, and for a tree_only job (one routed to the single-file entry, whose tree alone is
+//          built here: no rows, no chunks) its n_bad repaired digests at byte offset dig_in.  lambda
+//          (enc elements from element lam0 of tabs, the listed positions unused) and the inverse table
+//          (n_bad elements from element dinv0) are the locator launch's; the repaired columns are
+//          [n_bad][rows_pad] canonical words at byte offset rep of the repaired arena; the chaining value
+//          of (chunk, listed column k) is slot cv0 + chunk * n_bad + k of cvs; the repaired digests are
+//          [dig0, dig0 + n_bad) of digests, the row flags [row0, row0 + n_rows) of flags and the tree
+//          the 2 enc - 1 digests from digest tree0 of trees.
+struct PosRepairJob {
+  uint64_t img, cmap, bad, leaves, dig_in, lam0, dinv0, rep, cv0, dig0, row0, tree0;
+  uint32_t pre, log_enc, n_rows, rows_pad, n_chunks, n_bad, has_tree, tree_only;
+};
+constexpr uint8_t POS_REPAIR_ROW_DEGREE = 1;    // flags[row]: a coefficient at or past pre + n_bad is not zero
+constexpr uint8_t POS_REPAIR_ROW_NONCANON = 2;  // flags[row]: a word of a column that is not listed is not < p
+// The launches of a staging group, at most four, in one profiling region (pos_group_repair):
+// k_group_repair_locators and k_group_repair_trees with a workgroup per job, k_group_repair_rows over
+// n_wgs workgroups with lds_bytes of LDS each (none when no job has a row), k_group_repair_chunks over
+// n_waves waves (4 per workgroup; none when nothing is listed).  With tree_only_group only the last one
+// runs.  tw: pos_ingest_twiddles.  max_chunks as pos_group_ingest; n_wgs, n_waves / 4 and n_jobs stay
+// below 2^24.
+hipError_t pos_group_repair(const uint8_t *arena, const PosRepairJob *jobs, size_t n_jobs, const PosIngestTile *tiles,
+                            const PosIngestWg *wgs, size_t n_wgs, size_t lds_bytes, const PosIngestWave *waves,
+                            size_t n_waves, size_t max_chunks, bool tree_only_group, const uint32_t *tw, uint32_t *tabs,
+                            uint8_t *rep, uint32_t *cvs, uint8_t *flags, uint8_t *digests, uint8_t *trees,
+                            hipStream_t s);
+
 }  // namespace lcpc

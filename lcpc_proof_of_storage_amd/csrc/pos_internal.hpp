@@ -1,5 +1,5 @@
 // pos_internal.hpp -- what the proof-of-storage host units share (lcpc_host.cpp, pos_files_host.cpp,
-// pos_repair_host.cpp, pos_group_host.cpp, pos_verify_group_host.cpp, pos_ingest_host.cpp, pos_scrub_host.cpp): constants, page-locked staging, argument checks and the device-side steps
+// pos_repair_host.cpp, pos_group_host.cpp, pos_verify_group_host.cpp, pos_ingest_host.cpp, pos_scrub_host.cpp, pos_repair_group_host.cpp): constants, page-locked staging, argument checks and the device-side steps
 // that more than one entry point runs.  The image's host side is pos_image.hpp.  Stateless, inline.
 #pragma once
 #include "host_internal.hpp"

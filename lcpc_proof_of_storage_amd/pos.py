@@ -1485,6 +1485,85 @@ def scrub_files_grouped(images, pres, encs, rows_written, row_capacities, trees=
     return out
 
 
+# ---------------------------------------------------------------- grouped repair of stored files
+REPAIR_MAX_ENC = 1024             # LCPC_POS_REPAIR_MAX_ENC: rows of more points take lcpc_pos_repair_columns
+REPAIR_TILE_ROWS = 8              # LCPC_POS_REPAIR_TILE_ROWS
+REPAIR_LAUNCHES_PER_GROUP = 4     # LCPC_POS_REPAIR_LAUNCHES_PER_GROUP
+
+
+def repair_plan(rows_written, pres, encs, n_bad):
+    """lcpc_pos_repair_plan: (tiles, n_groups) for stored files of rows_written[j] rows at dims pres[j] /
+    encs[j] with n_bad[j] listed columns.  tiles is a structured array with the fields job, row_lo, row_hi,
+    launch and workgroup: the work list of the row launch of every staging group repair_files_grouped makes
+    (launch = the group), a job routed to lcpc_pos_repair_columns as one record with launch ==
+    GROUP_SINGLE; a job with more listed columns than encs[j] - pres[j], or with no rows, has no record.
+    Host only, a pure function."""
+    rw, pr, en, nb = _sizes(rows_written), _sizes(pres), _sizes(encs), _sizes(n_bad)
+    if not (rw.size == pr.size == en.size == nb.size):
+        raise ValueError("rows_written, pres, encs and n_bad must have one entry per job")
+    n, launches = C.c_size_t(), C.c_size_t()
+    L = N.load()
+    args = (rw.ctypes.data_as(N.szp), pr.ctypes.data_as(N.szp), en.ctypes.data_as(N.szp), nb.ctypes.data_as(N.szp),
+            rw.size)
+    _raise(L.lcpc_pos_repair_plan(*args, None, 0, C.byref(n), C.byref(launches)))
+    dt = np.dtype([("job", "<u8"), ("row_lo", "<u8"), ("row_hi", "<u8"), ("launch", "<u4"), ("workgroup", "<u4")])
+    assert dt.itemsize == C.sizeof(N.PosIngestTile)
+    tiles = np.zeros(n.value, dt)
+    _raise(L.lcpc_pos_repair_plan(*args, tiles.ctypes.data_as(C.POINTER(N.PosIngestTile)), tiles.size, C.byref(n),
+                                  C.byref(launches)))
+    return tiles, launches.value
+
+
+def repair_files_grouped(images, pres, encs, rows_written, row_capacities, bad_cols, leaves=None,
+                         want_cols: bool = True, want_tree: bool = False) -> list:
+    """lcpc_pos_repair_files_grouped: the listed columns of many stored files recomputed in one call.  Job j
+    is the column-major `.porenc` image images[j] (a numpy array or an mmap of row_capacities[j] x encs[j]
+    elements, None with no rows) of which rows_written[j] rows count, bad_cols[j] its erasure set (distinct
+    columns, never read from the image) and leaves[j] the encs[j] digests of its columns as they stand
+    (bytes or a uint8 array, or None).  Returns one dict per job: status (0, or UNRECOVERABLE when the job
+    lists more than enc - pre columns, a row is no codeword on the columns that are not listed, or one of
+    them holds a word that is not < p), cols ((n_bad, rows_written) uint64 with want_cols), digests ((n_bad,
+    32) uint8), tree ((2 enc - 1, 32) uint8: the tree over the leaves with the repaired digests in place)
+    and root (bytes) with want_tree for a job with leaves.  The data of a failed job is None.  Every answer
+    is byte for byte lcpc_pos_repair_columns' per file; the launches are per staging group of files."""
+    n = len(images)
+    pres, encs = [int(p) for p in pres], [int(e) for e in encs]
+    rows, caps = [int(r) for r in rows_written], [int(c) for c in row_capacities]
+    leaves = [None] * n if leaves is None else list(leaves)
+    bad_cols = list(bad_cols)
+    if not (len(pres) == len(encs) == len(rows) == len(caps) == len(bad_cols) == len(leaves) == n):
+        raise ValueError("every argument must have one entry per job")
+    jobs, keep, out = [], [], []
+    for j in range(n):
+        enc = encs[j]
+        img = None if images[j] is None else _byte_view(images[j])
+        if img is not None and img.size < caps[j] * enc * WRITTEN_BYTES_WIDTH:
+            raise ValueError(f"job {j}: the image is smaller than row_capacity x enc elements")
+        bad = np.ascontiguousarray(np.asarray(bad_cols[j], np.uint64).reshape(-1))
+        lv = None if leaves[j] is None else _byte_view(leaves[j])
+        if lv is not None and lv.size != max(enc, 0) * DIGEST_BYTES:
+            raise ValueError(f"job {j}: the leaves are enc 32-byte digests")
+        nb = int(bad.size)
+        cols = np.zeros((nb, rows[j]), np.uint64) if want_cols else None
+        digests = np.zeros((nb, DIGEST_BYTES), np.uint8)
+        tree = np.zeros((2 * enc - 1, DIGEST_BYTES), np.uint8) if want_tree and lv is not None and enc >= 1 else None
+        root = np.zeros(DIGEST_BYTES, np.uint8) if tree is not None else None
+        keep.append((img, bad, lv))
+        jobs.append(N.PosRepairJob(_addr(img), pres[j], enc, rows[j], caps[j], _addr(bad), nb, _addr(lv),
+                                   _addr(cols), _addr(digests), _addr(tree), _addr(root), 0))
+        out.append({"cols": cols, "digests": digests, "tree": tree, "root": root})
+    arr = (N.PosRepairJob * max(n, 1))(*jobs)
+    _raise(N.load().lcpc_pos_repair_files_grouped(arr if n else None, n))
+    del keep
+    for j, o in enumerate(out):
+        o["status"] = int(arr[j].status)
+        if o["status"]:
+            o["cols"] = o["digests"] = o["tree"] = o["root"] = None
+        elif o["root"] is not None:
+            o["root"] = o["root"].tobytes()
+    return out
+
+
 def field_to_montgomery(values, field: int = FT63) -> np.ndarray:
     """lcpc_field_to_montgomery: (v R) mod p per 64-bit word, R = 2^64 (Ft63 only): canonical values,
     as a `.porenc` holds them, to the Montgomery words a commitment opens.  Same shape as `values`."""

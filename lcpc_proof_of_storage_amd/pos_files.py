@@ -1701,7 +1701,13 @@ class FileHandler:
         With more damage the raw file is encoded again, accepted only if its root is the anchor.  A
         sound `.porenc` rewrites a damaged raw file from its decode.  UnrecoverableError if nothing
         verifies; every file is then byte for byte what it was."""
-        report, tree, digests, raw_tree = self._scrub_state(expected_root)
+        return self._apply_repair(expected_root, *self._scrub_state(expected_root))
+
+    def _apply_repair(self, expected_root: Optional[bytes], report: ScrubReport, tree: MerkleTree,
+                      digests: np.ndarray, raw_tree: Optional[MerkleTree], repaired=None) -> ScrubReport:
+        """The trust rules of _repair_by_tree over a scrub state (_scrub_state's, or the grouped scrub's
+        of repair_files).  repaired: (columns, digests, tree digests) of report.bad_columns from a grouped
+        repair over `digests` as leaves; None: they are recomputed here, by this file's own call."""
         w, pre = self.encoded_size, self.pre_encoded_size
         if expected_root is not None:
             anchor = bytes(expected_root)
@@ -1714,15 +1720,19 @@ class FileHandler:
         new_tree, cols = None, None
         if len(bad) <= w - pre:
             try:
+                rebuilt = None
                 if bad:
-                    with open(self.encoded_file_handle, "rb") as f:
-                        cols, rdig = self._reader(f).repair_columns(bad)
+                    if repaired is not None:
+                        cols, rdig, rebuilt = repaired
+                    else:
+                        with open(self.encoded_file_handle, "rb") as f:
+                            cols, rdig = self._reader(f).repair_columns(bad)
                     digests = digests.copy()
                     digests[bad] = rdig
                 # a repaired column whose digest is not its leaf is a damaged leaf (or damage this
                 # cannot mend): either way only a tree over the digests that folds to the anchor counts
                 cand = tree if (report.tree_consistent and np.array_equal(digests, tree.digests[:w])) \
-                    else MerkleTree.new(digests)
+                    else MerkleTree(rebuilt) if rebuilt is not None else MerkleTree.new(digests)
                 if cand.root() == anchor:
                     new_tree = cand
             except UnrecoverableError:
@@ -1794,14 +1804,18 @@ def _close_map(mm) -> None:
         pass
 
 
-def _scrub_files_batch(handlers, roots, locate: bool) -> List[ScrubReport]:
+def _scrub_files_batch(handlers, roots, locate: bool, states: Optional[list] = None) -> List[ScrubReport]:
+    """states (repair_files): a list that gets, per file, what FileHandler._scrub_state returns beside the
+    report -- (stored tree, column digests, raw file's tree or None) -- or None for a file without a usable
+    tree, which is then no error here either."""
     from .pos import encode_files_grouped_into, scrub_files_grouped
     trees: List[Optional[MerkleTree]] = []
     for h in handlers:
         try:
             trees.append(h._stored_tree())
         except (UnrecoverableError, OSError):
-            if not locate:   # scrub() raises; scrub(locate=True) reports a file without a usable tree
+            # scrub() raises; scrub(locate=True) reports a file without a usable tree; repair_files asks its handler
+            if not locate and states is None:
                 raise
             trees.append(None)
     files, maps, images = [], [], []
@@ -1819,7 +1833,7 @@ def _scrub_files_batch(handlers, roots, locate: bool) -> List[ScrubReport]:
             images, [h.pre_encoded_size for h in handlers], [h.encoded_size for h in handlers],
             [h.rows_written for h in handlers], [h.row_capacity for h in handlers],
             [None if t is None else t.digests for t in trees],
-            [None if t is None else r for t, r in zip(trees, roots)])
+            [None if t is None else r for t, r in zip(trees, roots)], want_digests=states is not None)
     finally:
         del images
         for mm in maps:
@@ -1877,6 +1891,8 @@ def _scrub_files_batch(handlers, roots, locate: bool) -> List[ScrubReport]:
             else:
                 h._locate_report(report)
         out.append(report)
+        if states is not None:
+            states.append(None if tree is None else (tree, r["digests"], None if raw is None else MerkleTree(raw)))
     return out
 
 
@@ -1897,6 +1913,81 @@ def scrub_files(handlers, expected_roots=None, locate: bool = False) -> List[Scr
     out: List[ScrubReport] = []
     for lo in range(0, len(handlers), _SCRUB_FILES_BATCH):
         out += _scrub_files_batch(handlers[lo:lo + _SCRUB_FILES_BATCH], roots[lo:lo + _SCRUB_FILES_BATCH], locate)
+    return out
+
+
+# -- grouped repair
+def _repair_files_batch(handlers, roots, locate: bool) -> list:
+    from .pos import repair_files_grouped
+    states: list = []
+    reports = _scrub_files_batch(handlers, roots, False, states)
+    # one grouped repair for the files the tree can mend: an anchor, and 1 .. enc - pre bad columns
+    who = []
+    for i, (h, root, report, st) in enumerate(zip(handlers, roots, reports, states)):
+        if st is not None and (root is not None or report.tree_consistent) and \
+                1 <= len(report.bad_columns) <= h.encoded_size - h.pre_encoded_size:
+            who.append(i)
+    repaired = {}
+    files, maps, images = [], [], []
+    try:
+        for i in who:
+            h = handlers[i]
+            need = h.row_capacity * h.encoded_size * WRITTEN_BYTES_WIDTH
+            f = open(h.encoded_file_handle, "rb")
+            files.append(f)
+            mm = mmap.mmap(f.fileno(), need, access=mmap.ACCESS_READ) if need else None
+            maps.append(mm)
+            images.append(np.frombuffer(mm, np.uint8) if need else None)
+        if who:
+            res = repair_files_grouped(
+                images, [handlers[i].pre_encoded_size for i in who], [handlers[i].encoded_size for i in who],
+                [handlers[i].rows_written for i in who], [handlers[i].row_capacity for i in who],
+                [reports[i].bad_columns for i in who], [states[i][1] for i in who], want_cols=True, want_tree=True)
+            for i, o in zip(who, res):
+                if o["status"] == 0:     # (a file the grouped pass could not mend takes its own handler's path)
+                    repaired[i] = (o["cols"], o["digests"], o["tree"])
+    finally:
+        del images
+        for mm in maps:
+            if mm is not None:
+                _close_map(mm)
+        for f in files:
+            f.close()
+    out = []
+    for i, (h, root, report, st) in enumerate(zip(handlers, roots, reports, states)):
+        try:
+            if st is None:       # no usable tree file: the handler's own path says what that means
+                out.append(h.repair(expected_root=root, locate=locate))
+                continue
+            try:
+                out.append(h._apply_repair(root, report, *st, repaired=repaired.get(i)))
+            except UnrecoverableError:
+                if not locate:
+                    raise
+                out.append(h._repair_located(root))
+        except (UnrecoverableError, OSError) as e:
+            out.append(e)
+    return out
+
+
+def repair_files(handlers, expected_roots=None, locate: bool = False) -> list:
+    """FileHandler.repair for many stored files in grouped passes: entry i is the ScrubReport that
+    handlers[i].repair(expected_root=expected_roots[i], locate=locate) returns, field by field, or the
+    exception (UnrecoverableError, or the OSError of a missing file) that call would raise; the other
+    files are still repaired, and afterwards every file on disk is byte for byte what the per-file loop
+    leaves.  The scrub state of a batch comes from the grouped scrub (scrub_files' passes); every file
+    with an anchor and between 1 and enc - pre bad columns goes through one
+    lcpc_pos_repair_files_grouped call per batch, with the scrub's digests as leaves and the tree
+    wanted; FileHandler._apply_repair then applies _repair_by_tree's trust rules and writes.  A file
+    the grouped repair cannot mend (too many columns, no anchor, an unrecoverable verdict, no usable tree
+    file, the locate=True fallback) takes its own handler's calls from there."""
+    handlers = list(handlers)
+    roots = [None] * len(handlers) if expected_roots is None else list(expected_roots)
+    if len(roots) != len(handlers):
+        raise ValueError("expected_roots must have one entry per handler")
+    out: list = []
+    for lo in range(0, len(handlers), _SCRUB_FILES_BATCH):
+        out += _repair_files_batch(handlers[lo:lo + _SCRUB_FILES_BATCH], roots[lo:lo + _SCRUB_FILES_BATCH], locate)
     return out
 
 
