@@ -1414,6 +1414,16 @@ lcpc_status lcpc_pos_locate_porenc(const uint8_t *porenc, size_t pre, size_t enc
 lcpc_status lcpc_selftest_pool_ordering(int rounds, uint32_t spin_us, uint64_t *violations,
                                         uint64_t *control_violations, uint64_t *reused);
 
+/* LCPC_POOL_POISON=<0..255> (the environment, read once per process) fills every device block
+ * of the pool over its whole rounded size, and every page-locked staging block, with that byte
+ * before its owner sees it: a result must not depend on what a block held before.  This call
+ * takes one pool block of `bytes` (> 0) as the library's own code does -- on a stream of the pool
+ * when with_stream != 0, with none otherwise -- copies back its first and last byte and releases
+ * it.  *enabled = 1 when the switch is set (both bytes are then the poison, for a fresh block and
+ * for a recycled one), 0 when it is not (the bytes are whatever the block held: no claim). */
+lcpc_status lcpc_selftest_pool_poison(size_t bytes, int with_stream, int *enabled, uint8_t *first,
+                                      uint8_t *last);
+
 /* The field primitives every kernel is built from (csrc/field.hpp) and the Ft127 matrix-core
  * digit recombination (csrc/collapse_mfma.hpp), one call per GPU thread: raw words in, raw words
  * out, NO range check on the values -- the caller owns the domain, which is the point: a test

@@ -12,7 +12,7 @@ from .lcpc2d import (  # noqa: F401
     LcBatchEvalProof, BATCH_MAX_TENSORS, collapse_columns_many, collapse_many_chunk,
     collapse_columns, merkle_tree, hash_columns, verify_column_path, verify_column_value,
     n_degree_tests, log2, limbs, num_bits, set_device, device_count, field_random,
-    prof_enable, prof_reset, prof_stats, selftest_pool_ordering,
+    prof_enable, prof_reset, prof_stats, selftest_pool_ordering, selftest_pool_poison,
     SELFTEST_OPS, selftest_fe_dot_kmax, selftest_field_op, selftest_recombine, selftest_recombine63, selftest_twiddle_words, selftest_ntt_rows,
     selftest_spmm, selftest_reed_solomon,
 )

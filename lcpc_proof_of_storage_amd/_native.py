@@ -341,6 +341,7 @@ SIGNATURES = {
     "lcpc_prof_get": (i32, [C.c_char_p, C.POINTER(C.c_double), u64p]),
     "lcpc_prof_names": (sz, [C.c_char_p, sz]),
     "lcpc_selftest_pool_ordering": (i32, [i32, C.c_uint32, u64p, u64p, u64p]),
+    "lcpc_selftest_pool_poison": (i32, [sz, i32, C.POINTER(C.c_int), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     "lcpc_selftest_fe_dot_kmax": (i32, [i32]),
     "lcpc_selftest_field_op": (i32, [i32, i32, i32, u64p, u64p, u64p, sz]),
     "lcpc_selftest_recombine": (i32, [C.POINTER(C.c_int32), u64p, sz]),

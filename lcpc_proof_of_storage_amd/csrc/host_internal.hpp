@@ -180,7 +180,21 @@ struct Device {
   // (device-side waits), on the host otherwise
   hipError_t alloc(void **p, size_t bytes, hipStream_t s = nullptr) {
     bytes = round_bytes(bytes);
-    if ((*p = blocks.take(bytes, s))) return hipSuccess;
+    if ((*p = blocks.take(bytes, s))) return pool_poison() < 0 ? hipSuccess : poison(*p, bytes, s);
+    const hipError_t e = alloc_fresh(p, bytes);
+    return e != hipSuccess || pool_poison() < 0 ? e : poison(*p, bytes, s);
+  }
+  // LCPC_POOL_POISON (kernels.hpp): the whole rounded block, cached or fresh, before its owner
+  // sees it.  take() has ordered s behind the block's fence, so the fill is queued there; without
+  // a stream it has completed on return.
+  hipError_t poison(void *p, size_t bytes, hipStream_t s) {
+    if (!s) {
+      const hipError_t e = hipSetDevice(id);  // the null stream of THIS device
+      if (e != hipSuccess) return e;
+    }
+    return pool_poison_fill(p, bytes, s);
+  }
+  hipError_t alloc_fresh(void **p, size_t bytes) {
     prof::HostScope hs("rt_hipMalloc");
     // a pool thread's current device is whatever it last set (GPU 0 for a fresh thread): the
     // block must come from THIS device, so make it current before allocating
@@ -222,7 +236,9 @@ struct Device {
       auto it = pinned_free.lower_bound(want);
       if (it != pinned_free.end() && it->first <= 2 * want) {
         void *p = it->second;
+        const size_t have = it->first;
         pinned_free.erase(it);
+        if (pool_poison() >= 0) std::memset(p, pool_poison(), have);  // (nothing is queued on a free block)
         return p;
       }
     }
@@ -230,6 +246,7 @@ struct Device {
     void *p = nullptr;
     (void)hipSetDevice(id);
     if (hipHostMalloc(&p, want, hipHostMallocPortable) != hipSuccess) return nullptr;
+    if (pool_poison() >= 0) std::memset(p, pool_poison(), want);
     std::lock_guard<std::mutex> lk(mu);
     pinned_sizes[p] = want;
     return p;
@@ -434,6 +451,9 @@ struct PinnedSlot {
       if (hipHostMalloc(&p, want, hipHostMallocPortable) != hipSuccess) return nullptr;
       cap = want;
     }
+    // LCPC_POOL_POISON: every get() in the library is an acquisition (the caller fills the n bytes
+    // or has the device write them before anyone reads), so the n bytes are filled here
+    if (pool_poison() >= 0 && p) std::memset(p, pool_poison(), n);
     return p;
   }
 };

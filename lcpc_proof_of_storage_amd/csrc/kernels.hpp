@@ -4,10 +4,45 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
 
 #include "../../include/lcpc_fft_convention.h"
 
 namespace lcpc {
+
+// LCPC_POOL_POISON=<0..255> (read once per process; -1 when unset or out of range): every device
+// block and staging block the library hands to itself is filled with that byte first, so a word
+// that a kernel or a memset was meant to write and did not shows in the results whatever the
+// block held before (tests/test_gpu_pool_poison.py).  Off by default: one flag test per block.
+inline int pool_poison() {
+  static const int v = [] {
+    const char *e = std::getenv("LCPC_POOL_POISON");
+    if (!e || !*e) return -1;
+    char *end = nullptr;
+    const long x = std::strtol(e, &end, 10);
+    return (*end || x < 0 || x > 255) ? -1 : (int)x;
+  }();
+  return v;
+}
+// The fill itself.  On stream s when given; without one the fill has completed on return
+// (hipMemset on device memory may return before it has run, so the null stream is drained).
+inline hipError_t pool_poison_fill(void *p, size_t bytes, hipStream_t s) {
+  const int v = pool_poison();
+  if (v < 0 || !p || !bytes) return hipSuccess;
+  if (s) return hipMemsetAsync(p, v, bytes, s);
+  const hipError_t e = hipMemsetAsync(p, v, bytes, nullptr);
+  return e == hipSuccess ? hipStreamSynchronize(nullptr) : e;
+}
+// hipMalloc for the blocks that do not come from a Device's pool (plan tables, the sharded
+// engine's temporaries): the same fill, completed on return.
+inline hipError_t device_malloc(void **p, size_t bytes) {
+  const hipError_t e = hipMalloc(p, bytes);
+  return e == hipSuccess ? pool_poison_fill(*p, bytes, nullptr) : e;
+}
+template <class T>
+inline hipError_t device_malloc(T **p, size_t bytes) {
+  return device_malloc(reinterpret_cast<void **>(p), bytes);
+}
 
 // Bytes per element of field `fid` (8, 16, 24, 32) and 32-bit words per element.
 int field_words(int fid);

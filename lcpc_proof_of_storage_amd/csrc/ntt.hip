@@ -72,7 +72,7 @@ hipError_t ntt_plan_init(NttPlan &p, int fid, int log_n, bool inverse, hipStream
   p.l1 = fid == 0 && log_n == 15 ? 8 : log_n / 2;
   p.l2 = log_n - p.l1;
   const size_t n = (size_t)1 << log_n;
-  hipError_t e = hipMalloc(&p.d_tw, n * field_bytes(fid));
+  hipError_t e = device_malloc(&p.d_tw, n * field_bytes(fid));
   if (e != hipSuccess) return e;
   switch (fid) {
     case 0: e = ntt_tw_table_ft63(p.d_tw, log_n, inv_root, s); break;
@@ -83,7 +83,7 @@ hipError_t ntt_plan_init(NttPlan &p, int fid, int log_n, bool inverse, hipStream
   }
   if (e != hipSuccess) return e;
   if (log_n > 12) {  // the pass-A kernels' [t][c] inter-pass twiddles
-    if ((e = hipMalloc(&p.d_tw2, n * field_bytes(fid))) != hipSuccess) return e;
+    if ((e = device_malloc(&p.d_tw2, n * field_bytes(fid))) != hipSuccess) return e;
     if ((e = ntt_tw2_table(fid, p.d_tw, log_n, p.l1, p.d_tw2, s)) != hipSuccess) return e;
   }
   if (fid == 1 && log_n > 12 && ntt_tw4_enabled()) {
@@ -91,18 +91,18 @@ hipError_t ntt_plan_init(NttPlan &p, int fid, int log_n, bool inverse, hipStream
     // tw[e << l2], pass B's tw[e << l1]
     const size_t na = ntt_tw4_entries(p.l1), nb = ntt_tw4_entries(p.l2);
     if (na + nb) {
-      if ((e = hipMalloc(&p.d_tw4, (na + nb) * 4 * field_bytes(fid))) != hipSuccess) return e;
+      if ((e = device_malloc(&p.d_tw4, (na + nb) * 4 * field_bytes(fid))) != hipSuccess) return e;
       if ((e = ntt_tw4_table(fid, p.d_tw, (size_t)1 << p.l2, na, p.d_tw4, s)) != hipSuccess) return e;
       if ((e = ntt_tw4_table(fid, p.d_tw, (size_t)1 << p.l1, nb, p.d_tw4 + na * 16, s)) != hipSuccess) return e;
     }
   }
   if (!inverse) {
     // canonical words of w^e = Montgomery words of w^e R^-1 (canon_out encodes)
-    e = hipMalloc(&p.d_tw_canon, n * field_bytes(fid));
+    e = device_malloc(&p.d_tw_canon, n * field_bytes(fid));
     if (e != hipSuccess) return e;
     if ((e = convert(fid, p.d_tw, p.d_tw_canon, n, false, s)) != hipSuccess) return e;
     if (log_n > 12) {
-      if ((e = hipMalloc(&p.d_tw2_canon, n * field_bytes(fid))) != hipSuccess) return e;
+      if ((e = device_malloc(&p.d_tw2_canon, n * field_bytes(fid))) != hipSuccess) return e;
       if ((e = ntt_tw2_table(fid, p.d_tw_canon, log_n, p.l1, p.d_tw2_canon, s)) != hipSuccess) return e;
     }
   }

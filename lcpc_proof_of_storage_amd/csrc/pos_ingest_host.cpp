@@ -129,7 +129,7 @@ lcpc_status ingest_twiddles(Device *dev, hipStream_t s, const uint32_t **out) {
   auto it = tables.find(dev->id);
   if (it == tables.end()) {
     uint32_t *tw = nullptr;
-    HIP_TRY(hipMalloc(&tw, ((size_t)1 << POS_INGEST_MAX_LOG_ENC) * POS_WB));
+    HIP_TRY(device_malloc(&tw, ((size_t)1 << POS_INGEST_MAX_LOG_ENC) * POS_WB));
     hipError_t e = pos_ingest_twiddles(tw, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) {

@@ -395,7 +395,7 @@ static hipError_t plan_upload_matrices(SdigPlan &plan, int fid, const std::vecto
   size_t total = 0;
   for (const auto &h : pre) total += bytes_of(h);
   for (const auto &h : post) total += bytes_of(h);
-  hipError_t e = hipMalloc(&plan.d_buf, total ? total : 256);
+  hipError_t e = device_malloc(&plan.d_buf, total ? total : 256);
   if (e != hipSuccess) return e;
   plan.fid = fid;
   uint8_t *cur = (uint8_t *)plan.d_buf;
@@ -486,7 +486,7 @@ hipError_t sdig_plan_mfma(SdigPlan &plan, const std::vector<CsrHost> &pre, const
       }
     total += al((h.rows + 1) * 4) + al(4 * groups * 4) + al(4 * groups * 16);
   }
-  hipError_t e = hipMalloc(&plan.d_mfma, total ? total : 256);
+  hipError_t e = device_malloc(&plan.d_mfma, total ? total : 256);
   if (e != hipSuccess) return e;
   uint8_t *cur = (uint8_t *)plan.d_mfma;
   for (size_t m = 0; m < hs.size() && e == hipSuccess; m++) {

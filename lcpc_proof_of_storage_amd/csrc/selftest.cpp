@@ -235,3 +235,34 @@ extern "C" lcpc_status lcpc_selftest_reed_solomon(lcpc_field f, const uint64_t *
   HIP_TRY(hipStreamSynchronize(lease.s));
   return LCPC_OK;
 }
+
+// LCPC_POOL_POISON as a caller of Device::alloc sees it: one block of `bytes` (on a leased stream,
+// or with none: the fill must then have completed when alloc returns, so the bytes are read back
+// by plain copies that wait for nothing but themselves), its first and last byte, and the block
+// back to the pool.  No claim when the switch is off: *enabled = 0, *first and *last are what the
+// block happened to hold.
+extern "C" lcpc_status lcpc_selftest_pool_poison(size_t bytes, int with_stream, int *enabled, uint8_t *first,
+                                                 uint8_t *last) {
+  if (!bytes || !enabled || !first || !last) return fail(LCPC_ERR_INVALID_ARG, "bytes / outputs");
+  lcpc_status st;
+  Device *dev = current_device(&st);
+  if (!dev) return st;
+  *enabled = pool_poison() >= 0 ? 1 : 0;
+  Lease lease(dev);
+  if (!lease.s) return fail(LCPC_ERR_DEVICE, "no HIP stream");
+  const hipStream_t s = with_stream ? lease.s : nullptr;
+  const size_t rb = Device::round_bytes(bytes);
+  void *p = nullptr;
+  HIP_TRY(dev->alloc(&p, bytes, s));
+  // (on a second stream when the block was taken with none: nothing orders that stream behind
+  // the fill but the fill's own completion)
+  hipError_t e = hipMemcpyAsync(first, p, 1, hipMemcpyDeviceToHost, lease.s);
+  if (e == hipSuccess) e = hipMemcpyAsync(last, (const uint8_t *)p + rb - 1, 1, hipMemcpyDeviceToHost, lease.s);
+  // the block goes back holding the poison's complement: a later call that gets it recycled sees
+  // the poison only if it was filled again
+  if (e == hipSuccess && *enabled) e = hipMemsetAsync(p, ~pool_poison() & 0xff, rb, lease.s);
+  if (e == hipSuccess) e = hipStreamSynchronize(lease.s);
+  dev->release(p);  // every use has completed (or the stream is broken)
+  HIP_TRY(e);
+  return LCPC_OK;
+}

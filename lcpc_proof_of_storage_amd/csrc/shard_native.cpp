@@ -730,9 +730,9 @@ void debug_commit(lcpc_sharded_commit *c) {
   hipStream_t ds = nullptr;
   (void)hipStreamCreateWithFlags(&ds, hipStreamNonBlocking);
   void *tc = nullptr, *tk = nullptr, *tv = nullptr;
-  (void)hipMalloc(&tc, c->nr * c->nc * wb + 16);
-  (void)hipMalloc(&tk, c->nr * c->np * wb + 16);
-  (void)hipMalloc(&tv, cvb + 16);
+  (void)device_malloc(&tc, c->nr * c->nc * wb + 16);
+  (void)device_malloc(&tk, c->nr * c->np * wb + 16);
+  (void)device_malloc(&tv, cvb + 16);
   if (c->nr)
     (void)ntt_rows(c->e->plan, (const uint32_t *)c->d_rows, c->np, c->np, (uint32_t *)tc, c->nc, c->nr, ds,
                    (uint32_t *)tk, c->np, true);

@@ -154,6 +154,16 @@ def selftest_pool_ordering(rounds: int = 8, spin_us: int = 300) -> dict:
     return {"violations": v.value, "control_violations": cv.value, "reused": r.value}
 
 
+def selftest_pool_poison(n_bytes: int, with_stream: bool = True) -> dict:
+    """One block of the device pool as the library takes it (lcpc_selftest_pool_poison):
+    {"enabled": LCPC_POOL_POISON is set in this process, "first", "last": the block's first and
+    last byte, the poison when enabled}."""
+    en, first, last = C.c_int(), C.c_uint8(), C.c_uint8()
+    _raise(N.load().lcpc_selftest_pool_poison(n_bytes, 1 if with_stream else 0, C.byref(en), C.byref(first),
+                                              C.byref(last)))
+    return {"enabled": bool(en.value), "first": first.value, "last": last.value}
+
+
 # lcpc_selftest_op (include/lcpc_mi.h)
 SELFTEST_OPS = {name: i for i, name in enumerate([
     "add", "sub", "add_2p", "sub_2p", "reduce_2p", "sub_lazy", "mul_sub_lazy", "mul", "mul_cios", "sqr",
