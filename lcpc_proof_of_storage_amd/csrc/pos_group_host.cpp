@@ -21,12 +21,7 @@ constexpr size_t GROUP_WANT_THREADS = (size_t)1 << 18;  // left_mul_split's
 constexpr size_t GROUP_MAX_JOBS = (size_t)1 << 16, GROUP_MAX_OUT_WORDS = (size_t)1 << 20,
                  GROUP_MAX_ROWS = (size_t)1 << 20, GROUP_MAX_TILES = (size_t)1 << 17;
 
-inline size_t ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
-
 size_t group_bytes() { return pos_group_bytes(); }
-
-inline size_t job_rows(size_t n_bytes, size_t pre) { return ceil_div(ceil_div(n_bytes, POS_DB), pre); }
 
 struct GroupStep {
   bool single = false;
@@ -184,8 +179,8 @@ struct GroupRunner {
     const size_t in_bytes = align_up(o_folds + g.folds.size() * sizeof(PosGroupFold), 256);
     const size_t total = in_bytes + g.out_words * 8;
     if (stg[slot].n < total && !stg[slot].get(dev, total)) return fail(LCPC_ERR_OUT_OF_MEMORY, "pinned host staging");
-    if (arena.n < in_bytes || !arena.p) HIP_TRY(arena.alloc(dev, align_up(in_bytes, (size_t)4 << 20)));
-    if (res.n < g.res_words * 8 || !res.p) HIP_TRY(res.alloc(dev, align_up(g.res_words * 8, (size_t)1 << 20)));
+    if (lcpc_status st = ensure(arena, dev, in_bytes, (size_t)4 << 20)) return st;
+    if (lcpc_status st = ensure(res, dev, g.res_words * 8, (size_t)1 << 20)) return st;
     uint8_t *h = stg[slot].b();
     {
       prof::HostScope hs("pos_group_gather");

@@ -16,6 +16,7 @@
 
 namespace lcpc_host {
 
+constexpr size_t POS_DB = 7;  // F::DATA_BYTE_CAPACITY (data_field.rs:22)
 constexpr size_t POS_WB = 8;  // F::WRITTEN_BYTES_WIDTH = size_of::<F>() (data_field.rs:24)
 
 template <class Fn>

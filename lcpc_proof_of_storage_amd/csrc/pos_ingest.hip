@@ -22,10 +22,8 @@
 //
 // Control flow is uniform over a workgroup in the first kernel (its tiles share enc) and over a wave in
 // the other two (a wave's lanes share a job).  No atomics.
-#include "blake3_dev.hpp"
-#include "field.hpp"
 #include "kernels.hpp"
-#include "pos.hpp"
+#include "pos_rows_dev.hpp"
 #include "prof.hpp"
 
 namespace lcpc {
@@ -51,10 +49,6 @@ __device__ __forceinline__ uint64_t ingest_elem(const uint64_t *__restrict__ img
   uint64_t v = word(w) >> sh;
   if (sh > 8) v |= word(w + 1) << (64 - sh);
   return v & 0x00ffffffffffffffull;
-}
-
-__device__ __forceinline__ int bitrev_bits(int x, int bits) {
-  return (int)(__builtin_bitreverse32((uint32_t)x) >> (32 - bits));
 }
 
 // workgroup b of the launch reads wgs[b]; element idx of its LDS is (tile slot, row of the tile, point)
@@ -86,28 +80,13 @@ __global__ __launch_bounds__(256) void k_group_encode(const uint8_t *__restrict_
     e.v[1] = (uint32_t)(v >> 32);
     buf[idx] = e;
   }
-  // k_ntt_small's stages: gap = 2^lg, w_enc^(enc / (2 gap) j) = tw[j << (MAX_LOG - 1 - lg)]
-  for (int lg = log_enc - 1; lg >= 0; lg--) {
-    __syncthreads();
-    const int gap = 1 << lg;
-    for (int idx = threadIdx.x; idx < total / 2; idx += 256) {
-      const int row = idx >> (log_enc - 1), i = idx & (enc / 2 - 1);
-      const int j = i & (gap - 1);
-      const int base = (row << log_enc) + ((i >> lg) << (lg + 1));
-      const Fe<F> a = buf[base + j], b = buf[base + j + gap];
-      buf[base + j] = fe_add<F>(a, b);
-      buf[base + j + gap] = j ? fe_mul<F>(fe_sub_lazy<F>(a, b), fe_load<F>(tw, (size_t)j << (POS_INGEST_MAX_LOG_ENC - 1 - lg)))
-                              : fe_sub<F>(a, b);
-    }
-  }
-  __syncthreads();
+  rows_forward_stages<F>(buf, log_enc, total, tw);
   for (int idx = threadIdx.x; idx < total; idx += 256) {
     const int r = idx & 7, c = (idx >> 3) & (enc - 1), t = idx >> (3 + log_enc);
     const PosIngestTile tl = tiles[wg.tile0 + t];
     if ((uint32_t)r >= tl.n_rows) continue;
     const PosIngestJob &jb = jobs[tl.job];
-    const int src = LCPC_FFT_OUTPUT_BITREV ? c : bitrev_bits(c, log_enc);
-    const Fe<F> v = fe_from_mont<F>(buf[(t << (3 + log_enc)) + (r << log_enc) + src]);
+    const Fe<F> v = fe_from_mont<F>(buf[row_elem(t, r, row_slot(c, log_enc), log_enc)]);
     uint64_t *col = reinterpret_cast<uint64_t *>(enc_out + jb.enc_off) + (size_t)c * jb.rows_pad;
     col[tl.row_lo + r] = (uint64_t)v.v[0] | ((uint64_t)v.v[1] << 32);
   }
@@ -120,10 +99,10 @@ __global__ __launch_bounds__(256) void k_group_ingest_chunks(const uint8_t *__re
                                                              const PosIngestWave *__restrict__ waves, uint32_t n_waves,
                                                              uint32_t *__restrict__ cvs) {
   __shared__ uint4 stage[4][64][5];
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const uint32_t w = blockIdx.x * 4 + wave;
-  if (w >= n_waves) return;
-  const PosIngestWave wv = waves[w];
+  const uint32_t lane = threadIdx.x & 63;
+  uint32_t wave;
+  PosIngestWave wv;
+  if (!chunk_wave(waves, n_waves, wave, wv)) return;
   const PosIngestJob jb = jobs[wv.job];
   const size_t n_cols = (size_t)1 << jb.log_enc;
   uint32_t cv[8];
@@ -153,18 +132,7 @@ __global__ __launch_bounds__(256) void k_group_ingest_trees(const PosIngestJob *
     leaf_fold_stack<D>(cvs + (jb.cv0 + c) * 8, enc, (int)jb.n_chunks, leaf);
     store8(reinterpret_cast<uint32_t *>(tree + 32 * (size_t)c), leaf);
   }
-  size_t in = 0;
-  for (uint32_t n = enc; n > 1; n >>= 1) {
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < n / 2; i += 256) {
-      uint32_t msg[16], o[8];
-      load8(reinterpret_cast<const uint32_t *>(tree + 32 * (in + 2 * i)), msg);
-      load8(reinterpret_cast<const uint32_t *>(tree + 32 * (in + 2 * i + 1)), msg + 8);
-      hash64(msg, o);
-      store8(reinterpret_cast<uint32_t *>(tree + 32 * (in + n + i)), o);
-    }
-    in += n;
-  }
+  merkle_levels(tree, enc);
 }
 
 }  // namespace

@@ -1,9 +1,12 @@
 // pos_internal.hpp -- what the proof-of-storage host units share (lcpc_host.cpp, pos_files_host.cpp,
 // pos_repair_host.cpp, pos_group_host.cpp, pos_verify_group_host.cpp, pos_ingest_host.cpp, pos_scrub_host.cpp, pos_repair_group_host.cpp): constants, page-locked staging, argument checks and the device-side steps
-// that more than one entry point runs.  The image's host side is pos_image.hpp.  Stateless, inline.
+// that more than one entry point runs.  The image's host side is pos_image.hpp; the arithmetic of an
+// image's rows and chunks and the planning of the grouped ingest, scrub and repair are
+// pos_rowgroup_plan.hpp (host only), their two-slot staging pos_rowgroup_stage.hpp.  Stateless, inline.
 #pragma once
 #include "host_internal.hpp"
 #include "pos_image.hpp"
+#include "pos_rowgroup_plan.hpp"
 
 namespace lcpc_host {
 
@@ -11,7 +14,6 @@ namespace lcpc_host {
 __attribute__((visibility("hidden"))) lcpc_status make_rs_encoding(int fid, size_t n_per_row, size_t n_cols, size_t nco, size_t ndt, lcpc_encoding **out);
 
 constexpr int POS_FID = LCPC_FT63;  // WriteableFt63: Ft63's modulus (writable_ft63.rs:8-12)
-constexpr size_t POS_DB = 7;        // F::DATA_BYTE_CAPACITY (data_field.rs:22)
 
 // Encoded bytes per pipelined batch or column block: 256 MiB.  LCPC_POS_STAGE_BYTES (a test seam,
 // read at every call) can only lower it; zero or an unparsable value is ignored.
@@ -78,6 +80,12 @@ struct Events {
   hipError_t reuse(int k) const { return k >= 2 ? hipEventSynchronize(e[k & 1]) : hipSuccess; }
 };
 
+// a device buffer that only grows, in steps of `granule`: at least `bytes` of it after this
+inline lcpc_status ensure(DBuf &b, Device *dev, size_t bytes, size_t granule) {
+  if (b.n < bytes || !b.p) HIP_TRY(b.alloc(dev, align_up(bytes, granule)));
+  return LCPC_OK;
+}
+
 inline lcpc_status pos_dims_check(size_t pre, size_t enc) {
   // EncodedFileWriter::convert_unencoded_file / new (encoded_file_writer.rs:53-67, 146-163)
   if (pre < 1) return fail(LCPC_ERR_INVALID_ARG, "Number of pre-encoded columns must be greater than 0");
@@ -86,6 +94,12 @@ inline lcpc_status pos_dims_check(size_t pre, size_t enc) {
   if (enc <= pre)
     return fail(LCPC_ERR_INVALID_ARG, "Number of encoded columns must be greater than the number of columns");
   if ((int)log2_np2(enc) > field_info(POS_FID).s) return fail(LCPC_FFT_TOO_BIG, "FFTError::TooBig");
+  return LCPC_OK;
+}
+// the same for every job of a queue, the first failure returned
+inline lcpc_status pos_dims_check(const size_t *pre, const size_t *enc, size_t n_jobs) {
+  for (size_t j = 0; j < n_jobs; j++)
+    if (lcpc_status st = pos_dims_check(pre[j], enc[j])) return st;
   return LCPC_OK;
 }
 

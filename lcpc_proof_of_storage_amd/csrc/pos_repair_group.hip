@@ -34,10 +34,8 @@
 // Listed columns are not in the arena at all: no kernel can read them.  Control flow is uniform over a
 // workgroup in the row kernel (its tiles share enc) and over a wave elsewhere, but for bounds.  No
 // atomics: every output byte has one writer.
-#include "blake3_dev.hpp"
-#include "field.hpp"
 #include "kernels.hpp"
-#include "pos.hpp"
+#include "pos_rows_dev.hpp"
 #include "prof.hpp"
 
 namespace lcpc {
@@ -46,17 +44,10 @@ namespace {
 
 using namespace b3;
 
-__device__ __forceinline__ int repair_bitrev(int x, int bits) {
-  return (int)(__builtin_bitreverse32((uint32_t)x) >> (32 - bits));
-}
 // index in the table of 2^POS_INGEST_MAX_LOG_ENC points of x_c, c a stored position of a row of 2^log_enc
 __device__ __forceinline__ size_t repair_point(int c, int log_enc) {
-  const int e = LCPC_FFT_OUTPUT_BITREV ? repair_bitrev(c, log_enc) : c;
+  const int e = LCPC_FFT_OUTPUT_BITREV ? bitrev_bits(c, log_enc) : c;
   return (size_t)e << (POS_INGEST_MAX_LOG_ENC - log_enc);
-}
-// the slot of a row's LDS that k_group_encode stores at position c
-__device__ __forceinline__ int repair_slot(int c, int log_enc) {
-  return LCPC_FFT_OUTPUT_BITREV ? c : repair_bitrev(c, log_enc);
 }
 
 // workgroup j of the launch is job j
@@ -137,26 +128,11 @@ __global__ __launch_bounds__(256) void k_group_repair_rows(const uint8_t *__rest
             ncmask |= 1u << q;
         }
       }
-      buf[(t << (3 + log_enc)) + (r << log_enc) + repair_slot(c, log_enc)] = e;
+      buf[row_elem(t, r, row_slot(c, log_enc), log_enc)] = e;
     }
   }
   // k_group_scrub_rows' inverse stages (times 2 per stage)
-  constexpr int TW_N = 1 << POS_INGEST_MAX_LOG_ENC;
-  for (int lg = 0; lg < log_enc; lg++) {
-    __syncthreads();
-    const int gap = 1 << lg;
-    for (int idx = threadIdx.x; idx < total / 2; idx += 256) {
-      const int row = idx >> (log_enc - 1), i = idx & (enc / 2 - 1);
-      const int j = i & (gap - 1);
-      const int base = (row << log_enc) + ((i >> lg) << (lg + 1));
-      const Fe<F> a = buf[base + j];
-      Fe<F> b = buf[base + j + gap];
-      if (j) b = fe_mul<F>(b, fe_load<F>(tw, (size_t)(TW_N - (j << (POS_INGEST_MAX_LOG_ENC - 1 - lg)))));
-      buf[base + j] = fe_add<F>(a, b);
-      buf[base + j + gap] = fe_sub<F>(a, b);
-    }
-  }
-  __syncthreads();
+  rows_inverse_stages<F>(buf, log_enc, total, tw);
   // degree check and x P'(x) in one sweep: min(enc, 64) lanes share a row and OR through the wave's ballot
   const int log_g = log_enc < 6 ? log_enc : 6, g = 1 << log_g, rows_per_wave = 64 >> log_g;
   const int wave = (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -187,20 +163,7 @@ __global__ __launch_bounds__(256) void k_group_repair_rows(const uint8_t *__rest
     }
   }
   // k_group_encode's forward stages
-  for (int lg = log_enc - 1; lg >= 0; lg--) {
-    __syncthreads();
-    const int gap = 1 << lg;
-    for (int idx = threadIdx.x; idx < total / 2; idx += 256) {
-      const int row = idx >> (log_enc - 1), i = idx & (enc / 2 - 1);
-      const int j = i & (gap - 1);
-      const int base = (row << log_enc) + ((i >> lg) << (lg + 1));
-      const Fe<F> a = buf[base + j], b = buf[base + j + gap];
-      buf[base + j] = fe_add<F>(a, b);
-      buf[base + j + gap] = j ? fe_mul<F>(fe_sub_lazy<F>(a, b), fe_load<F>(tw, (size_t)j << (POS_INGEST_MAX_LOG_ENC - 1 - lg)))
-                              : fe_sub<F>(a, b);
-    }
-  }
-  __syncthreads();
+  rows_forward_stages<F>(buf, log_enc, total, tw);
   // fill, at the listed positions only: one product, canonical, column-major into the repaired arena
   for (int idx = threadIdx.x; idx < total; idx += 256) {
     const int r = idx & 7, c = (idx >> 3) & (enc - 1), t = idx >> (3 + log_enc);
@@ -209,7 +172,7 @@ __global__ __launch_bounds__(256) void k_group_repair_rows(const uint8_t *__rest
     const PosRepairJob &jb = jobs[tl.job];
     const int32_t m = reinterpret_cast<const int32_t *>(arena + jb.cmap)[c];
     if (m < 0) continue;
-    const Fe<F> v = fe_mul<F>(buf[(t << (3 + log_enc)) + (r << log_enc) + repair_slot(c, log_enc)],
+    const Fe<F> v = fe_mul<F>(buf[row_elem(t, r, row_slot(c, log_enc), log_enc)],
                               fe_load<F>(tabs, jb.dinv0 + (size_t)m));
     uint64_t *col = reinterpret_cast<uint64_t *>(rep + jb.rep) + (size_t)m * jb.rows_pad;
     col[tl.row_lo + r] = (uint64_t)v.v[0] | ((uint64_t)v.v[1] << 32);
@@ -246,10 +209,10 @@ __global__ __launch_bounds__(256) void k_group_repair_chunks(const uint8_t *__re
                                                              const PosIngestWave *__restrict__ waves, uint32_t n_waves,
                                                              uint32_t *__restrict__ cvs) {
   __shared__ uint4 stage[4][64][5];
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const uint32_t w = blockIdx.x * 4 + wave;
-  if (w >= n_waves) return;
-  const PosIngestWave wv = waves[w];
+  const uint32_t lane = threadIdx.x & 63;
+  uint32_t wave;
+  PosIngestWave wv;
+  if (!chunk_wave(waves, n_waves, wave, wv)) return;
   const PosRepairJob jb = jobs[wv.job];
   const size_t n_cols = jb.n_bad;
   uint32_t cv[8];
@@ -296,18 +259,7 @@ __global__ __launch_bounds__(256) void k_group_repair_trees(const uint8_t *__res
     load8(reinterpret_cast<const uint32_t *>(arena + jb.leaves + 32 * (size_t)c), leaf);
     store8(reinterpret_cast<uint32_t *>(tree + 32 * (size_t)c), leaf);
   }
-  size_t in = 0;
-  for (uint32_t n = enc; n > 1; n >>= 1) {
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < n / 2; i += 256) {
-      uint32_t msg[16], o[8];
-      load8(reinterpret_cast<const uint32_t *>(tree + 32 * (in + 2 * i)), msg);
-      load8(reinterpret_cast<const uint32_t *>(tree + 32 * (in + 2 * i + 1)), msg + 8);
-      hash64(msg, o);
-      store8(reinterpret_cast<uint32_t *>(tree + 32 * (in + n + i)), o);
-    }
-    in += n;
-  }
+  merkle_levels(tree, enc);
 }
 
 }  // namespace

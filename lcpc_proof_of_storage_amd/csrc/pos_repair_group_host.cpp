@@ -3,48 +3,22 @@
 // the tree over the leaves with those digests in place, and a verdict per job -- with a number of
 // launches that does not grow with the number of files.
 //
-//   repair::Planner  (pos_repair_plan.hpp, host only, with the block's layout and the packing) cuts the
-//                  jobs, in order, into steps: a staging group of consecutive jobs (at most four launches)
-//                  or one job for lcpc_pos_repair_columns;
+//   RepairPlanner  (pos_rowgroup_plan.hpp, host only; the block's layout and the packing are
+//                  pos_repair_plan.hpp) cuts the jobs, in order, into steps: a staging group of
+//                  consecutive jobs (at most four launches) or one job for lcpc_pos_repair_columns;
 //   RepairRunner   stages a group -- the written rows of the columns that are not listed packed, the
 //                  leaves, the column maps, the lists and the tables in one page-locked block, one
 //                  upload (h2d_blocks) -- queues its launches as the block lands and the read-back of
 //                  flags, digests and trees (and of the repaired columns where a job wants them) into the
 //                  same block; two blocks alternate, and the host hands group k - 1 to the jobs while
-//                  group k runs;
+//                  group k runs (pos_rowgroup_stage.hpp);
 //   lcpc_pos_repair_plan   the same steps as a work list, host only: what the CPU tests check.
-#include "pos_internal.hpp"
 #include "pos_repair_plan.hpp"
-
-#include <map>
-#include <mutex>
+#include "pos_rowgroup_stage.hpp"
 
 namespace {
 
-using repair::align_up;
 using repair::wants_tree;
-using RepairStep = repair::Step;
-
-// the twiddles of the grouped lengths (the encode's table), built once per device and kept
-lcpc_status repair_twiddles(Device *dev, hipStream_t s, const uint32_t **out) {
-  static std::mutex mu;
-  static std::map<int, uint32_t *> tables;
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = tables.find(dev->id);
-  if (it == tables.end()) {
-    uint32_t *tw = nullptr;
-    HIP_TRY(device_malloc(&tw, ((size_t)1 << POS_INGEST_MAX_LOG_ENC) * POS_WB));
-    hipError_t e = pos_ingest_twiddles(tw, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-      (void)hipFree(tw);
-      HIP_TRY(e);
-    }
-    it = tables.emplace(dev->id, tw).first;
-  }
-  *out = it->second;
-  return LCPC_OK;
-}
 
 // One call's staging and launches.  run() returns with the group's upload, launches and read-back
 // queued and the group before it handed to its jobs; the last group is handed over in finish().
@@ -54,28 +28,20 @@ struct RepairRunner {
   const uint32_t *tw;
   lcpc_pos_repair_job *all;
   DBuf arena, tabs, rep, cvs, out;
-  Pinned stg[2];
-  Events ev;
   struct Pending {
-    bool live = false, tree_only = false, has_cols = false;
+    bool tree_only = false, has_cols = false;
     size_t job_lo = 0, o_flags = 0, o_dig = 0, o_trees = 0, o_rep = 0;
     std::vector<uint32_t> src;
     std::vector<PosRepairJob> jobs;
-  } pend[2];
-  int k = 0;
+  };
+  TwoSlotStager<Pending> stage;
 
   RepairRunner(Device *d, hipStream_t stream, const uint32_t *twiddles, lcpc_pos_repair_job *jobs)
-      : dev(d), s(stream), tw(twiddles), all(jobs) {}
-  // (an early return leaves copies queued on the blocks the members are about to give back)
-  ~RepairRunner() { (void)hipStreamSynchronize(s); }
+      : dev(d), s(stream), tw(twiddles), all(jobs),
+        stage(d, stream, [this](Pending &p, const uint8_t *h) { scatter(p, h); }) {}
 
-  lcpc_status drain(int slot) {
-    Pending &p = pend[slot];
-    if (!p.live) return LCPC_OK;
-    p.live = false;
-    HIP_TRY(hipEventSynchronize(ev.e[slot]));
+  void scatter(const Pending &p, const uint8_t *h) {
     prof::HostScope hs("pos_group_repair_scatter");
-    const uint8_t *h = stg[slot].b();
     auto one = [&](size_t i) {
       const PosRepairJob &g = p.jobs[i];
       lcpc_pos_repair_job &job = all[p.job_lo + p.src[i]];
@@ -102,27 +68,23 @@ struct RepairRunner {
     } else {
       parallel_for(p.jobs.size(), one);
     }
-    return LCPC_OK;
   }
 
   // single_digests: the step's one job went through lcpc_pos_repair_columns, which gave these digests of
   // its listed columns; only its tree is built here
   lcpc_status run(RepairStep &g, const uint8_t *single_digests = nullptr) {
-    const int slot = k & 1;
     const bool tree_only = single_digests != nullptr;
     lcpc_status st;
-    HIP_TRY(ev.init());
-    if ((st = drain(slot))) return st;  // (already drained by the run before this one, but for an error there)
     const size_t n_jobs = g.jobs.size();
     const repair::Layout L = repair::lay_out(g, all, tree_only);
-    const size_t in_bytes = L.in_bytes, out_bytes = L.out_bytes;
-    if (stg[slot].n < L.total && !stg[slot].get(dev, L.total)) return fail(LCPC_ERR_OUT_OF_MEMORY, "pinned host staging");
-    if (arena.n < in_bytes || !arena.p) HIP_TRY(arena.alloc(dev, align_up(in_bytes, (size_t)4 << 20)));
-    if (tabs.n < g.tab_elems * POS_WB + 16 || !tabs.p) HIP_TRY(tabs.alloc(dev, align_up(g.tab_elems * POS_WB + 16, (size_t)1 << 20)));
-    if (rep.n < g.rep_bytes + 16 || !rep.p) HIP_TRY(rep.alloc(dev, align_up(g.rep_bytes + 16, (size_t)4 << 20)));
-    if (cvs.n < g.cv_slots * 32 + 32 || !cvs.p) HIP_TRY(cvs.alloc(dev, align_up(g.cv_slots * 32 + 32, (size_t)1 << 20)));
-    if (out.n < out_bytes || !out.p) HIP_TRY(out.alloc(dev, align_up(out_bytes, (size_t)1 << 20)));
-    uint8_t *h = stg[slot].b();
+    const TableOffsets &T = L.T;
+    const size_t in_bytes = T.in_bytes, out_bytes = L.out_bytes;
+    uint8_t *h = nullptr;
+    if ((st = stage.begin(L.total, &h))) return st;
+    if ((st = ensure(arena, dev, in_bytes, (size_t)4 << 20)) || (st = ensure(tabs, dev, g.tab_elems * POS_WB + 16, (size_t)1 << 20)) ||
+        (st = ensure(rep, dev, g.rep_bytes + 16, (size_t)4 << 20)) || (st = ensure(cvs, dev, g.cv_slots * 32 + 32, (size_t)1 << 20)) ||
+        (st = ensure(out, dev, out_bytes, (size_t)1 << 20)))
+      return st;
     {
       prof::HostScope hs("pos_group_repair_gather");
       repair::pack(g, all, L, single_digests, h);
@@ -130,10 +92,10 @@ struct RepairRunner {
     const uint8_t *d = arena.as<uint8_t>();
     uint8_t *dout = out.as<uint8_t>();
     st = h2d_blocks(dev, arena.as<uint8_t>(), h, in_bytes, in_bytes, s, [&](size_t, size_t) -> lcpc_status {
-      HIP_TRY(pos_group_repair(d, reinterpret_cast<const PosRepairJob *>(d + L.o_jobs), n_jobs,
-                               reinterpret_cast<const PosIngestTile *>(d + L.o_tiles),
-                               reinterpret_cast<const PosIngestWg *>(d + L.o_wgs), g.wgs.size(), g.lds_bytes,
-                               reinterpret_cast<const PosIngestWave *>(d + L.o_waves), g.waves.size(), g.max_chunks,
+      HIP_TRY(pos_group_repair(d, reinterpret_cast<const PosRepairJob *>(d + T.o_jobs), n_jobs,
+                               reinterpret_cast<const PosIngestTile *>(d + T.o_tiles),
+                               reinterpret_cast<const PosIngestWg *>(d + T.o_wgs), g.wgs.size(), g.lds_bytes,
+                               reinterpret_cast<const PosIngestWave *>(d + T.o_waves), g.waves.size(), g.max_chunks,
                                tree_only, tw, tabs.as<uint32_t>(), rep.as<uint8_t>(), cvs.as<uint32_t>(), dout,
                                dout + L.d_dig, dout + L.d_trees, s));
       return LCPC_OK;
@@ -141,25 +103,8 @@ struct RepairRunner {
     if (st) return st;
     HIP_TRY(hipMemcpyAsync(h + in_bytes, out.p, out_bytes, hipMemcpyDeviceToHost, s));
     if (L.want_cols) HIP_TRY(hipMemcpyAsync(h + in_bytes + out_bytes, rep.p, g.rep_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipEventRecord(ev.e[slot], s));
-    Pending &p = pend[slot];
-    p.live = true;
-    p.tree_only = tree_only;
-    p.has_cols = L.want_cols;
-    p.job_lo = g.job_lo;
-    p.o_flags = in_bytes, p.o_dig = in_bytes + L.d_dig, p.o_trees = in_bytes + L.d_trees, p.o_rep = in_bytes + out_bytes;
-    p.src = std::move(g.src);
-    p.jobs = std::move(g.jobs);
-    k++;
-    return drain(slot ^ 1);  // the group before this one, while this one runs
-  }
-
-  lcpc_status finish() {
-    lcpc_status st;
-    if ((st = drain(k & 1))) return st;
-    if ((st = drain((k & 1) ^ 1))) return st;
-    HIP_TRY(hipStreamSynchronize(s));
-    return LCPC_OK;
+    return stage.commit(Pending{tree_only, L.want_cols, g.job_lo, in_bytes, in_bytes + L.d_dig, in_bytes + L.d_trees,
+                                in_bytes + out_bytes, std::move(g.src), std::move(g.jobs)});
   }
 };
 
@@ -180,19 +125,13 @@ lcpc_status repair_single(lcpc_pos_repair_job &job, RepairRunner &runner, size_t
   RepairStep g;
   g.job_lo = j, g.job_hi = j + 1;
   PosRepairJob t{};
-  t.pre = (uint32_t)job.pre, t.log_enc = repair::log2_pow2(job.enc), t.n_chunks = 1, t.n_bad = (uint32_t)job.n_bad;
+  t.pre = (uint32_t)job.pre, t.log_enc = log2_pow2(job.enc), t.n_chunks = 1, t.n_bad = (uint32_t)job.n_bad;
   g.jobs.push_back(t);
   g.src.push_back(0);
   g.col0.push_back(0);
   g.lds_bytes = POS_INGEST_WG_ELEMS * POS_WB;
   const uint8_t none = 0;
   return runner.run(g, digests ? digests : &none);
-}
-
-lcpc_status repair_dims(const size_t *pre, const size_t *enc, size_t n_jobs) {
-  for (size_t j = 0; j < n_jobs; j++)
-    if (lcpc_status st = pos_dims_check(pre[j], enc[j])) return st;
-  return LCPC_OK;
 }
 
 }  // namespace
@@ -225,8 +164,8 @@ lcpc_status lcpc_pos_repair_files_grouped(lcpc_pos_repair_job *jobs, size_t n_jo
   Lease lease(dev);
   HIP_TRY(hipSetDevice(dev->id));
   const uint32_t *tw = nullptr;
-  if ((st = repair_twiddles(dev, lease.s, &tw))) return st;
-  repair::Planner planner(rows.data(), pre.data(), enc.data(), n_bad.data(), n_jobs, pos_group_bytes());
+  if ((st = pos_group_twiddles(dev, lease.s, &tw))) return st;
+  RepairPlanner planner(rows.data(), pre.data(), enc.data(), n_bad.data(), n_jobs, pos_group_bytes());
   for (size_t j = 0; j < n_jobs; j++) jobs[j].status = planner.works(j) ? LCPC_OK : LCPC_ERR_UNRECOVERABLE;
   RepairRunner runner(dev, lease.s, tw, jobs);
   RepairStep g;
@@ -238,7 +177,7 @@ lcpc_status lcpc_pos_repair_files_grouped(lcpc_pos_repair_job *jobs, size_t n_jo
     if (g.jobs.empty()) continue;  // none of its jobs does device work
     if ((st = runner.run(g))) return st;
   }
-  return runner.finish();
+  return runner.stage.finish();
 }
 
 lcpc_status lcpc_pos_repair_plan(const size_t *rows_written, const size_t *pre, const size_t *enc, const size_t *n_bad,
@@ -246,31 +185,9 @@ lcpc_status lcpc_pos_repair_plan(const size_t *rows_written, const size_t *pre, 
                                  size_t *n_launches) {
   if (!rows_written || !pre || !enc || !n_bad || (!tiles && cap)) return fail(LCPC_ERR_INVALID_ARG, "null argument");
   if (!n_jobs) return fail(LCPC_ERR_INVALID_ARG, "no jobs");
-  if (lcpc_status st = repair_dims(pre, enc, n_jobs)) return st;
-  repair::Planner planner(rows_written, pre, enc, n_bad, n_jobs, pos_group_bytes());
-  RepairStep g;
-  size_t n = 0, launches = 0;
-  auto emit = [&](const lcpc_pos_ingest_tile &t) {
-    if (n < cap) tiles[n] = t;
-    n++;
-  };
-  while (planner.next(g)) {
-    if (g.single) {
-      const size_t j = g.job_lo;
-      if (rows_written[j]) emit(lcpc_pos_ingest_tile{j, 0, rows_written[j], LCPC_POS_GROUP_SINGLE, 0});
-      continue;
-    }
-    if (g.jobs.empty()) continue;
-    for (size_t w = 0; w < g.wgs.size(); w++)
-      for (uint32_t i = 0; i < g.wgs[w].n_tiles; i++) {
-        const PosIngestTile &t = g.tiles[g.wgs[w].tile0 + i];
-        emit(lcpc_pos_ingest_tile{g.job_lo + g.src[t.job], t.row_lo, (uint64_t)t.row_lo + t.n_rows, (uint32_t)launches,
-                                  (uint32_t)w});
-      }
-    launches++;
-  }
-  if (n_tiles) *n_tiles = n;
-  if (n_launches) *n_launches = launches;
+  if (lcpc_status st = pos_dims_check(pre, enc, n_jobs)) return st;
+  RepairPlanner planner(rows_written, pre, enc, n_bad, n_jobs, pos_group_bytes());
+  emit_plan(planner, tiles, cap, n_tiles, n_launches);
   return LCPC_OK;
 }
 

@@ -37,10 +37,8 @@
 // Control flow is uniform over a workgroup in the first kernel (its tiles share enc) and over a wave in
 // the chunk kernel; the third is uniform over the workgroup but for the column and node bounds.  No
 // atomics: every output byte has one writer.
-#include "blake3_dev.hpp"
-#include "field.hpp"
 #include "kernels.hpp"
-#include "pos.hpp"
+#include "pos_rows_dev.hpp"
 #include "prof.hpp"
 
 namespace lcpc {
@@ -48,10 +46,6 @@ namespace lcpc {
 namespace {
 
 using namespace b3;
-
-__device__ __forceinline__ int scrub_bitrev(int x, int bits) {
-  return (int)(__builtin_bitreverse32((uint32_t)x) >> (32 - bits));
-}
 
 // workgroup b of the launch reads wgs[b]; element idx of its LDS is (tile slot, row of the tile, slot)
 template <class F>
@@ -76,29 +70,13 @@ __global__ __launch_bounds__(256) void k_group_scrub_rows(const uint8_t *__restr
       const uint64_t *col = reinterpret_cast<const uint64_t *>(arena + jb.img) + (size_t)c * jb.rows_pad;
       v = col[tl.row_lo + r];
     }
-    const int slot = LCPC_FFT_OUTPUT_BITREV ? c : scrub_bitrev(c, log_enc);
     Fe<F> e;
     e.v[0] = (uint32_t)v;
     e.v[1] = (uint32_t)(v >> 32);
-    buf[(t << (3 + log_enc)) + (r << log_enc) + slot] = e;
+    buf[row_elem(t, r, row_slot(c, log_enc), log_enc)] = e;
   }
   // D^-1 (times 2 per stage): the encode's stages in reverse order with the inverse twiddles
-  constexpr int TW_N = 1 << POS_INGEST_MAX_LOG_ENC;
-  for (int lg = 0; lg < log_enc; lg++) {
-    __syncthreads();
-    const int gap = 1 << lg;
-    for (int idx = threadIdx.x; idx < total / 2; idx += 256) {
-      const int row = idx >> (log_enc - 1), i = idx & (enc / 2 - 1);
-      const int j = i & (gap - 1);
-      const int base = (row << log_enc) + ((i >> lg) << (lg + 1));
-      const Fe<F> a = buf[base + j];
-      Fe<F> b = buf[base + j + gap];
-      if (j) b = fe_mul<F>(b, fe_load<F>(tw, (size_t)(TW_N - (j << (POS_INGEST_MAX_LOG_ENC - 1 - lg)))));
-      buf[base + j] = fe_add<F>(a, b);
-      buf[base + j + gap] = fe_sub<F>(a, b);
-    }
-  }
-  __syncthreads();
+  rows_inverse_stages<F>(buf, log_enc, total, tw);
   // a row is dirty iff a slot k >= pre is non-zero.  min(enc, 64) lanes share a row and OR through the
   // wave's ballot; the group's first lane stores the row's byte, 0 or 1: one writer per byte.
   const int log_g = log_enc < 6 ? log_enc : 6, g = 1 << log_g, rows_per_wave = 64 >> log_g;
@@ -133,10 +111,10 @@ __global__ __launch_bounds__(256) void k_group_scrub_chunks(const uint8_t *__res
                                                             const PosIngestWave *__restrict__ waves, uint32_t n_waves,
                                                             uint32_t *__restrict__ cvs, uint8_t *__restrict__ cflags) {
   __shared__ uint4 stage[4][64][5];
-  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const uint32_t w = blockIdx.x * 4 + wave;
-  if (w >= n_waves) return;
-  const PosIngestWave wv = waves[w];
+  const uint32_t lane = threadIdx.x & 63;
+  uint32_t wave;
+  PosIngestWave wv;
+  if (!chunk_wave(waves, n_waves, wave, wv)) return;
   const PosScrubJob jb = jobs[wv.job];
   const size_t n_cols = (size_t)1 << jb.log_enc;
   uint32_t cv[8];

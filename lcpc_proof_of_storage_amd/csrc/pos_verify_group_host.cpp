@@ -20,12 +20,8 @@ namespace {
 
 constexpr size_t VG_MAX_JOBS = (size_t)1 << 16, VG_MAX_COLS = (size_t)1 << 16, VG_MAX_WAVES = (size_t)1 << 20;
 
-inline size_t ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
-inline size_t job_rows(size_t n_bytes, size_t pre) { return ceil_div(ceil_div(n_bytes, POS_DB), pre); }
 // a staged column: 2 n_rows words rounded up to a 16-byte unit; its leaf message: 8 zero words first
 inline size_t col_words(size_t n_rows) { return align_up(2 * n_rows, 4); }
-inline size_t leaf_chunks(size_t n_rows) { return ceil_div(8 + 2 * n_rows, 256); }
 
 // ---- Ft63 Montgomery words on the host (R = 2^64; every operand but b is reduced)
 struct Mont63 {
@@ -202,10 +198,10 @@ struct VerifyRunner {
     const size_t in_bytes = align_up(o_fwaves + g.fwaves.size() * sizeof(PosVerifyWave), 256);
     const size_t total = in_bytes + g.n_cols * 4;
     if (stg[slot].n < total && !stg[slot].get(dev, total)) return fail(LCPC_ERR_OUT_OF_MEMORY, "pinned host staging");
-    if (arena.n < in_bytes || !arena.p) HIP_TRY(arena.alloc(dev, align_up(in_bytes, (size_t)4 << 20)));
-    if (cvs.n < g.n_slots * 32 || !cvs.p) HIP_TRY(cvs.alloc(dev, align_up(g.n_slots * 32, (size_t)1 << 20)));
-    if (partials.n < g.n_slots * 8 || !partials.p) HIP_TRY(partials.alloc(dev, align_up(g.n_slots * 8, (size_t)1 << 20)));
-    if (bits.n < g.n_cols * 4 || !bits.p) HIP_TRY(bits.alloc(dev, align_up(g.n_cols * 4, (size_t)1 << 16)));
+    lcpc_status est;
+    if ((est = ensure(arena, dev, in_bytes, (size_t)4 << 20)) || (est = ensure(cvs, dev, g.n_slots * 32, (size_t)1 << 20)) ||
+        (est = ensure(partials, dev, g.n_slots * 8, (size_t)1 << 20)) || (est = ensure(bits, dev, g.n_cols * 4, (size_t)1 << 16)))
+      return est;
     uint8_t *h = stg[slot].b();
     {
       prof::HostScope hs("pos_group_verify_gather");

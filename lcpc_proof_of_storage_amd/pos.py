@@ -1289,6 +1289,19 @@ def _leaf_chunks(rows: int) -> int:
     return (32 + WRITTEN_BYTES_WIDTH * rows + 1023) // 1024
 
 
+def _row_plan(entry, columns):
+    """the size-then-fill calls of lcpc_pos_ingest_plan, lcpc_pos_scrub_plan and lcpc_pos_repair_plan
+    (entry) over the per-job size arrays `columns`: (tiles, n_groups)"""
+    n, launches = C.c_size_t(), C.c_size_t()
+    args = tuple(a.ctypes.data_as(N.szp) for a in columns) + (columns[0].size,)
+    _raise(entry(*args, None, 0, C.byref(n), C.byref(launches)))
+    dt = np.dtype([("job", "<u8"), ("row_lo", "<u8"), ("row_hi", "<u8"), ("launch", "<u4"), ("workgroup", "<u4")])
+    assert dt.itemsize == C.sizeof(N.PosIngestTile)
+    tiles = np.zeros(n.value, dt)
+    _raise(entry(*args, tiles.ctypes.data_as(C.POINTER(N.PosIngestTile)), tiles.size, C.byref(n), C.byref(launches)))
+    return tiles, launches.value
+
+
 def ingest_plan(n_bytes, pres, encs):
     """lcpc_pos_ingest_plan: (tiles, n_groups) for files of n_bytes[j] bytes at dims pres[j] / encs[j].
     tiles is a structured array with the fields job, row_lo, row_hi, launch and workgroup: the work list
@@ -1297,16 +1310,7 @@ def ingest_plan(n_bytes, pres, encs):
     nb, pr, en = _sizes(n_bytes), _sizes(pres), _sizes(encs)
     if not (nb.size == pr.size == en.size):
         raise ValueError("n_bytes, pres and encs must have one entry per job")
-    n, launches = C.c_size_t(), C.c_size_t()
-    L = N.load()
-    args = (nb.ctypes.data_as(N.szp), pr.ctypes.data_as(N.szp), en.ctypes.data_as(N.szp), nb.size)
-    _raise(L.lcpc_pos_ingest_plan(*args, None, 0, C.byref(n), C.byref(launches)))
-    dt = np.dtype([("job", "<u8"), ("row_lo", "<u8"), ("row_hi", "<u8"), ("launch", "<u4"), ("workgroup", "<u4")])
-    assert dt.itemsize == C.sizeof(N.PosIngestTile)
-    tiles = np.zeros(n.value, dt)
-    _raise(L.lcpc_pos_ingest_plan(*args, tiles.ctypes.data_as(C.POINTER(N.PosIngestTile)), tiles.size, C.byref(n),
-                                  C.byref(launches)))
-    return tiles, launches.value
+    return _row_plan(N.load().lcpc_pos_ingest_plan, (nb, pr, en))
 
 
 def _addr(a):
@@ -1413,16 +1417,7 @@ def scrub_plan(rows_written, pres, encs):
     rw, pr, en = _sizes(rows_written), _sizes(pres), _sizes(encs)
     if not (rw.size == pr.size == en.size):
         raise ValueError("rows_written, pres and encs must have one entry per job")
-    n, launches = C.c_size_t(), C.c_size_t()
-    L = N.load()
-    args = (rw.ctypes.data_as(N.szp), pr.ctypes.data_as(N.szp), en.ctypes.data_as(N.szp), rw.size)
-    _raise(L.lcpc_pos_scrub_plan(*args, None, 0, C.byref(n), C.byref(launches)))
-    dt = np.dtype([("job", "<u8"), ("row_lo", "<u8"), ("row_hi", "<u8"), ("launch", "<u4"), ("workgroup", "<u4")])
-    assert dt.itemsize == C.sizeof(N.PosIngestTile)
-    tiles = np.zeros(n.value, dt)
-    _raise(L.lcpc_pos_scrub_plan(*args, tiles.ctypes.data_as(C.POINTER(N.PosIngestTile)), tiles.size, C.byref(n),
-                                 C.byref(launches)))
-    return tiles, launches.value
+    return _row_plan(N.load().lcpc_pos_scrub_plan, (rw, pr, en))
 
 
 def _byte_view(data) -> np.ndarray:
@@ -1501,17 +1496,7 @@ def repair_plan(rows_written, pres, encs, n_bad):
     rw, pr, en, nb = _sizes(rows_written), _sizes(pres), _sizes(encs), _sizes(n_bad)
     if not (rw.size == pr.size == en.size == nb.size):
         raise ValueError("rows_written, pres, encs and n_bad must have one entry per job")
-    n, launches = C.c_size_t(), C.c_size_t()
-    L = N.load()
-    args = (rw.ctypes.data_as(N.szp), pr.ctypes.data_as(N.szp), en.ctypes.data_as(N.szp), nb.ctypes.data_as(N.szp),
-            rw.size)
-    _raise(L.lcpc_pos_repair_plan(*args, None, 0, C.byref(n), C.byref(launches)))
-    dt = np.dtype([("job", "<u8"), ("row_lo", "<u8"), ("row_hi", "<u8"), ("launch", "<u4"), ("workgroup", "<u4")])
-    assert dt.itemsize == C.sizeof(N.PosIngestTile)
-    tiles = np.zeros(n.value, dt)
-    _raise(L.lcpc_pos_repair_plan(*args, tiles.ctypes.data_as(C.POINTER(N.PosIngestTile)), tiles.size, C.byref(n),
-                                  C.byref(launches)))
-    return tiles, launches.value
+    return _row_plan(N.load().lcpc_pos_repair_plan, (rw, pr, en, nb))
 
 
 def repair_files_grouped(images, pres, encs, rows_written, row_capacities, bad_cols, leaves=None,

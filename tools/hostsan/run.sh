@@ -4,9 +4,11 @@
 # record absorb against one append_message per record, at every block offset) and the
 # Brakedown matgen (CSR invariants for SdigCode 1..6), and the stored files' image stager
 # (pos_image.hpp: strided gather / scatter by mapping and by pread, the chunk-aligned row batches,
-# the column-block partition), and the host-only half of the grouped repair of stored files
-# (pos_repair_plan.hpp: the staging groups, the block's layout and the packing, with the listed columns
-# of every image poisoned).  GPU sanitizers are not available.
+# the column-block partition), and the host-only half of the grouped ingest, scrub and repair of stored
+# files (pos_rowgroup_plan.hpp, pos_repair_plan.hpp: the three planners over the fleets of the plan
+# golden, the tables' ladder and copy, the column packing of scrub and repair with the rows that are not
+# written and the listed columns of every image poisoned, empty groups and tables).  GPU sanitizers are
+# not available.
 set -e -o pipefail
 cd "$(dirname "$0")/../../lcpc_proof_of_storage_amd/csrc"
 OUT=${TMPDIR:-/tmp}/lcpc_hostsan; mkdir -p "$OUT"
@@ -15,10 +17,10 @@ g++ $SAN ../../tools/hostsan/transcript_san.cpp transcript.cpp -o "$OUT/transcri
 g++ $SAN -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include ../../tools/hostsan/matgen_san.cpp sdig_host.cpp transcript.cpp \
   -o "$OUT/matgen_san" -lpthread
 g++ $SAN ../../tools/hostsan/pos_image_san.cpp -o "$OUT/pos_image_san" -lpthread
-g++ $SAN -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include ../../tools/hostsan/pos_repair_san.cpp -o "$OUT/pos_repair_san" -lpthread
+g++ $SAN -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include ../../tools/hostsan/pos_rowgroup_san.cpp -o "$OUT/pos_rowgroup_san" -lpthread
 export ASAN_OPTIONS=detect_leaks=0 UBSAN_OPTIONS=halt_on_error=1
 LCPC_KECCAK=scalar "$OUT/transcript_san"
 LCPC_KECCAK=avx512 "$OUT/transcript_san"
 "$OUT/matgen_san" | tail -1
 "$OUT/pos_image_san"
-"$OUT/pos_repair_san"
+"$OUT/pos_rowgroup_san"
