@@ -58,7 +58,8 @@ extern "C" {
  * lcpc_pos_verify_group_plan).  So is the grouped ingest of small files (lcpc_pos_ingest_job,
  * lcpc_pos_encode_files_grouped, lcpc_pos_ingest_tile, lcpc_pos_ingest_plan).  So is the grouped scrub of
  * stored files (lcpc_pos_scrub_job, lcpc_pos_scrub_files_grouped, lcpc_pos_scrub_plan).  So is the grouped
- * repair of stored files (lcpc_pos_repair_job, lcpc_pos_repair_files_grouped, lcpc_pos_repair_plan). */
+ * repair of stored files (lcpc_pos_repair_job, lcpc_pos_repair_files_grouped, lcpc_pos_repair_plan).  So is the
+ * grouped locate of stored files (lcpc_pos_locate_job, lcpc_pos_locate_files_grouped). */
 #define LCPC_ABI_VERSION 3
 
 typedef enum lcpc_status {
@@ -941,6 +942,53 @@ lcpc_status lcpc_pos_repair_files_grouped(lcpc_pos_repair_job *jobs, size_t n_jo
 lcpc_status lcpc_pos_repair_plan(const size_t *rows_written, const size_t *pre, const size_t *enc,
                                  const size_t *n_bad, size_t n_jobs, lcpc_pos_ingest_tile *tiles,
                                  size_t cap, size_t *n_tiles, size_t *n_launches);
+/* ---- PoS grouped locate: the damaged columns of many stored files named by their own rows in one pass
+ * (Reed-Solomon syndromes, Berlekamp-Massey and a root search, as lcpc_pos_locate_porenc) ----
+ * NO COUNTERPART IN THE REFERENCE.  Additive within LCPC_ABI_VERSION 3.  The leg for a store whose
+ * `.portree` cannot say where the damage is: every such file went through lcpc_pos_locate_porenc on its
+ * own.  Here a queue of (stored image, known-bad columns) jobs is answered with a number of launches that
+ * does not grow with the number of files.
+ * EQUALITY: for every job, col_status, the three counters and status are byte for byte what
+ * lcpc_pos_locate_porenc(porenc, pre, enc, rows_written, row_capacity, known_bad, n_known, ...) returns
+ * and writes (a job whose status is not LCPC_OK has its other outputs left as they were, as that entry
+ * leaves them).  row_status has no per-file counterpart: 0 the row is a codeword on the columns that are
+ * not listed, 1 its wrong positions were located, 2 it is no codeword and cannot say where.
+ * VERDICTS are per job: one job's failure never fails the call and never touches a neighbour's outputs.
+ * status is LCPC_ERR_UNRECOVERABLE when n_known > enc - pre (that job does no device work), or when the
+ * known columns and the columns that hold a word that is not < p together exceed enc - pre.
+ * n_known == enc - pre leaves no syndromes: every row is status 0.  rows_written == 0 is legal.  KNOWN
+ * COLUMNS ARE NEVER READ, neither by the host packing nor by a kernel.
+ * STAGING, GROUPS: exactly the grouped repair's, with known_bad as the listed columns: the same cut, the
+ * same tables, the same two alternating page-locked blocks; row statuses, column statuses and row flags
+ * come back in one copy.  The syndromes of the dirty rows (at most the packed image's size) and the rows'
+ * position masks stay on the device.  A group takes at most LCPC_POS_LOCATE_LAUNCHES_PER_GROUP kernel
+ * launches, whatever the number of jobs or of distinct enc, all inside one profiling region
+ * (pos_group_locate).  NO PLAN ENTRY of its own: the work list of a group's row launch is
+ * lcpc_pos_repair_plan's with n_bad = n_known.
+ * ROUTING: a job with enc > LCPC_POS_LOCATE_MAX_ENC, or whose image alone exceeds a group, or whose columns
+ * have more than 2^16 1-KiB chunks, ends the group before it and goes through lcpc_pos_locate_porenc
+ * inside the same call.  So does, after the last group, a job one of whose columns that are not listed
+ * holds a word that is not < p (status 2 in col_status): that entry names such columns and takes them as
+ * erasures.  The row_status of a job answered that way is LCPC_POS_LOCATE_ROW_NOT_EVALUATED throughout.
+ * Errors, before any device work and before any output byte is written: a NULL jobs, n_jobs == 0,
+ * porenc == NULL with rows_written > 0, rows_written > row_capacity, pre == 0, enc no power of two or
+ * enc <= pre, col_status NULL, known_bad NULL with n_known > 0, a column index >= enc, a duplicate index:
+ * LCPC_ERR_INVALID_ARG; enc beyond the field's two-adicity: LCPC_FFT_TOO_BIG; no device:
+ * LCPC_ERR_NO_DEVICE.  Ft63 and BLAKE3 only.  Threading as every entry: a stream of its own per call. */
+#define LCPC_POS_LOCATE_MAX_ENC ((size_t)1024)  /* as LCPC_POS_REPAIR_MAX_ENC */
+#define LCPC_POS_LOCATE_LAUNCHES_PER_GROUP 4    /* locators, rows + syndromes, Berlekamp-Massey + roots, columns */
+#define LCPC_POS_LOCATE_ROW_NOT_EVALUATED 0xff  /* row_status of a job lcpc_pos_locate_porenc answered */
+typedef struct lcpc_pos_locate_job {
+  const uint8_t *porenc;     /* column-major image (lcpc_pos_encode_file's layout); NULL iff rows_written == 0 */
+  size_t pre, enc, rows_written, row_capacity;
+  const uint64_t *known_bad; /* erasures: n_known distinct columns < enc; never read, host or device */
+  size_t n_known;
+  uint8_t *col_status;       /* enc bytes, out, required: 0 / 1 / 2 / 3 as lcpc_pos_locate_porenc */
+  uint8_t *row_status;       /* rows_written bytes, out, may be NULL: 0 codeword, 1 located, 2 not locatable */
+  size_t n_bad_cols, n_dirty_rows, n_unlocatable_rows; /* out */
+  lcpc_status status;        /* out: LCPC_OK, or LCPC_ERR_UNRECOVERABLE (known + non-canonical > enc - pre) */
+} lcpc_pos_locate_job;
+lcpc_status lcpc_pos_locate_files_grouped(lcpc_pos_locate_job *jobs, size_t n_jobs);
 /* The streaming writer itself: EncodedFileWriter::new (:40-105; porenc = the preallocated
  * image of row_capacity rows, batch_rows as above), push_bytes (:233-262), and
  * finalize_to_column_digest / _to_commit / _to_merkle_tree (:452-501): digests = the enc column

@@ -28,4 +28,5 @@ from .pos import scrub_files_grouped, scrub_plan  # noqa: F401,E402
 from .pos_files import scrub_files  # noqa: F401,E402
 # the leg after it: the damaged columns of many stored files recomputed in one pass
 from .pos import repair_files_grouped, repair_plan  # noqa: F401,E402
+from .pos import locate_files_grouped  # noqa: F401,E402
 from .pos_files import repair_files  # noqa: F401,E402

@@ -97,6 +97,14 @@ class PosRepairJob(C.Structure):
                 ("cols_out", vp), ("digests_out", vp), ("tree_out", vp), ("root_out", vp), ("status", C.c_int32)]
 
 
+class PosLocateJob(C.Structure):
+    """lcpc_pos_locate_job (include/lcpc_mi.h)"""
+    _fields_ = [("porenc", vp), ("pre", C.c_size_t), ("enc", C.c_size_t), ("rows_written", C.c_size_t),
+                ("row_capacity", C.c_size_t), ("known_bad", vp), ("n_known", C.c_size_t), ("col_status", vp),
+                ("row_status", vp), ("n_bad_cols", C.c_size_t), ("n_dirty_rows", C.c_size_t),
+                ("n_unlocatable_rows", C.c_size_t), ("status", C.c_int32)]
+
+
 class CommOps(C.Structure):
     _fields_ = [("user", vp), ("all_gather", ALL_GATHER_FN), ("all_to_all_v", ALL_TO_ALL_V_FN),
                 ("broadcast", BROADCAST_FN)]
@@ -250,6 +258,7 @@ SIGNATURES = {
     "lcpc_pos_scrub_plan": (i32, [szp, szp, szp, sz, C.POINTER(PosIngestTile), sz, szp, szp]),
     "lcpc_pos_repair_files_grouped": (i32, [C.POINTER(PosRepairJob), sz]),
     "lcpc_pos_repair_plan": (i32, [szp, szp, szp, szp, sz, C.POINTER(PosIngestTile), sz, szp, szp]),
+    "lcpc_pos_locate_files_grouped": (i32, [C.POINTER(PosLocateJob), sz]),
     "lcpc_pos_update_rows": (i32, [sz, sz, sz, sz, szp, szp, szp, szp]),
     "lcpc_pos_update_evaluation": (i32, [vp, vp, sz, vp, vp, sz, u64p, u64p, sz, u64p, sz,
                                          u64p, u64p, u8p, u8p, u64p, u64p, u8p, u8p, u64p]),

@@ -229,5 +229,40 @@ hipError_t pos_group_repair(const uint8_t *arena, const PosRepairJob *jobs, size
                             size_t n_waves, size_t max_chunks, bool tree_only_group, const uint32_t *tw, uint32_t *tabs,
                             uint8_t *rep, uint32_t *cvs, uint8_t *flags, uint8_t *digests, uint8_t *trees,
                             hipStream_t s);
+// k_group_repair_locators alone, a workgroup per job (the grouped locate's first launch: it needs
+// lambda; the inverse table is written too and not read)
+hipError_t pos_group_repair_locators(const uint8_t *arena, const PosRepairJob *jobs, size_t n_jobs, const uint32_t *tw,
+                                     uint32_t *tabs, hipStream_t s);
+
+// ---- pos_locate_group.hip: the damaged columns of many stored files named by the rows themselves --
+// Reed-Solomon error location by syndromes, Berlekamp-Massey and a root search -- in one
+// pass.  A staging group is the grouped repair's (PosRepairJob with the known columns as
+// the listed ones, tiles and workgroups; no waves, leaves or trees) plus one record per job of where its
+// rows' syndromes, position masks and column statuses go:
+//   synd0   element of the syndrome arena where row 0's N = enc - pre - n_bad syndromes S_0 .. S_{N-1}
+//           stand (8-byte words, fully reduced; row r at synd0 + r N; written for dirty rows only);
+//   mask0   64-bit word of the mask arena where row 0's enc-bit position mask starts (row r at mask0 +
+//           r max(1, enc / 64); bit c = the root search found stored position c; written for the rows
+//           Berlekamp-Massey gave a candidate for, read for the located rows only);
+//   col0    the first of the job's enc bytes of col_status.
+struct PosLocateJob {
+  uint64_t synd0, mask0, col0, reserved;
+};
+// LDS of a k_group_locate_bm workgroup (one wave, one row) for a group whose longest row has enc_max
+// points: the row's syndromes, later C zero-padded for the root search (enc_max elements), and C, B and
+// the next B of at most N / 2 + 1 <= enc_max / 2 coefficients each.
+constexpr size_t pos_locate_bm_lds(size_t enc_max) { return (enc_max + 3 * (enc_max / 2)) * 8; }
+// The launches of a staging group, at most four, in one profiling region (pos_group_locate):
+// k_group_repair_locators (only with any_listed), k_group_locate_rows over n_wgs workgroups with lds_rows
+// of LDS each, k_group_locate_bm with a one-wave workgroup per row slot of the n_tiles tiles and lds_bm of
+// LDS (both none when no job has a row), k_group_locate_cols with a workgroup per job.  flags[row]: the
+// repair's row flags; rstat[row] = 0 codeword, 1 located, 2 not locatable; col_status[col0 + c] = 0, 1
+// (some located row names c) or 3 (listed).  Every byte of flags, rstat and col_status has one writer and
+// nothing is cleared first.  tw: pos_ingest_twiddles.
+hipError_t pos_group_locate(const uint8_t *arena, const PosRepairJob *jobs, const PosLocateJob *ljobs, size_t n_jobs,
+                            const PosIngestTile *tiles, size_t n_tiles, const PosIngestWg *wgs, size_t n_wgs,
+                            size_t lds_rows, size_t lds_bm, bool any_listed, const uint32_t *tw, uint32_t *tabs,
+                            uint64_t *synd, uint64_t *masks, uint8_t *flags, uint8_t *rstat, uint8_t *col_status,
+                            hipStream_t s);
 
 }  // namespace lcpc

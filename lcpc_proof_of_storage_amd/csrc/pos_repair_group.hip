@@ -264,6 +264,13 @@ __global__ __launch_bounds__(256) void k_group_repair_trees(const uint8_t *__res
 
 }  // namespace
 
+hipError_t pos_group_repair_locators(const uint8_t *arena, const PosRepairJob *jobs, size_t n_jobs, const uint32_t *tw,
+                                     uint32_t *tabs, hipStream_t s) {
+  if (!n_jobs || n_jobs >= ((size_t)1 << 24)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((k_group_repair_locators<Ft63>), dim3((unsigned)n_jobs), dim3(256), 0, s, arena, jobs, tw, tabs);
+  return hipGetLastError();
+}
+
 hipError_t pos_group_repair(const uint8_t *arena, const PosRepairJob *jobs, size_t n_jobs, const PosIngestTile *tiles,
                             const PosIngestWg *wgs, size_t n_wgs, size_t lds_bytes, const PosIngestWave *waves,
                             size_t n_waves, size_t max_chunks, bool tree_only_group, const uint32_t *tw, uint32_t *tabs,

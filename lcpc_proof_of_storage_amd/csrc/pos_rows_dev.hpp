@@ -26,14 +26,15 @@ __device__ __forceinline__ int row_elem(int t, int r, int i, int log_enc) {
 
 // k_ntt_small's radix-2 DIF stages over the `total` elements of a workgroup of 256 threads, rows of
 // 2^log_enc points: gap = 2^lg, w_enc^(enc / (2 gap) j) = tw[j << (MAX_LOG - 1 - lg)].  A barrier
-// before every stage and one after the last.
-template <class F>
+// before every stage and one after the last.  NT: the workgroup's threads where they are not 256
+// (k_group_locate_bm: one wave over its one row).
+template <class F, int NT = 256>
 __device__ __forceinline__ void rows_forward_stages(Fe<F> *buf, int log_enc, int total, const uint32_t *__restrict__ tw) {
   const int enc = 1 << log_enc;
   for (int lg = log_enc - 1; lg >= 0; lg--) {
     __syncthreads();
     const int gap = 1 << lg;
-    for (int idx = threadIdx.x; idx < total / 2; idx += 256) {
+    for (int idx = threadIdx.x; idx < total / 2; idx += NT) {
       const int row = idx >> (log_enc - 1), i = idx & (enc / 2 - 1);
       const int j = i & (gap - 1);
       const int base = (row << log_enc) + ((i >> lg) << (lg + 1));

@@ -1549,6 +1549,61 @@ def repair_files_grouped(images, pres, encs, rows_written, row_capacities, bad_c
     return out
 
 
+# ---------------------------------------------------------------- grouped locate of stored files
+LOCATE_MAX_ENC = 1024             # LCPC_POS_LOCATE_MAX_ENC: rows of more points take lcpc_pos_locate_porenc
+LOCATE_LAUNCHES_PER_GROUP = 4     # LCPC_POS_LOCATE_LAUNCHES_PER_GROUP
+LOCATE_ROW_NOT_EVALUATED = 0xFF   # LCPC_POS_LOCATE_ROW_NOT_EVALUATED
+
+
+def locate_files_grouped(images, pre, enc, rows_written, row_capacity, known_bad=None,
+                         want_row_status: bool = False) -> list:
+    """lcpc_pos_locate_files_grouped: the damaged columns of many stored files named by their own rows
+    (syndromes, Berlekamp-Massey, a root search) in one call.  Job j is the column-major `.porenc` image
+    images[j] (a numpy array or an mmap of row_capacity[j] x enc[j] elements, None with no rows) of which
+    rows_written[j] rows count and known_bad[j] the columns already known to be bad (distinct, never read
+    from the image; None for none).  Returns one dict per job: status (0, or UNRECOVERABLE when the known
+    columns and those holding a word that is not < p exceed enc - pre), col_status ((enc,) uint8: 0 sound,
+    1 some row located a wrong element there, 2 it holds a word that is not < p, 3 listed), n_bad_cols,
+    n_dirty_rows (rows that are no codewords), n_unlocatable_rows (of those, the rows that cannot name
+    their wrong positions) and row_status ((rows_written,) uint8 with want_row_status: 0 / 1 / 2, or
+    LOCATE_ROW_NOT_EVALUATED throughout for a job the single-file entry answered).  The data of a failed
+    job is None.  col_status, the counters and status are byte for byte lcpc_pos_locate_porenc's per file;
+    the launches are per staging group of files (the grouped repair's groups with known_bad as its list:
+    repair_plan(rows_written, pre, enc, [len(k) for k in known_bad]) is the work list)."""
+    n = len(images)
+    pres, encs = [int(p) for p in pre], [int(e) for e in enc]
+    rows, caps = [int(r) for r in rows_written], [int(c) for c in row_capacity]
+    known_bad = [None] * n if known_bad is None else list(known_bad)
+    if not (len(pres) == len(encs) == len(rows) == len(caps) == len(known_bad) == n):
+        raise ValueError("every argument must have one entry per job")
+    jobs, keep, out = [], [], []
+    for j in range(n):
+        e = encs[j]
+        img = None if images[j] is None else _byte_view(images[j])
+        if img is not None and img.size < caps[j] * e * WRITTEN_BYTES_WIDTH:
+            raise ValueError(f"job {j}: the image is smaller than row_capacity x enc elements")
+        kb = np.zeros(0, np.uint64) if known_bad[j] is None else \
+            np.ascontiguousarray(np.asarray(known_bad[j], np.uint64).reshape(-1))
+        col_status = np.zeros(max(e, 1), np.uint8)
+        row_status = np.zeros(max(rows[j], 1), np.uint8) if want_row_status else None
+        keep.append((img, kb))
+        jobs.append(N.PosLocateJob(_addr(img), pres[j], e, rows[j], caps[j], _addr(kb) if kb.size else None,
+                                   int(kb.size), _addr(col_status), _addr(row_status), 0, 0, 0, 0))
+        out.append({"col_status": col_status[:max(e, 0)],
+                    "row_status": row_status[:rows[j]] if want_row_status else None})
+    arr = (N.PosLocateJob * max(n, 1))(*jobs)
+    _raise(N.load().lcpc_pos_locate_files_grouped(arr if n else None, n))
+    del keep
+    for j, o in enumerate(out):
+        o["status"] = int(arr[j].status)
+        o["n_bad_cols"] = int(arr[j].n_bad_cols)
+        o["n_dirty_rows"] = int(arr[j].n_dirty_rows)
+        o["n_unlocatable_rows"] = int(arr[j].n_unlocatable_rows)
+        if o["status"]:
+            o["col_status"] = o["row_status"] = o["n_bad_cols"] = o["n_dirty_rows"] = o["n_unlocatable_rows"] = None
+    return out
+
+
 def field_to_montgomery(values, field: int = FT63) -> np.ndarray:
     """lcpc_field_to_montgomery: (v R) mod p per 64-bit word, R = 2^64 (Ft63 only): canonical values,
     as a `.porenc` holds them, to the Montgomery words a commitment opens.  Same shape as `values`."""

@@ -1592,11 +1592,24 @@ class FileHandler:
     def _locate_report(self, report: ScrubReport) -> ScrubReport:
         """The locate half of scrub(locate=True) over a report of the tree's findings."""
         try:
-            status = self._locate_into(report)
-            if not report.bad_columns and not report.tree_consistent:
-                report.noncanonical_columns = [int(c) for c in np.flatnonzero(status == 2)]
+            with open(self.encoded_file_handle, "rb") as f:
+                located = self._reader(f).locate_damaged_columns()
         except UnrecoverableError:  # more non-canonical columns than the code's redundancy
+            located = None
+        return self._fill_locate_report(report, located)
+
+    def _fill_locate_report(self, report: ScrubReport, located) -> ScrubReport:
+        """located: (col_status, unlocatable_rows) of locate_damaged_columns with no known columns (this
+        file's own call, or the grouped locate of repair_files), or None where that is
+        unrecoverable."""
+        if located is None:
             report.located_columns, report.unlocatable_rows = [], self.rows_written
+            return report
+        status, n_unloc = located
+        report.located_columns = [int(c) for c in np.flatnonzero(status)]
+        report.unlocatable_rows = int(n_unloc)
+        if not report.bad_columns and not report.tree_consistent:
+            report.noncanonical_columns = [int(c) for c in np.flatnonzero(status == 2)]
         return report
 
     def scrub(self, expected_root: Optional[bytes] = None, locate: bool = False) -> ScrubReport:
@@ -1615,9 +1628,29 @@ class FileHandler:
         syndromes name are recomputed, and the result is written only if the tree over all column
         digests folds to expected_root -- or, with no expected_root, equals the tree of a fresh
         encode of the raw file.  The code's self-consistency alone is never an anchor."""
-        w, pre = self.encoded_size, self.pre_encoded_size
         report = self._scrub_state_located(expected_root)
         raw_tree = self._raw_file_tree()
+
+        def recompute(bad):
+            w = self.encoded_size
+            with open(self.encoded_file_handle, "rb") as f:
+                reader = self._reader(f)
+                cols, rdig = reader.repair_columns(bad) if bad else (None, None)
+                # the digests of every column as the file holds it; the located ones are replaced below
+                _, digests = reader._scrub(np.zeros((w, DIGEST_BYTES), np.uint8))
+            digests = digests.copy()
+            if bad:
+                digests[bad] = rdig
+            return cols, MerkleTree.new(digests)
+        return self._apply_located(expected_root, report, raw_tree, recompute)
+
+    def _apply_located(self, expected_root: Optional[bytes], report: ScrubReport, raw_tree: Optional[MerkleTree],
+                       recompute) -> ScrubReport:
+        """The trust rule and all writes of _repair_located over a located scrub state (this file's own, or
+        the grouped passes' of repair_files).  recompute(located columns) gives (their recomputed columns or
+        None with none located, the tree over the digests of all columns with the recomputed ones in place):
+        this file's own calls, or what a grouped repair already returned."""
+        w, pre = self.encoded_size, self.pre_encoded_size
         if report.unlocatable_rows:
             raise UnrecoverableError(f"{report.unlocatable_rows} rows hold more wrong elements than can be located")
         bad = report.located_columns
@@ -1625,15 +1658,7 @@ class FileHandler:
             raise UnrecoverableError(f"{len(bad)} columns located as damaged (at most {w - pre} can be recomputed)")
         if expected_root is None and raw_tree is None:
             raise UnrecoverableError("no expected_root was given and the raw file cannot vouch for the repair")
-        with open(self.encoded_file_handle, "rb") as f:
-            reader = self._reader(f)
-            cols, rdig = reader.repair_columns(bad) if bad else (None, None)
-            # the digests of every column as the file holds it; the located ones are replaced below
-            _, digests = reader._scrub(np.zeros((w, DIGEST_BYTES), np.uint8))
-        digests = digests.copy()
-        if bad:
-            digests[bad] = rdig
-        new_tree = MerkleTree.new(digests)
+        cols, new_tree = recompute(bad)
         if expected_root is not None:
             if new_tree.root() != bytes(expected_root):
                 raise UnrecoverableError("the located repair does not fold to expected_root")
@@ -1804,10 +1829,37 @@ def _close_map(mm) -> None:
         pass
 
 
+_OWN_LOCATE = object()   # _locate_grouped: the grouped pass gave no answer; the file's handler locates
+
+
+def _locate_grouped(handlers, images, noncanon, keys) -> dict:
+    """One lcpc_pos_locate_files_grouped call over mapped images with the columns the scrub found to hold a
+    word that is not < p as known columns.  {key: what FileHandler._fill_locate_report takes} -- (col_status
+    with those columns as 2, as the file's own locate_damaged_columns() names them, unlocatable rows), or
+    None where the call is unrecoverable for the file."""
+    from .pos import locate_files_grouped
+    if not handlers:
+        return {}
+    res = locate_files_grouped(images, [h.pre_encoded_size for h in handlers], [h.encoded_size for h in handlers],
+                               [h.rows_written for h in handlers], [h.row_capacity for h in handlers], noncanon)
+    out = {}
+    for key, o in zip(keys, res):
+        if o["status"] == LCPC_ERR_UNRECOVERABLE:
+            out[key] = None
+        elif o["status"]:
+            out[key] = _OWN_LOCATE
+        else:
+            status = o["col_status"].copy()
+            status[status == 3] = 2
+            out[key] = (status, o["n_unlocatable_rows"])
+    return out
+
+
 def _scrub_files_batch(handlers, roots, locate: bool, states: Optional[list] = None) -> List[ScrubReport]:
     """states (repair_files): a list that gets, per file, what FileHandler._scrub_state returns beside the
-    report -- (stored tree, column digests, raw file's tree or None) -- or None for a file without a usable
-    tree, which is then no error here either."""
+    report -- (stored tree, column digests, raw file's tree or None) -- and the columns that hold a word that
+    is not < p; the stored tree is None for a file without a usable tree file, which is then no error here
+    either (its digests are those of the columns as they stand, its raw file is still encoded)."""
     from .pos import encode_files_grouped_into, scrub_files_grouped
     trees: List[Optional[MerkleTree]] = []
     for h in handlers:
@@ -1846,7 +1898,7 @@ def _scrub_files_batch(handlers, roots, locate: bool, states: Optional[list] = N
     files, maps, datas, who = [], [], [], []
     try:
         for i, h in enumerate(handlers):
-            if trees[i] is None:
+            if trees[i] is None and states is None:
                 continue
             try:
                 if os.path.getsize(h.unencoded_file_handle) != h.total_data_bytes:
@@ -1892,7 +1944,8 @@ def _scrub_files_batch(handlers, roots, locate: bool, states: Optional[list] = N
                 h._locate_report(report)
         out.append(report)
         if states is not None:
-            states.append(None if tree is None else (tree, r["digests"], None if raw is None else MerkleTree(raw)))
+            states.append((tree, r["digests"], None if raw is None else MerkleTree(raw),
+                           [int(c) for c in np.flatnonzero(status == 2)]))
     return out
 
 
@@ -1917,6 +1970,32 @@ def scrub_files(handlers, expected_roots=None, locate: bool = False) -> List[Scr
 
 
 # -- grouped repair
+def _map_images(handlers):
+    """(files, maps, images) of the handlers' `.porenc` files mapped read-only; _unmap gives them back"""
+    files, maps, images = [], [], []
+    try:
+        for h in handlers:
+            need = h.row_capacity * h.encoded_size * WRITTEN_BYTES_WIDTH
+            f = open(h.encoded_file_handle, "rb")
+            files.append(f)
+            mm = mmap.mmap(f.fileno(), need, access=mmap.ACCESS_READ) if need else None
+            maps.append(mm)
+            images.append(np.frombuffer(mm, np.uint8) if need else None)
+    except BaseException:
+        _unmap(files, maps, images)
+        raise
+    return files, maps, images
+
+
+def _unmap(files, maps, images) -> None:
+    del images[:]
+    for mm in maps:
+        if mm is not None:
+            _close_map(mm)
+    for f in files:
+        f.close()
+
+
 def _repair_files_batch(handlers, roots, locate: bool) -> list:
     from .pos import repair_files_grouped
     states: list = []
@@ -1924,20 +2003,12 @@ def _repair_files_batch(handlers, roots, locate: bool) -> list:
     # one grouped repair for the files the tree can mend: an anchor, and 1 .. enc - pre bad columns
     who = []
     for i, (h, root, report, st) in enumerate(zip(handlers, roots, reports, states)):
-        if st is not None and (root is not None or report.tree_consistent) and \
+        if st[0] is not None and (root is not None or report.tree_consistent) and \
                 1 <= len(report.bad_columns) <= h.encoded_size - h.pre_encoded_size:
             who.append(i)
     repaired = {}
-    files, maps, images = [], [], []
+    files, maps, images = _map_images([handlers[i] for i in who])
     try:
-        for i in who:
-            h = handlers[i]
-            need = h.row_capacity * h.encoded_size * WRITTEN_BYTES_WIDTH
-            f = open(h.encoded_file_handle, "rb")
-            files.append(f)
-            mm = mmap.mmap(f.fileno(), need, access=mmap.ACCESS_READ) if need else None
-            maps.append(mm)
-            images.append(np.frombuffer(mm, np.uint8) if need else None)
         if who:
             res = repair_files_grouped(
                 images, [handlers[i].pre_encoded_size for i in who], [handlers[i].encoded_size for i in who],
@@ -1947,27 +2018,94 @@ def _repair_files_batch(handlers, roots, locate: bool) -> list:
                 if o["status"] == 0:     # (a file the grouped pass could not mend takes its own handler's path)
                     repaired[i] = (o["cols"], o["digests"], o["tree"])
     finally:
-        del images
-        for mm in maps:
-            if mm is not None:
-                _close_map(mm)
-        for f in files:
-            f.close()
-    out = []
+        _unmap(files, maps, images)
+    out: list = [None] * len(handlers)
+    fallback = []            # locate=True: the files whose tree path raised what repair() answers by locating
     for i, (h, root, report, st) in enumerate(zip(handlers, roots, reports, states)):
         try:
-            if st is None:       # no usable tree file: the handler's own path says what that means
-                out.append(h.repair(expected_root=root, locate=locate))
+            if st[0] is None:       # no usable tree file: the handler's own path says what that means
+                if locate:
+                    try:
+                        h._stored_tree()
+                    except (UnrecoverableError, FileNotFoundError):
+                        fallback.append(i)
+                        continue
+                out[i] = h.repair(expected_root=root, locate=locate)
                 continue
             try:
-                out.append(h._apply_repair(root, report, *st, repaired=repaired.get(i)))
+                out[i] = h._apply_repair(root, report, *st[:3], repaired=repaired.get(i))
             except UnrecoverableError:
                 if not locate:
                     raise
-                out.append(h._repair_located(root))
+                fallback.append(i)
         except (UnrecoverableError, OSError) as e:
-            out.append(e)
+            out[i] = e
+    if fallback:
+        _repair_located_grouped(handlers, roots, reports, states, fallback, out)
     return out
+
+
+def _located_is_repairable(h, report, root, raw_tree) -> bool:
+    """whether FileHandler._apply_located gets as far as recomputing the located columns (none among them:
+    the tree over the columns as they stand)"""
+    return not report.unlocatable_rows and \
+        len(report.located_columns) <= h.encoded_size - h.pre_encoded_size and (root is not None or raw_tree is not None)
+
+
+def _repair_located_grouped(handlers, roots, reports, states, who, out) -> None:
+    """FileHandler._repair_located for the files `who` of a batch in grouped passes: one grouped locate (the
+    columns the scrub found to hold a word that is not < p as known columns), one grouped repair with the
+    located columns as the erasure set, the scrub's digests of all columns as leaves and the tree wanted,
+    then FileHandler._apply_located per file -- the trust rule and all writes -- against expected_root or
+    the raw file's tree of the batch's grouped ingest.  A file the grouped passes cannot answer takes its
+    handler's own _repair_located."""
+    from .pos import repair_files_grouped
+    try:
+        files, maps, images = _map_images([handlers[i] for i in who])
+    except OSError:
+        for i in who:        # a `.porenc` that cannot be opened: every file says for itself what it raises
+            try:
+                out[i] = handlers[i]._repair_located(roots[i])
+            except (UnrecoverableError, OSError) as e:
+                out[i] = e
+        return
+    mended = {}
+    try:
+        located = _locate_grouped([handlers[i] for i in who], images, [states[i][3] for i in who], who)
+        rep, rep_images = [], []
+        for i, img in zip(who, images):
+            h = handlers[i]
+            if located[i] is _OWN_LOCATE:
+                continue
+            h._fill_locate_report(reports[i], located[i])
+            if _located_is_repairable(h, reports[i], roots[i], states[i][2]):
+                rep.append(i)
+                rep_images.append(img)
+        if rep:
+            res = repair_files_grouped(
+                rep_images, [handlers[i].pre_encoded_size for i in rep], [handlers[i].encoded_size for i in rep],
+                [handlers[i].rows_written for i in rep], [handlers[i].row_capacity for i in rep],
+                [reports[i].located_columns for i in rep], [states[i][1] for i in rep], want_cols=True, want_tree=True)
+            for i, o in zip(rep, res):
+                if o["status"] == 0:
+                    mended[i] = (o["cols"], MerkleTree(o["tree"]))
+        del rep_images
+    finally:
+        _unmap(files, maps, images)
+    for i in who:
+        h, report = handlers[i], reports[i]
+        try:
+            if located[i] is _OWN_LOCATE or \
+                    (i not in mended and _located_is_repairable(h, report, roots[i], states[i][2])):
+                out[i] = h._repair_located(roots[i])        # the grouped passes gave no answer
+                continue
+
+            def recompute(bad, i=i):
+                cols, tree = mended[i]
+                return (cols if bad else None), tree
+            out[i] = h._apply_located(roots[i], report, states[i][2], recompute)
+        except (UnrecoverableError, OSError) as e:
+            out[i] = e
 
 
 def repair_files(handlers, expected_roots=None, locate: bool = False) -> list:
@@ -1980,7 +2118,10 @@ def repair_files(handlers, expected_roots=None, locate: bool = False) -> list:
     lcpc_pos_repair_files_grouped call per batch, with the scrub's digests as leaves and the tree
     wanted; FileHandler._apply_repair then applies _repair_by_tree's trust rules and writes.  A file
     the grouped repair cannot mend (too many columns, no anchor, an unrecoverable verdict, no usable tree
-    file, the locate=True fallback) takes its own handler's calls from there."""
+    file with locate=False) takes its own handler's calls from there.  With locate=True the files whose tree
+    path raised -- a tree file that is missing, truncated or overwritten among them -- go through one
+    grouped locate and one grouped repair per batch (_repair_located_grouped) and
+    FileHandler._apply_located, the trust rule and the writes of _repair_located."""
     handlers = list(handlers)
     roots = [None] * len(handlers) if expected_roots is None else list(expected_roots)
     if len(roots) != len(handlers):
